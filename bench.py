@@ -14,12 +14,18 @@ patch 256 (=16^2) -> 196 tokens + CLS, hidden 768, 12 heads, 12 layers, MLP 3072
 MSE loss (what baseline.yaml's loss.name 'mae' resolves to), AdamW lr 1e-3 wd 0.  Weak scaling: 256 images per GPU
 (default; `--global-batch 256` fixes the total instead: strong scaling, 256 / N images per GPU).
 
-Rank 0 prints ONE JSON line.  Besides the driver's fields it carries
+Rank 0 prints ONE JSON line: metric / value / unit / higher_is_better / dtype / ms_per_step (the median timed step) and the
+per-step `timing`.  A plain run does only that: set up, warm up, time the K steps, print.  With `--full` the line also carries
+what takes runs of its own after the headline (null without it):
   roofline     -- the dominant kernel (by summed time) of the step: algorithmic FLOPs per launch / mean launch duration,
-                  measured live with HIP events on the launch stream during the timed steps, against the dense bf16
+                  measured with HIP events on the launch stream in a repetition of the timed steps, against the dense bf16
                   MFMA peak (2.5 PFLOP/s, MI355X_MICROARCH.md); `step_frac` is the whole-step model-FLOPs utilisation.
   cpu_baseline -- the CPU oracle (oracle/refvit.py, plain fp32 torch: a "port") timed on this host's cores on a bounded
                   sample of the same workload (rank 0, N=1 only).
+  input_pipeline, secondary (N=1) and comm (N>1) -- see input_pipeline_probe, secondary_workloads and comm_probe.
+
+`--dump-outputs DIR` writes what the last timed step computed (loss, gradient norm, samples of the updated parameters and of
+the gradients) to DIR/*.npy; the inputs, weights and dropout stream are seeded, so equal arguments give equal inputs.
 """
 from __future__ import annotations
 
@@ -334,7 +340,20 @@ def main():
     ap.add_argument("--no-input-probe", action="store_true", help="skip the host-staged / device-gather input measurements")
     ap.add_argument("--launch-check", action="store_true",
                     help="rank plumbing only (no GPU): every rank joins a gloo group, rank 0 prints {world, sum of ranks}")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure what the headline does not need: the per-GEMM event brackets "
+                         "(`roofline`, `kernels`), `input_pipeline`, `secondary` (C5, C2), `cpu_baseline` and, with N > 1, the "
+                         "`comm` probe.  Off by default: a plain run sets up, warms up, times the K steps and prints its line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32): `loss`, `grad_norm` (the "
+                         "global gradient norm before clipping), and a fixed seeded sample of the updated parameters "
+                         "(`params`) and of the step's gradients (`grads`) at the same indices (every element when the model "
+                         "has at most 4 Mi parameters)")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
+    if not args.full:  # a plain run measures the headline only; the extras below stay null in its line
+        args.no_kernel_timing = args.no_input_probe = args.no_secondary = args.no_cpu_baseline = args.no_comm_probe = True
 
     from vit_amd.launch import launch_ranks, under_launcher  # imports neither torch nor HIP
 
@@ -477,6 +496,8 @@ def main():
     gc.callbacks.remove(gc_cb)
     step_ms = [marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps)]
     two_streams = module.model.engine.side_stream is not None  # what the timed steps ran with (engine: overlap_dw "auto")
+    if args.dump_outputs and rank == 0:  # before anything below takes another step
+        dump_outputs(args.dump_outputs, module, trainer, loss)
     # The per-GEMM HIP-event brackets (two event records around each of ~170 vit_gemm calls per step) are installed ONLY for
     # this repetition of the same steps (same state, same inputs): the clean region above ran the library's own vf.gemm, so
     # `value` carries no event record beyond the K + 1 step marks.  `roofline.instrumented_ms_per_step` is what the bracketed
@@ -664,6 +685,37 @@ def main():
     if exchanging:
         torch.distributed.barrier()
         torch.distributed.destroy_process_group()
+
+
+DUMP_MAX_ELEMS = 1 << 22  # per sampled array: 16 MB of float32, 2 x 16 MB + two scalars in all
+
+
+def dump_outputs(out_dir, module, trainer, loss):
+    """`--dump-outputs`: what a caller of the timed step receives from its last step -- the loss it returns, the updated
+    parameters and the gradients it left (the engine's flat fp32 buffers) -- as float32 .npy files.  A model larger than
+    DUMP_MAX_ELEMS parameters is sampled at indices drawn from a fixed seed, so that two builds of the project write the same
+    elements for the same arguments."""
+    import numpy as np
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    eng = module.model.engine
+    torch.cuda.synchronize()
+    n = eng.flat.numel()
+    idx = None
+    if n > DUMP_MAX_ELEMS:
+        g = torch.Generator(device="cpu").manual_seed(20240611)
+        idx = torch.randint(0, n, (DUMP_MAX_ELEMS,), generator=g).sort().values.to(eng.flat.device)
+    arrays = {"loss": loss.detach().float().reshape(1)}
+    gn = getattr(trainer.optimizer, "last_grad_norm", None)
+    if gn is not None:
+        arrays["grad_norm"] = gn.detach().float().sqrt().reshape(1)  # the optimizer keeps the squared norm
+    for name, buf in (("params", eng.flat), ("grads", eng.grads)):
+        if buf is not None:
+            arrays[name] = buf.detach().float() if idx is None else buf.detach().float()[idx]
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), t.cpu().numpy().astype(np.float32))
+    log(f"outputs of the last timed step written to {out_dir}: {', '.join(sorted(arrays))}")
 
 
 def run_cpu_baseline(workload, L, P, D, layers, heads):

@@ -190,8 +190,8 @@ def test_bench_two_ranks_reports_the_multi_gpu_probe():
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2",
-                        "--workload", "vit_tiny16_32", "--batch", "512", "--no-cpu-baseline"], env=env, capture_output=True, text=True,
-                       timeout=900)
+                        "--workload", "vit_tiny16_32", "--batch", "512", "--no-cpu-baseline", "--full"], env=env,
+                       capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]

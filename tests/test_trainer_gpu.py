@@ -753,7 +753,7 @@ def test_bench_contract_single_gpu(dev):
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "VIT_DIST_SINGLE"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "6", "--warmup", "2", "--workload", "vit_tiny16_32",
-                        "--batch", "256"], env=env, capture_output=True, text=True, timeout=900)
+                        "--batch", "256", "--full"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -778,6 +778,45 @@ def test_bench_contract_single_gpu(dev):
     assert abs(doc["ms_per_step"] - 0.5 * (srt[2] + srt[3])) < 2e-3
     assert abs(doc["value"] - 256 / (doc["ms_per_step"] * 1e-3)) <= 1e-3 * doc["value"]
     assert abs(doc["mean_ms_per_step"] * 6 - tm["region_wall_ms"]) < 1e-2 * tm["region_wall_ms"]
+
+
+def test_bench_plain_run_and_dump_outputs(dev, tmp_path):
+    """A plain `bench.py` run (no --full) times exactly --steps steps and measures nothing else: the extras are null in its line.
+    `--dump-outputs DIR` writes the last timed step's loss, gradient norm and the updated parameters / gradients as float32
+    .npy files; two runs with the same arguments start from the same inputs, so their first steps' outputs agree."""
+    import json
+    import subprocess
+    import sys
+
+    import numpy as np
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "VIT_DIST_SINGLE"):
+        env.pop(k, None)
+
+    def run(steps, out):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", str(steps), "--warmup", "0", "--workload",
+                            "vit_tiny16_32", "--dump-outputs", str(out)], env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, r.stdout[-2000:]
+        return json.loads(lines[0]), {f[:-4]: np.load(os.path.join(out, f)) for f in os.listdir(out)}
+
+    doc, a = run(3, tmp_path / "a")
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in doc, k
+    assert doc["steps"] == 3 and len(doc["timing"]["step_ms"]) == 3 and doc["ms_per_step"] > 0
+    assert all(doc[k] is None for k in ("roofline", "cpu_baseline", "secondary", "input_pipeline", "comm")) and doc["kernels"] == {}
+    assert set(a) == {"loss", "grad_norm", "params", "grads"}
+    assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in a.values())
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert abs(float(a["loss"][0]) - doc["config"]["final_loss"]) <= 1e-6 * abs(doc["config"]["final_loss"])
+    assert a["params"].shape == a["grads"].shape and float(np.abs(a["grads"]).max()) > 0
+    _, b = run(1, tmp_path / "b")
+    _, c = run(1, tmp_path / "c")
+    for k in b:
+        np.testing.assert_allclose(b[k], c[k], rtol=1e-5, atol=1e-6, err_msg=k)
 
 
 @pytest.mark.parametrize("opt_cfg", [{"type": "AdamW", "lr": 1e-3, "lr_sch": "onecycle"}, {"type": "SGD", "lr": 1e-2}])
@@ -867,8 +906,8 @@ def test_bench_line_carries_secondary_and_input_pipeline(dev):
     env = dict(os.environ)
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "VIT_DIST_SINGLE"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "4", "--warmup", "2", "--no-cpu-baseline"],
-                       env=env, capture_output=True, text=True, timeout=900)
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "4", "--warmup", "2", "--no-cpu-baseline",
+                        "--full"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, r.stdout[-2000:]

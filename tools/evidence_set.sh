@@ -1,8 +1,8 @@
 set -e
 OUT=${1:-gpurun_out/evidence}
 mkdir -p $OUT
-python bench.py > $OUT/bench_c3.json 2> $OUT/bench_c3.err
-python bench.py --workload vit_l16_384 --no-cpu-baseline --no-input-probe > $OUT/bench_c5.json 2> $OUT/bench_c5.err
+python bench.py --full > $OUT/bench_c3.json 2> $OUT/bench_c3.err
+python bench.py --full --workload vit_l16_384 --no-cpu-baseline --no-input-probe > $OUT/bench_c5.json 2> $OUT/bench_c5.err
 R=$GRAFT_REPO_ROOT
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats -d $R/$OUT/prof3 -o c3 -- python3 $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-kernel-timing --no-overlap --no-secondary --no-input-probe > $R/$OUT/prof3.log 2>&1
