@@ -48,7 +48,7 @@ const char* vit_last_error(void);
 int vit_create(vit_handle* out, int device);
 int vit_destroy(vit_handle h);
 int vit_set_workspace(vit_handle h, void* ws, size_t bytes);
-/* Process-wide tuning / diagnostics knobs (never change results beyond rounding order):
+/* Process-wide options (none changes results beyond rounding order):
  *   "gemm_core": 0 = generic 128x128 core only, 1 = automatic (default): tile-aligned problems (M, N multiples of 256, K of
  *                64) run the 256x256x64 ping-pong core (wave halves one barrier out of phase: LOAD segment beside MFMA
  *                segment, ring of 8 half-tiles, 4 in flight); 5 = the same choice named explicitly.
@@ -56,38 +56,15 @@ int vit_set_workspace(vit_handle h, void* ws, size_t bytes);
  *   "attn_bwd_fused": attention backward form: non-zero (default 4) = the pair-pipelined single kernel where it fits (head_dim
  *                64, 64 <= T <= 208), the dQ + dK/dV pair elsewhere; 0 = the dQ + dK/dV pair everywhere.  (The values 1 .. 3
  *                named the single-kernel forms of round 2, removed in round 4; they are accepted and mean the default.)
- *   "attn_bwd_dma": 1 (default) = the dQ + dK/dV pair at head_dim 64 stages its LDS images by LDS-DMA in reading order with
- *                per-tile counted waits (the first tile's arithmetic starts when 16 KiB have landed); 0 = register-staged
- *                images, all in before the loop starts.  Same results bit for bit.
- *   "attn32_mfma": 1 (default) = fp32 attention (precision '32') at head_dim 64 runs on the f32-input matrix instructions
- *                (v_mfma_f32_16x16x4_f32: exact f32 products and accumulation); 0 = the one-wave-per-row vector kernels.
- *   "gemm_ngroups": 1 (default) = XCDs 0-3 / 4-7 walk the lower / upper half of the N-tiles when the weights exceed an L2.
- *   "attn_res_max_t": longest sequence the resident attention kernels take (default 592 = what fits the LDS at head_dim
- *                64); longer ones, or everything with 0, go to the tiled kernels.
- *   "gemm_half_tail": 1 = the tiles of a partial last round of a multi-round ping-pong GEMM (bias/dropout -> bf16
- *                and plain dX epilogues; 2 = the GELU epilogue too) run in a second launch as half tiles, two workgroups per
- *                tile; 0 (default since r05) = one launch: the half tiles shorten that product but cost more CU-time, and
- *                inside the power-limited training step the single launch is faster overall.  Same results bit for bit.
  *   "reserve_cus": 0 (default) .. 128 = the one-workgroup-per-CU kernels (ping-pong GEMMs, pair-pipelined attention backward) size
  *                their grids for that many fewer CUs, leaving room for a collective's kernels that overlap them (data-parallel
  *                runs; bench.py --reserve-cus).
- *   "attn_fwd_waves": 12 (default) or 8 = most waves per workgroup of the resident attention forward; only changes the launch
- *                where one workgroup fills the LDS (head_dim 64, T > ~290): 577 tokens run as 2 x 10 waves instead of 3 x 7.
- *   "gemm_split_tail": 1 (default) = a SHORT tail (at most a quarter of the workgroup slots) of a long-K product runs as K-slices of
- *                whole tiles + a small reduce-and-epilogue kernel instead of half tiles (ViT-L: 36 of 292 tiles at K = 3072 /
- *                4096); needs 4 x slices x 65536 bytes of workspace per tail tile, else the half-tile launch is used; 0 = never.
- *   "gemm_balance_wgs": 1 (default) = a multi-round ping-pong GEMM launches ceil(tiles / rounds) workgroups instead of 256
- *                (same makespan in tile-times, idle CUs instead of CUs that idle for the last round); 0 = always 256.
- *   "gemm_pp_slots": 8 (the only value since round 2: the 10-slot ring, 96 KiB of operand loads in flight per CU, measured
- *                0-15 % slower on the ViT-B shapes and was removed with the K-loop rewrite; any other value is VIT_ERR_ARG).
- *   (Timing diagnostics that switch pieces of a kernel off are compile-time variant builds -- python -m vit_amd.build
- *   --defs ... --tag ... -- never a switch of this library: results are meaningless in such a build.)
- *                Returns VIT_ERR_ARG for an unknown name. */
+ * The first three select the reference paths the tests compare against.  Returns VIT_ERR_ARG for an unknown name. */
 int vit_set_option(const char* name, int value);
 /* Per-handle launch geometry: what changes HOW MANY workgroups a call through this handle launches belongs to the handle, so
  * that two engines of one process (training + evaluation, an engine's second-stream handle) do not depend on the order
  * in which they were configured.  "reserve_cus": -1 (default) = follow the process-wide value above, 0 .. 128 = this handle's
- * own.  The remaining vit_set_option knobs select between bit-identical kernel forms for A/B runs and stay process-wide.
+ * own.  The remaining vit_set_option options select kernel forms and stay process-wide.
  * Reference: none (Lightning's 'ddp' overlaps NCCL with kernels that do not own whole SMs, src/hardware_utils.py:86-95). */
 int vit_handle_set_option(vit_handle h, const char* name, int value);
 

@@ -659,74 +659,48 @@ def test_attention_bwd_fused_colsum(dev, B, H, T, dh):
             _cabi.set_option("attn_split", 2)
 
 
-@pytest.mark.parametrize("M,N,K", [(256 * 100, 768, 256), (256 * 197, 768, 768), (256 * 90, 1024, 512)])
-def test_gemm_half_tile_tail(dev, M, N, K):
-    """Tile counts that leave a partial last round (300, 591, 360 tiles on 256 workgroups): those tiles run in a second
-    launch as half tiles (two workgroups per tile, two phases per K-tile).  Same products in the same order per element:
-    the outputs must equal the single-launch ones bit for bit, for the forward (bias + dropout) and the dX layouts."""
+@pytest.mark.parametrize("M,N,K", [(256 * 100, 768, 256), (256 * 197, 768, 768), (256 * 90, 1024, 512),
+                                   (256 * 73, 1024, 4096), (256 * 73, 1024, 3072), (256 * 70, 1024, 4096)])
+def test_gemm_partial_last_round(dev, M, N, K):
+    """Tile counts that leave a partial last round on 256 workgroups, short-K (300, 591, 360 tiles) and long-K (ViT-L: 292 =
+    one round + 36; 280 = 256 + 24): those tiles run in the same single launch as the full rounds.  The forward (bias +
+    dropout, bias, plain, GELU with its saved derivative) and the dX layout against the fp32 references, on the whole output
+    and on the rows of the last tiles; the dropout zeros where the mask drops; two runs equal bit for bit."""
     import vit_amd.functional as vf
-    from vit_amd import _cabi
-
-    x, W = bf(randn((M, K), dev, 150)), bf(randn((N, K), dev, 151, 0.1))
-    bias = randn((N,), dev, 152)
-    dy, W2 = bf(randn((M, K), dev, 153)), bf(randn((K, N), dev, 154, 0.1))
-    drop = (0.1, 5, 6)
-    outs = {}
-    for mode in (0, 1):
-        _cabi.set_option("gemm_half_tail", mode)
-        try:
-            outs[mode] = (vf.gemm(x, W, M=M, N=N, K=K, bias=bias, dropout=drop),
-                          vf.gemm(x, W, M=M, N=N, K=K),
-                          vf.gemm(dy, W2, M=M, N=N, K=K, b_trans=True))
-        finally:
-            _cabi.set_option("gemm_half_tail", 0)  # the default since r05
-    for a, b in zip(outs[0], outs[1]):
-        assert torch.equal(a, b)
-    # the GELU epilogue (with the saved derivative) through the same two launches
     from vit_amd._cabi import ACT_GELU_GRAD
-    ge = {}
-    for mode in (0, 2):
-        _cabi.set_option("gemm_half_tail", mode)
-        try:
-            aux = torch.empty((M, N), dtype=torch.bfloat16, device=dev)
-            ge[mode] = (vf.gemm(x, W, M=M, N=N, K=K, bias=bias, act=ACT_GELU_GRAD, aux_out=aux), aux)
-        finally:
-            _cabi.set_option("gemm_half_tail", 0)  # the default since r05
-    assert torch.equal(ge[0][0], ge[2][0]) and torch.equal(ge[0][1], ge[2][1])
-    assert rel(outs[1][1], x.float() @ W.float().t()) < 4e-3
-    assert rel(outs[1][2], dy.float() @ W2.float()) < 4e-3
 
-
-@pytest.mark.parametrize("M,N,K", [(256 * 73, 1024, 4096), (256 * 73, 1024, 3072), (256 * 70, 1024, 4096)])
-def test_gemm_split_k_tail(dev, M, N, K):
-    """A short tail of a long-K product (ViT-L: 292 tiles = one round of 256 + 36; 280 = 256 + 24) runs as K-slices of whole
-    tiles + a reduce-and-epilogue kernel.  Same dropout mask and bias as the half-tile form; the sums are ordered differently
-    (slices of K added in f32), so the bf16 outputs agree to rounding, and both agree with the fp32 product."""
-    import vit_amd.functional as vf
-    from vit_amd import _cabi
-
-    x, W = bf(randn((M, K), dev, 160)), bf(randn((N, K), dev, 161, 0.05))
-    bias = randn((N,), dev, 162)
-    dy, W2 = bf(randn((M, K), dev, 163)), bf(randn((K, N), dev, 164, 0.05))
+    scale = 0.1 if K <= 1024 else 0.05
+    x, W = bf(randn((M, K), dev, 150)), bf(randn((N, K), dev, 151, scale))
+    bias = randn((N,), dev, 152)
+    dy, W2 = bf(randn((M, K), dev, 153)), bf(randn((K, N), dev, 154, scale))
     drop = (0.1, 5, 6)
-    outs = {}
-    for mode in (0, 1):
-        _cabi.set_option("gemm_split_tail", mode)
-        try:
-            outs[mode] = (vf.gemm(x, W, M=M, N=N, K=K, bias=bias, dropout=drop),
-                          vf.gemm(x, W, M=M, N=N, K=K, bias=bias),
-                          vf.gemm(dy, W2, M=M, N=N, K=K, b_trans=True))
-        finally:
-            _cabi.set_option("gemm_split_tail", 1)
-    tail = slice(M - 256 * 12, M)  # rows of the last tiles: the ones that went through the slices
-    for a, b in zip(outs[0], outs[1]):
-        assert torch.equal(a[:M - 256 * 12], b[:M - 256 * 12])  # the full rounds are the same launch either way
-        assert rel(a[tail], b[tail]) < 3e-3
-    assert ((outs[0][0] == 0) == (outs[1][0] == 0)).all()  # same dropout mask
-    assert rel(outs[1][1], x.float() @ W.float().t() + bias) < 4e-3
-    assert rel(outs[1][2], dy.float() @ W2.float()) < 4e-3
-    assert rel(outs[1][1][tail], (x.float() @ W.float().t() + bias)[tail]) < 4e-3
-    assert rel(outs[1][2][tail], (dy.float() @ W2.float())[tail]) < 4e-3
+
+    def run():
+        aux = torch.empty((M, N), dtype=torch.bfloat16, device=dev)
+        return (vf.gemm(x, W, M=M, N=N, K=K, bias=bias, dropout=drop),
+                vf.gemm(x, W, M=M, N=N, K=K, bias=bias),
+                vf.gemm(x, W, M=M, N=N, K=K),
+                vf.gemm(dy, W2, M=M, N=N, K=K, b_trans=True),
+                vf.gemm(x, W, M=M, N=N, K=K, bias=bias, act=ACT_GELU_GRAD, aux_out=aux), aux)
+
+    outs = run()
+    for a, b in zip(outs, run()):
+        assert torch.equal(a, b)
+    yd, yb, y, dx, yg, aux = outs
+    prod = x.float() @ W.float().t()
+    pre = (prod + bias).requires_grad_(True)
+    gelu = F.gelu(pre)
+    gelu.sum().backward()  # pre.grad = gelu'(pre)
+    mask = vf.dropout_bwd_cast(torch.ones((M, N), device=dev), drop).float()
+    assert torch.equal(yd == 0, mask == 0)  # same dropout mask
+    assert rel(yd, pre.detach() * mask) < 5e-3  # mask scale is bf16-rounded in this reconstruction
+    ref_dx = dy.float() @ W2.float()
+    tail = slice(M - 256 * 12, M)  # rows of the last tiles: the partial last round
+    for out, ref in ((yb, pre.detach()), (y, prod), (dx, ref_dx)):
+        assert rel(out, ref) < 4e-3
+        assert rel(out[tail], ref[tail]) < 4e-3
+    assert rel(yg, gelu.detach()) < 6e-3
+    assert rel(aux, pre.grad) < 4e-3
 
 
 @pytest.mark.parametrize("B,H,T,dh", [(1, 2, 197, 64), (1, 2, 577, 64), (1, 1, 640, 64)])

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Time the attention forward at the ViT-B shape (A/B runs of variant builds through VIT_AMD_LIB).
+"""Time the attention forward at the ViT-B shape (A/B runs of two builds, e.g. of two commits, through VIT_AMD_LIB).
 usage: python tools/fwd_ab.py [dropout=0.1] [B H T]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

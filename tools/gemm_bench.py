@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """GEMM microbenchmark over the ViT-B/16 (C3) shapes: every GEMM of one layer's forward + backward, each GEMM core
 (0 = generic 128x128 register-staged, 5 = the 256x256x64 ping-pong LDS-DMA core), interleaved rounds in ONE process, random data.
-Usage: python tools/gemm_bench.py [--rounds 5] [--cores 0,2,3]"""
+Usage: python tools/gemm_bench.py [--rounds 5] [--cores 0,5]"""
 import argparse
 import os
 import sys
@@ -21,15 +21,7 @@ def main():
     ap.add_argument("--M", type=int, default=50432)
     ap.add_argument("--only", default="", help="substring filter on the case names, e.g. 'fc1' or 'dX  fc2'")
     args = ap.parse_args()
-    cores = [c for c in args.cores.split(",")]  # "5" or "5s8" / "5s10": ping-pong core with an 8- / 10-slot ring
-    def select(c):  # "5", "5s10" (10-slot ring), "5b0" (always 256 workgroups), "5h0" (no half-tile tail launch)
-        core, _, half = c.partition("h")
-        core, _, bal = core.partition("b")
-        core, _, slots = core.partition("s")
-        _cabi.set_option("gemm_core", int(core))
-        _cabi.set_option("gemm_pp_slots", 8)  # the 10-slot ring is gone
-        _cabi.set_option("gemm_balance_wgs", int(bal) if bal else 1)
-        _cabi.set_option("gemm_half_tail", int(half) if half else 0)
+    cores = args.cores.split(",")
     dev = torch.device("cuda:0")
     M, D, F = args.M, 768, 3072
     g = torch.Generator(device="cpu").manual_seed(0)
@@ -65,7 +57,7 @@ def main():
     for r in range(args.rounds + 1):
         for name, (fn, fl) in cases.items():
             for c in cores:
-                select(c)
+                _cabi.set_option("gemm_core", int(c))
                 fn()
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record()
@@ -76,9 +68,6 @@ def main():
                 if r:
                     times[name][c].append(e0.elapsed_time(e1) / 3)
     _cabi.set_option("gemm_core", 1)
-    _cabi.set_option("gemm_pp_slots", 8)
-    _cabi.set_option("gemm_balance_wgs", 1)
-    _cabi.set_option("gemm_half_tail", 0)
     tot = {c: 0.0 for c in cores}
     print(f"{'case':48s} " + " ".join(f"core{c}: us / TF".rjust(20) for c in cores))
     for name, (fn, fl) in cases.items():

@@ -1,3 +1,5 @@
+"""Time layernorm_bwd_fused + its reducers for A/B runs of two builds through VIT_AMD_LIB.
+usage: python tools/ln_ab.py [M D]"""
 import os, sys, torch
 sys.path.insert(0, os.getcwd())
 import vit_amd.functional as vf
@@ -18,4 +20,4 @@ e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=Tr
 e0.record()
 for _ in range(50): run()
 e1.record(); torch.cuda.synchronize()
-print(os.environ.get("VIT_AMD_LIB", "prod").split("_")[-1], f"M={M} D={D} ln_bwd_fused + reducers: {e0.elapsed_time(e1) / 50 * 1e3:.1f} us", float(dgam.sum()), float(dbias.sum()))
+print(os.path.basename(os.environ.get("VIT_AMD_LIB", "libvit_amd.so")), f"M={M} D={D} ln_bwd_fused + reducers: {e0.elapsed_time(e1) / 50 * 1e3:.1f} us", float(dgam.sum()), float(dbias.sum()))

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Time layernorm_fwd_residual (x + bf16 delta -> xsum f32, y bf16) for A/B runs of variant builds (VIT_AMD_LIB).
+"""Time layernorm_fwd_residual (x + bf16 delta -> xsum f32, y bf16) for A/B runs of two builds through VIT_AMD_LIB.
 usage: python tools/lnf_ab.py [M D]"""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Time one attention-backward mode at the ViT-B shape (for A/B runs of variant builds through VIT_AMD_LIB).
+"""Time one attention-backward mode at the ViT-B shape (for A/B runs of two builds, e.g. of two commits, through VIT_AMD_LIB).
 usage: python tools/pipe_ab.py [mode=4] [dropout=0.1]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

@@ -1,6 +1,5 @@
 #!/bin/bash
-# one stream vs two streams (half-tail off) at several batch sizes: which launch mode does the tile count call for?
-export VIT_OPTIONS=gemm_half_tail=0
+# one stream vs two streams at several batch sizes: which launch mode does the tile count call for?
 for r in 1 2; do
 for b in 64 128 192 256 384 512; do
   for f in "" "--no-overlap"; do

@@ -18,8 +18,8 @@ struct vit_ctx {
 
 namespace vit {
 
-extern int g_gemm2_mode, g_pp_slots, g_balance_wgs, g_half_tail, g_split_tail, g_grp2;  // gemm2.hip
-extern int g_attn_split, g_attn_res_max_t, g_attn_bwd_fused, g_attn_fwd_waves, g_attn32_mfma, g_attn_bwd_dma;  // attention.hip
+extern int g_gemm2_mode;  // gemm2.hip
+extern int g_attn_split, g_attn_bwd_fused;  // attention.hip
 
 static thread_local char g_err[512] = "";
 thread_local char g_last_gemm[96] = "";  // symbol of the kernel the last vit_gemm on this thread launched
@@ -115,53 +115,12 @@ int vit_set_option(const char* name, int value) {
     vit::g_attn_bwd_fused = value;
     return VIT_OK;
   }
-  if (strcmp(name, "attn_bwd_dma") == 0) {
-    vit::g_attn_bwd_dma = value ? 1 : 0;
-    return VIT_OK;
-  }
   if (strcmp(name, "reserve_cus") == 0) {
     if (value < 0 || value > 128) {
       vit::set_error("vit_set_option: reserve_cus takes 0 .. 128");
       return VIT_ERR_ARG;
     }
     vit::g_reserve_cus = value;
-    return VIT_OK;
-  }
-  if (strcmp(name, "attn_fwd_waves") == 0) {
-    if (value != 8 && value != 12) {
-      vit::set_error("vit_set_option: attn_fwd_waves takes 8 or 12");
-      return VIT_ERR_ARG;
-    }
-    vit::g_attn_fwd_waves = value;
-    return VIT_OK;
-  }
-  if (strcmp(name, "attn32_mfma") == 0) {
-    vit::g_attn32_mfma = value;
-    return VIT_OK;
-  }
-  if (strcmp(name, "attn_res_max_t") == 0) {
-    vit::g_attn_res_max_t = value;
-    return VIT_OK;
-  }
-  if (strcmp(name, "gemm_split_tail") == 0) {
-    vit::g_split_tail = value;
-    return VIT_OK;
-  }
-  if (strcmp(name, "gemm_half_tail") == 0) {
-    vit::g_half_tail = value;
-    return VIT_OK;
-  }
-  if (strcmp(name, "gemm_ngroups") == 0) {
-    vit::g_grp2 = value;
-    return VIT_OK;
-  }
-  if (strcmp(name, "gemm_balance_wgs") == 0) {
-    vit::g_balance_wgs = value;
-    return VIT_OK;
-  }
-  if (strcmp(name, "gemm_pp_slots") == 0) {
-    if (value != 8) return VIT_ERR_ARG;  // the 10-slot ring (measured 0-15 % slower) was removed with the r02 loop rewrite
-    vit::g_pp_slots = value;
     return VIT_OK;
   }
   vit::set_error("vit_set_option: unknown option '%s'", name);
@@ -195,21 +154,3 @@ int vit_set_workspace(vit_handle h, void* ws, size_t bytes) {
 }
 
 }  // extern "C"
-
-#ifdef VIT_PP_DIAG
-// diagnostic twin build only (python -m vit_amd.build --diag; tools/pp_diag.py): switch pieces of the ping-pong K loop off
-namespace vit { extern int g_gemm2_debug; }
-extern "C" int vit_debug_pp_diag(int bits) {
-  vit::g_gemm2_debug = bits;
-  return 0;
-}
-#endif
-#ifdef VIT_PP_STAMP
-// diagnostic build only (python -m vit_amd.build --stamps N): where gemm3_kernel's workgroup `block` spends its cycles
-namespace vit { extern unsigned long long* g_pp_stamps; extern int g_pp_stamp_block; }
-extern "C" int vit_debug_pp_stamps(void* device_buf_64x_u64, int block) {
-  vit::g_pp_stamps = (unsigned long long*)device_buf_64x_u64;
-  vit::g_pp_stamp_block = block;
-  return 0;
-}
-#endif

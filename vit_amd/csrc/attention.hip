@@ -600,22 +600,6 @@ __device__ __forceinline__ u32x2 pack_lo(const f32x4& v, const u32x2& pk) {
   return (u32x2){pack2bf(v[0] - h0, v[1] - h1), pack2bf(v[2] - h2, v[3] - h3)};
 }
 
-#ifdef VIT_FWD_STAMP  // diagnostic build only (tools/fwd_stamps.py): where a wave's lifetime goes, one record per wave
-#define FWD_ST_WAVES (1 << 16)
-__device__ unsigned long long g_fwd_st[FWD_ST_WAVES * 8];
-#define FWD_ST(K)                                                                                   \
-  {                                                                                                 \
-    unsigned long long t_;                                                                          \
-    __builtin_amdgcn_sched_barrier(0);                                                              \
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");                     \
-    __builtin_amdgcn_sched_barrier(0);                                                              \
-    st_[K] = t_ - tprev_;                                                                           \
-    tprev_ = t_;                                                                                    \
-  }
-#else
-#define FWD_ST(K)
-#endif
-
 // The key loop of one wave: RQ 16-row query tiles (fragments qf) against the staged K / V images of a head; running max m,
 // row sums l and the transposed output accumulators ot are the caller's.  pre_pv() runs once, before the first V fragment read.
 template <int DH, int RQ, int TPC, class PrePV>  // TPC: the padded length 64 n + 16 when TPC - 16 < T <= TPC is known at compile time (208: ViT-B, 592: ViT-L), else 0
@@ -789,11 +773,6 @@ __device__ __forceinline__ void fwd_finish(const AttnArgs& p, const float (&m)[R
 template <int DH, int RQ, bool DMA, int TPC = 0, int HC = 0, int NSP = 0, int WPWC = 0>
 __global__ __launch_bounds__(768, 3) void attn_fwd_res_kernel(AttnArgs p) {
   resolve_drop(p.drop);
-#ifdef VIT_FWD_STAMP
-  unsigned long long tprev_, st_[5] = {0, 0, 0, 0, 0};
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tprev_)::"memory");
-  const unsigned long long tstart_ = tprev_;
-#endif
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, l15 = lane & 15, lg = lane >> 4;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -853,9 +832,7 @@ __global__ __launch_bounds__(768, 3) void attn_fwd_res_kernel(AttnArgs p) {
   } else {
     load_all_tiles2<DH>(Kimg, kb_, ld, Vimg, vb, ld, T, dh, rows_alloc, tid, blockDim.x);
   }
-  FWD_ST(0)  // Q + K landed (this wave's pieces)
   __syncthreads();
-  FWD_ST(1)  // barrier
   if (q00 >= T) {  // a wave with no query rows: it still owes the workgroup its V pieces and the barrier that publishes them
     if (v_pending) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -871,11 +848,6 @@ __global__ __launch_bounds__(768, 3) void attn_fwd_res_kernel(AttnArgs p) {
     for (int i = 0; i < DH / 16; ++i) ot[rq][i] = zero4();
   }
   const float c = p.scale * LOG2E;
-#ifdef VIT_FWD_STAMP
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  asm volatile("" ::"v"(qf[0][0]), "v"(qf[RQ - 1][DH / 32 - 1]));
-#endif
-  FWD_ST(2)  // Q fragments in registers
 
   fwd_keyloop<DH, RQ, TPC>(Kimg, Vimg, qf, m, l, ot, T, c, p.drop, bh, q00, l15, lg, [&]() {
     if (v_pending) {  // V in and published before its first fragment read
@@ -883,22 +855,7 @@ __global__ __launch_bounds__(768, 3) void attn_fwd_res_kernel(AttnArgs p) {
       __syncthreads();
     }
   });
-  FWD_ST(3)  // key loop
   fwd_finish<DH, RQ, DMA, HC>(p, m, l, ot, b, h, bh, q00, c, l15, lg);
-#ifdef VIT_FWD_STAMP
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  FWD_ST(4)  // normalise + stores retired
-  {
-    const unsigned wid = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    if ((threadIdx.x & 63) == 0 && wid < FWD_ST_WAVES) {
-#pragma unroll
-      for (int k = 0; k < 5; ++k) g_fwd_st[wid * 8 + k] = st_[k];
-      g_fwd_st[wid * 8 + 5] = tstart_;
-      g_fwd_st[wid * 8 + 6] = tprev_;
-      g_fwd_st[wid * 8 + 7] = 1;
-    }
-  }
-#endif
 }
 
 // Dropout keep FLAGS of 4 consecutive query rows at ONE key for the key-owner orientation of the backward kernels, from the
@@ -1478,28 +1435,10 @@ __device__ __forceinline__ int ds2_swz(int key) { return (((key >> 2) & 1) << 2)
 __device__ __forceinline__ int ds2_off(int key, int slot) { return key * 64 + ((slot ^ ds2_swz(key)) << 3); }
 
 constexpr int PIPE_SLOT = 16384, PIPE_NS = 3;
-#ifndef VIT_PIPE_SKIP  // timing variants only (python -m vit_amd.build --defs -DVIT_PIPE_SKIP=n --tag ..): 1 no B, 2 no A, 4 no DMA, 8 no D
-#define VIT_PIPE_SKIP 0
-#endif
 static size_t pipe_smem(int T) {
   const size_t R = (T + 15) & ~15;
   return PIPE_NS * PIPE_SLOT + PIPE_NS * 4 * 256 + 2 * R * 128 + R * 128 + 2 * R * 64 + 2 * 96 * 4;
 }
-
-#ifdef VIT_PIPE_STAMP  // diagnostic build only (tools/pipe_stamps.py): where an iteration of workgroup 0 goes, per wave
-__device__ unsigned long long g_pipe_st[8 * 8];
-#define PIPE_ST(K)                                                                   \
-  {                                                                                  \
-    unsigned long long t_;                                                           \
-    __builtin_amdgcn_sched_barrier(0);                                               \
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");      \
-    __builtin_amdgcn_sched_barrier(0);                                               \
-    st_[K] += t_ - tprev_;                                                           \
-    tprev_ = t_;                                                                     \
-  }
-#else
-#define PIPE_ST(K)
-#endif
 
 struct PipeHead { int bh, b, hh; };
 
@@ -1606,10 +1545,6 @@ __global__ __launch_bounds__(512) void attn_bwd_pipe_kernel(AttnArgs p) {
   int hm = 0, pm = -3, h0 = 0, p0 = -2, h1 = 0, p1 = -1, h2 = 0, p2 = 0;
   PipeHead Hm = head_of(0), H0 = Hm, H1 = Hm, H2 = Hm, Hn = Hm;
   long q2 = qoff_of(H2), c2 = coff_of(H2), qn = q2;  // element offsets of heads H2 / Hn: 64-bit products, once per head
-#ifdef VIT_PIPE_STAMP
-  unsigned long long st_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tprev_;
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tprev_)::"memory");
-#endif
   for (int g = -2; g <= G; ++g) {
     const bool vm = g - 1 >= 0 && g - 1 < G, v0 = g >= 0 && g < G, v1 = g + 1 >= 0 && g + 1 < G, v2 = g + 2 < G;
     int ln = lane;
@@ -1621,7 +1556,7 @@ __global__ __launch_bounds__(512) void attn_bwd_pipe_kernel(AttnArgs p) {
     // ------------------------------------------------------------------ top: B(g-1), head-end epilogue (stores)
     if (vm) {
       const bool head_done = pm == np - 1;
-      if (is_b && !(VIT_PIPE_SKIP & 1)) {
+      if (is_b) {
         const int qt = pm * 2 + bq;
         if (qt < nq) {
           f32x4 dq0 = zero4(), dq1 = zero4();
@@ -1691,7 +1626,6 @@ __global__ __launch_bounds__(512) void attn_bwd_pipe_kernel(AttnArgs p) {
             *(u32x4*)(p.dqkv + ((long)Hm.b * T + q) * ld + Hm.hh * DH + bd * 32 + col) = (u32x4){pa[0], pa[1], pb[0], pb[1]};
         }
       }
-      PIPE_ST(6)  // B(g-1) alone
       if (head_done) {  // dK, dV of this wave's key tiles of head hm; per-wave column sums of everything this wave stored
         f32x4 csk[ND], csv[ND];
 #pragma unroll
@@ -1745,7 +1679,6 @@ __global__ __launch_bounds__(512) void attn_bwd_pipe_kernel(AttnArgs p) {
         }
       }
     }
-    PIPE_ST(0)  // top: B(g-1) + head-end epilogue
     // ------------------------------------------------------------------ issue: next head's K / V images, pair g + 2
     // INVARIANT of every hand-counted wait below: a DMA piece may be read only after a wait of the wave that issued it AND a
     // barrier, both at least one iteration newer than its issue.  L pieces: issued in iteration g for pair g + 2, covered by
@@ -1766,8 +1699,7 @@ __global__ __launch_bounds__(512) void attn_bwd_pipe_kernel(AttnArgs p) {
       nissued += n_;
       if (p0 == np - 1) nkv_now = n_;  // the head's last iteration: these must have landed before its closing barrier
     }
-    if (v2 && !(VIT_PIPE_SKIP & 4)) nissued += issue_L(H2.bh, q2, c2, p2, (g + 2) % PIPE_NS);
-    PIPE_ST(1)  // DMA issue
+    if (v2) nissued += issue_L(H2.bh, q2, c2, p2, (g + 2) % PIPE_NS);
     // ------------------------------------------------------------------ A(g)
     if (v0) {
       if (p0 == 0) {  // a head starts: this wave's K / V rows out of the images (landed and published an iteration ago or more)
@@ -1783,7 +1715,7 @@ __global__ __launch_bounds__(512) void attn_bwd_pipe_kernel(AttnArgs p) {
           }
         }
       }
-      if (own0 && !(VIT_PIPE_SKIP & 2)) {
+      if (own0) {
         const char* Qt = ring + (g % PIPE_NS) * PIPE_SLOT;
         const char* Ot = Qt + 4096;
         const float* lse_s = stats + (g & 1) * 96;
@@ -1852,12 +1784,10 @@ __global__ __launch_bounds__(512) void attn_bwd_pipe_kernel(AttnArgs p) {
         }
       }
     }
-    PIPE_ST(2)  // A(g)
     // ------------------------------------------------------------------ my pieces of pair g + 1 (one iteration old) are in
     wait_vmcnt_dyn(nissued - nkv_now);
-    PIPE_ST(3)  // counted wait
     // ------------------------------------------------------------------ D(g+1): statistics of the 8 rows this wave loaded
-    if (v1 && is_d && !(VIT_PIPE_SKIP & 8)) {
+    if (v1 && is_d) {
       const int s1 = (g + 1) % PIPE_NS;
       const char* slot = ring + s1 * PIPE_SLOT;
       const int rl = grp * 8 + rl8, ch = ln & 7;
@@ -1879,10 +1809,8 @@ __global__ __launch_bounds__(512) void attn_bwd_pipe_kernel(AttnArgs p) {
         if (grow < T) p.delta[(long)H1.bh * T + grow] = d_;
       }
     }
-    PIPE_ST(4)  // D(g+1)
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
-    PIPE_ST(5)  // barrier
     hm = h0; pm = p0; h0 = h1; p0 = p1; h1 = h2; p1 = p2;
     Hm = H0; H0 = H1; H1 = H2;
     if (++p2 == np) {
@@ -1895,46 +1823,19 @@ __global__ __launch_bounds__(512) void attn_bwd_pipe_kernel(AttnArgs p) {
       }
     }
   }
-#ifdef VIT_PIPE_STAMP
-  if (blockIdx.x == 0 && lane == 0) {
-#pragma unroll
-    for (int k = 0; k < 8; ++k) g_pipe_st[wave * 8 + k] = st_[k];
-    g_pipe_st[wave * 8 + 7] = (unsigned long long)(G + 3);
-  }
-#endif
 }
-#ifdef VIT_FWD_STAMP
-}  // namespace vit
-extern "C" int vit_debug_fwd_stamps(unsigned long long* host, int reset) {  // host: FWD_ST_WAVES * 8 words
-  if (reset) {
-    void* d = nullptr;
-    if (hipGetSymbolAddress(&d, HIP_SYMBOL(vit::g_fwd_st)) != hipSuccess) return -1;
-    return (int)hipMemset(d, 0, sizeof(unsigned long long) * FWD_ST_WAVES * 8);
-  }
-  return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(vit::g_fwd_st), sizeof(unsigned long long) * FWD_ST_WAVES * 8);
-}
-namespace vit {
-#endif
-#ifdef VIT_PIPE_STAMP
-}  // namespace vit
-extern "C" int vit_debug_pipe_stamps(unsigned long long* host64) {
-  return (int)hipMemcpyFromSymbol(host64, HIP_SYMBOL(vit::g_pipe_st), 64 * sizeof(unsigned long long));
-}
-namespace vit {
-#endif
 
 static bool pipe_fits(int T, int dh) { return dh == 64 && T >= 64 && T <= 208 && pipe_smem(T) <= 160 * 1024; }
 
 // vit_set_option("attn_bwd_fused"): 0 = two-kernel backward everywhere; non-zero (default 4; 1 .. 3 named forms that no longer
 // exist and mean the same) = the pair-pipelined single kernel where it fits (dh 64, 64 <= T <= 208), the two-kernel path elsewhere
 int g_attn_bwd_fused = 4;
-int g_attn_fwd_waves = 12;  // vit_set_option("attn_fwd_waves"): most waves per workgroup of the resident forward (8 or 12)
 
 // resident kernels: a (batch, head)'s whole K/V (or Q/dO) in the LDS -- at head_dim 64 up to T = 592 rows (2 x 74 KiB; the
 // backward adds 4.6 KiB of row statistics): ViT-L/16 384^2 (T = 577) fits, one workgroup per CU, three workgroups of 7
 // waves per head
 constexpr int RES_MAX_T = 592, RES_MAX_DH = 64, RES_RQ = 2;
-int g_attn_res_max_t = RES_MAX_T;  // vit_set_option("attn_res_max_t"): larger T goes to the tiled kernels
+constexpr int RES_FWD_WAVES = 12;  // most waves per workgroup of the resident forward (res_geometry)
 int g_attn_split = 2;  // vit_set_option("attn_split"): workgroups per (batch, head) in the resident kernels
 
 static bool res_fits(int T, int dh) {  // the dK/dV kernel's LDS: the staged rows of Q and dO + three f32 rows of statistics
@@ -1979,11 +1880,10 @@ static int launch_res(const AttnArgs& a, size_t smem, hipStream_t st, int max_wa
     else { constexpr int DH_ = 64; rc = launch_res<KERNEL<64, RES_RQ>>(a, smem_expr, st); }                    \
   } while (0)
 // the two resident backward kernels: head_dim exactly 64 takes the DMA prologue (images requested in reading order, per-tile
-// counted waits); g_attn_bwd_dma = 0 (vit_set_option("attn_bwd_dma")) keeps the register-staged form for A/B runs
-int g_attn_bwd_dma = 1;
+// counted waits); head_dim 40 - 56 keeps the register-staged form
 #define DISPATCH_RES_BWD(KERNEL, a, smem_expr, st, rc)                                      \
   do {                                                                                      \
-    if (a.dh == 64 && g_attn_bwd_dma) { constexpr int DH_ = 64; rc = launch_res<KERNEL<64, RES_RQ, true>>(a, smem_expr, st); } \
+    if (a.dh == 64) { constexpr int DH_ = 64; rc = launch_res<KERNEL<64, RES_RQ, true>>(a, smem_expr, st); } \
     else if (a.dh <= 32) { constexpr int DH_ = 32; rc = launch_res<KERNEL<32, RES_RQ, false>>(a, smem_expr, st); } \
     else { constexpr int DH_ = 64; rc = launch_res<KERNEL<64, RES_RQ, false>>(a, smem_expr, st); }             \
   } while (0)
@@ -2436,12 +2336,10 @@ __global__ __launch_bounds__(256) void attn32m_dkv_kernel(Attn32Args p) {
 }
 #undef MFMA32
 
-int g_attn32_mfma = 1;  // vit_set_option("attn32_mfma"): 0 = the one-wave-per-row fp32 kernels for every shape
-
 static int launch_attn32(int which, Attn32Args& a, hipStream_t st) {
   VIT_CHECK(a.T <= 4096 && a.dh <= 128 && (a.dh % 4) == 0, VIT_ERR_UNSUPPORTED,
             "fp32 attention supports T <= 4096 and dh <= 128 (multiple of 4); got T=%d dh=%d", a.T, a.dh);
-  if (g_attn32_mfma && a.dh == 64 && !a.probs) {  // head_dim 64, no attention-map output: the f32-MFMA kernels
+  if (a.dh == 64 && !a.probs) {  // head_dim 64, no attention-map output: the f32-MFMA kernels
     dim3 grid(cdiv(cdiv(a.T, 16), 4), a.B * a.H);
     if (which == 0) hipLaunchKernelGGL(attn32m_fwd_kernel, grid, dim3(256), 0, st, a);
     else if (which == 1) hipLaunchKernelGGL(attn32m_dq_kernel, grid, dim3(256), 0, st, a);
@@ -2506,15 +2404,15 @@ int vit_attention_fwd_lo(vit_handle h, const void* qkv, void* ctx, void* ctx_lo,
   a.qkv = (const short*)qkv; a.ctx = (short*)ctx; a.ctx_lo = (short*)ctx_lo; a.lse = lse;
   a.B = B; a.H = H; a.T = T; a.dh = dh; a.scale = scale;
   a.drop = make_drop_h(h, dropout_p, seed, site);
-  if (T <= g_attn_res_max_t && T <= RES_MAX_T && dh <= RES_MAX_DH && res_fits(T, dh)) {
+  if (T <= RES_MAX_T && dh <= RES_MAX_DH && res_fits(T, dh)) {
     const size_t img = 2 * (size_t)((T + 15) & ~15) * 2;  // K + V images: rows x dh_padded x 2 bytes each
     int ns_ = 0, wp_ = 0;
-    res_geometry(T, &ns_, &wp_, g_attn_fwd_waves);
+    res_geometry(T, &ns_, &wp_, RES_FWD_WAVES);
     if (a.dh == 64 && T > 192 && T <= 208 && H == 12 && ns_ == 2 && wp_ == 4)
-      rc = launch_res<attn_fwd_res_kernel<64, RES_RQ, true, 208, 12, 2, 4>>(a, img * 64, (hipStream_t)stream, g_attn_fwd_waves);
-    else if (a.dh == 64) rc = launch_res<attn_fwd_res_kernel<64, RES_RQ, true>>(a, img * 64, (hipStream_t)stream, g_attn_fwd_waves);
-    else if (a.dh <= 32) rc = launch_res<attn_fwd_res_kernel<32, RES_RQ, false>>(a, img * 32, (hipStream_t)stream, g_attn_fwd_waves);
-    else rc = launch_res<attn_fwd_res_kernel<64, RES_RQ, false>>(a, img * 64, (hipStream_t)stream, g_attn_fwd_waves);
+      rc = launch_res<attn_fwd_res_kernel<64, RES_RQ, true, 208, 12, 2, 4>>(a, img * 64, (hipStream_t)stream, RES_FWD_WAVES);
+    else if (a.dh == 64) rc = launch_res<attn_fwd_res_kernel<64, RES_RQ, true>>(a, img * 64, (hipStream_t)stream, RES_FWD_WAVES);
+    else if (a.dh <= 32) rc = launch_res<attn_fwd_res_kernel<32, RES_RQ, false>>(a, img * 32, (hipStream_t)stream, RES_FWD_WAVES);
+    else rc = launch_res<attn_fwd_res_kernel<64, RES_RQ, false>>(a, img * 64, (hipStream_t)stream, RES_FWD_WAVES);
     return rc;
   }
   dim3 grid(cdiv(cdiv(T, 16), AW), B * H);
@@ -2549,7 +2447,7 @@ int vit_attention_bwd_lo(vit_handle h, const void* qkv, const void* ctx, const v
     return attention_bwd_impl(h, qkv, ctx, ctx_lo, dctx, lse, delta, dqkv, io_dtype, B, H, T, dh, scale, dropout_p, seed, site,
                               nullptr, stream);
   const int D3 = 3 * H * dh;
-  if (io_dtype == VIT_BF16 && T <= g_attn_res_max_t && T <= RES_MAX_T && dh <= RES_MAX_DH && (dh % 4) == 0 && res_fits(T, dh)) {
+  if (io_dtype == VIT_BF16 && T <= RES_MAX_T && dh <= RES_MAX_DH && (dh % 4) == 0 && res_fits(T, dh)) {
     int nsplit, wpw;
     res_geometry(T, &nsplit, &wpw);
     size_t wsb = 0;
@@ -2594,7 +2492,7 @@ static int attention_bwd_impl(vit_handle h, const void* qkv, const void* ctx, co
   a.B = B; a.H = H; a.T = T; a.dh = dh; a.scale = scale;
   a.drop = make_drop_h(h, dropout_p, seed, site);
   a.csum_part = colsum_part;
-  if (g_attn_bwd_fused && T <= g_attn_res_max_t && pipe_fits(T, dh)) {
+  if (g_attn_bwd_fused && pipe_fits(T, dh)) {
     static bool attr = false;
     if (!attr) {
       VIT_HIP(hipFuncSetAttribute((const void*)attn_bwd_pipe_kernel<true, 12, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
@@ -2610,7 +2508,7 @@ static int attention_bwd_impl(vit_handle h, const void* qkv, const void* ctx, co
     VIT_LAUNCH_CHECK();
     return VIT_OK;
   }
-  if (T <= g_attn_res_max_t && T <= RES_MAX_T && dh <= RES_MAX_DH && res_fits(T, dh)) {
+  if (T <= RES_MAX_T && dh <= RES_MAX_DH && res_fits(T, dh)) {
     DISPATCH_RES_BWD(attn_bwd_dq_res_kernel, a, (2 * (size_t)((T + 15) & ~15) * DH_ * 2), st, rc);
     if (rc != VIT_OK) return rc;
     DISPATCH_RES_BWD(attn_bwd_dkv_res_kernel, a, (2 * (size_t)((T + 15) & ~15) * DH_ * 2 + 3 * (size_t)((T + 63) & ~63) * 4), st, rc);

@@ -264,17 +264,9 @@ constexpr unsigned OOB = 0x80000000u;  // any voffset >= num_records reads as ze
 // ISA of gemm3_kernel<*,1,*,*>; the plain ds_read_b128 forms were never affected).  The asm form is invisible to that pass;
 // these loads still count in vmcnt, in order, and every wait for them is a hand-counted s_waitcnt.  M0 is written in the
 // statement that reads it (s_nop: M0 write -> use) and named in the clobber list (r04, advisor finding): the compiler's own
-// users of M0 (its LDS-DMA builtin in the VIT_DMA_BUILTIN variant, v_readlane / v_movrel indexing, s_sendmsg) then see a
-// definition here and neither keep a value live across the statement nor drop their own M0 write as redundant.  clang notes
-// that M0 is a reserved register (-Winline-asm, silenced in build.py): it is not allocatable, the clobber is still recorded.
-#ifdef VIT_DMA_BUILTIN  // A/B variant build only (python -m vit_amd.build --defs -DVIT_DMA_BUILTIN --tag dmab): the builtin form
-__device__ __forceinline__ void lds_dma16(const void* gsrc, void* lds_dst) {
-  __builtin_amdgcn_global_load_lds((__attribute__((address_space(1))) void*)gsrc, (__attribute__((address_space(3))) void*)lds_dst, 16, 0, 0);
-}
-__device__ __forceinline__ void lds_dma4(const void* gsrc, void* lds_dst) {
-  __builtin_amdgcn_global_load_lds((__attribute__((address_space(1))) void*)gsrc, (__attribute__((address_space(3))) void*)lds_dst, 4, 0, 0);
-}
-#else
+// users of M0 (v_readlane / v_movrel indexing, s_sendmsg) then see a definition here and neither keep a value live across
+// the statement nor drop their own M0 write as redundant.  clang notes that M0 is a reserved register (-Winline-asm, silenced
+// in build.py): it is not allocatable, the clobber is still recorded.
 __device__ __forceinline__ void lds_dma16(const void* gsrc, void* lds_dst /* wave-uniform */) {
   const unsigned a = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)lds_dst);
   asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(gsrc), "s"(a) : "memory", "m0");
@@ -283,7 +275,6 @@ __device__ __forceinline__ void lds_dma4(const void* gsrc, void* lds_dst /* wave
   const unsigned a = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)lds_dst);
   asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dword %0, off" ::"v"(gsrc), "s"(a) : "memory", "m0");
 }
-#endif
 // The same two with a wave-uniform 64-bit base (SGPR pair) and a per-lane 32-bit byte offset: the lane address is one
 // 32-bit multiply-add instead of a 64-bit one per piece (the attention backward's DMA issue was ~180 cycles per piece, most of
 // it address arithmetic: stamps).  base + off is the byte address; off < 2^32.

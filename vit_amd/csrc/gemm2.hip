@@ -4,7 +4,7 @@
 // the CU:
 //
 //   * 256x256x64 tiles, 8 waves = 512 threads, one workgroup per CU; the two wave halves run one barrier out of phase
-//     (LOAD segment beside MFMA segment): gemm3_kernel below; gemm3h_kernel takes the tiles of a partial last round;
+//     (LOAD segment beside MFMA segment): gemm3_kernel below;
 //   * LDS-DMA staging (global_load_lds_dwordx4 by inline asm, common.h: lds_dma16): 1 KiB per wave-instruction straight into
 //     a ring of 8 half-tile slots, no staging registers.  The DMA destination is lane-linear, so the XOR swizzle of both
 //     image kinds is applied to the per-lane SOURCE address and to the fragment reads (never to the destination);
@@ -13,11 +13,11 @@
 //   * persistent over output tiles: a workgroup walks its tiles in one flat (tile, k-tile) iteration space, so the
 //     loads of the next tile's first K-tiles are already in flight during the current tile's epilogue;
 //   * XCD-aware tile order inside each round of concurrently running tiles (neighbours in n share the A panel in L2);
+//   * one launch of just enough workgroups for ceil(tiles / CUs) rounds, a partial last round included: the step is
+//     power-limited, and the idle CUs' budget goes to the busy ones' clock (gemm2_try_launch);
 //   * epilogue through a per-wave LDS transpose (the 32 KiB the ring leaves free): accumulators go to LDS in MFMA layout and
 //     come back row-major, so every bias / aux / residual load and every output store of a wave-instruction covers whole
 //     128- or 256-byte row segments instead of 16 rows x 32 bytes.
-// (The earlier lock-step geometries -- 256x256 / 256x128, 2-4 stage rings, selectable as gemm_core 2 / 3 / 4 / 6 -- were never
-// chosen automatically once the ping-pong form existed and were removed in round 3.)
 //
 // LDS images (byte offsets inside one operand image of R rows):
 //   K-contiguous, BK=64: row r, 16-B chunk c at r*128 + ((c ^ ((r>>1)&7)) << 4)
@@ -46,21 +46,11 @@ struct Gemm2Args {
   int act, c_dtype;
   DropCfg drop;
   int rpb, orb, roff;
-#ifdef VIT_PP_DIAG
-  int debug;  // diagnostic twin build only (python -m vit_amd.build --diag, tools/pp_diag.py): pieces of the K loop switched off
-#endif
   int lin_split;  // ping-pong kernel, split-K with one tile per workgroup: 1-D grid of tiles x splits, XCD-contiguous
   float* colsum_part;  // ping-pong kernel, bf16 epilogues: [tiles_m * 2][N] per-wave-row column sums of C, or NULL
-  int tile_limit;      // ping-pong kernel: walk only the first tile_limit tiles (0 = all); the half-tile kernel takes the rest
-  int tail_first, tail_n;  // half-tile kernel: tiles [tail_first, tail_first + tail_n), two workgroups each
-  int slab_tiles;  // split-K over the tail tiles: the slab is compact, [split][tile - tail_first][256][256] f32 (0: [split][M][N])
   int grp2;  // ping-pong kernel: XCDs 0-3 walk the lower half of the N-tiles, XCDs 4-7 the upper half (see tile_coords)
   const float* rope_cos; const float* rope_sin;  // epilogue 8: rotary embedding of columns [0, rope_cols) (vit_gemm_desc)
   int rope_T, rope_dh, rope_cols;
-#ifdef VIT_PP_STAMP
-  unsigned long long* stamps;  // diagnostic build: [8 waves][8] summed s_memtime deltas of workgroup `stamp_block`
-  int stamp_block;
-#endif
 };
 
 __device__ __forceinline__ int tr_swz2(int k) { return ((k & 3) | (((k >> 3) & 1) << 2)) << 2; }
@@ -173,14 +163,7 @@ __device__ __forceinline__ void pp_epilogue(f32x4 (&acc)[NI][4], char* scr, cons
   if (FAST == 7) {
     // f32 out: a lane owns 4 consecutive columns of rows rr*4 + lane/16 (16-byte stores, 256-byte row segments)
     float* cf = p.splits > 1 ? p.slab + (long)split * p.M * p.N : (float*)p.C;
-    long ldc = p.splits > 1 ? (long)p.N : p.ldc;
-    if (p.slab_tiles) {  // tail tiles only: one 256 x 256 block per (K-slice, tile)
-      const int tl = (m0 >> 8) * p.tiles_n + (n0 >> 8) - p.tail_first;
-      cf = p.slab + ((long)split * p.slab_tiles + tl) * 65536;
-      ldc = 256;
-      m0 &= 255;
-      n0 &= 255;
-    }
+    const long ldc = p.splits > 1 ? (long)p.N : p.ldc;
     const int n = n0 + l15 * 4;
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
@@ -206,15 +189,10 @@ __device__ __forceinline__ void pp_epilogue(f32x4 (&acc)[NI][4], char* scr, cons
   // nobody in this launch reads again; kept in the 4 MiB L2 it evicts the operand panels the XCD's other workgroups are about
   // to re-read.  r04, same-box A/B against plain stores (tools/gemm_bench.py, two interleaved repetitions): FC1 + GELU (two
   // outputs, 620 MB) 284-286 -> 271-275 us, the K = 768 / N = 768 products 70 -> 66 and 62 -> 60.7 us, QKV 160.6 -> 159.
-#ifndef VIT_EPI_PLAIN_STORES
   const __amdgpu_buffer_rsrc_t rc_ = make_rsrc(p.C, (unsigned long long)p.M * p.ldc * 2);
   const __amdgpu_buffer_rsrc_t ra_ = make_rsrc(p.aux_out ? (const void*)p.aux_out : (const void*)p.C, (unsigned long long)p.M * p.ldaux * 2);
 #define EPI_STORE_C(M_, PK) __builtin_amdgcn_raw_buffer_store_b128(PK, rc_, (unsigned)(((M_) * p.ldc + n) * 2), 0, 16)
 #define EPI_STORE_AUX(M_, PK) __builtin_amdgcn_raw_buffer_store_b128(PK, ra_, (unsigned)(((M_) * p.ldaux + n) * 2), 0, 16)
-#else  // A/B variant build only
-#define EPI_STORE_C(M_, PK) *(u32x4*)(p.C + ((M_) * p.ldc + n) * 2) = PK
-#define EPI_STORE_AUX(M_, PK) *(u32x4*)(p.aux_out + (M_) * p.ldaux + n) = PK
-#endif
   const unsigned half_cols = (unsigned)(p.N >> 1);
   f32x4 bv0 = (f32x4){0.f, 0.f, 0.f, 0.f}, bv1 = bv0;
   if ((FAST == 3 || FAST == 4 || FAST == 8) && p.bias) {
@@ -240,13 +218,8 @@ __device__ __forceinline__ void pp_epilogue(f32x4 (&acc)[NI][4], char* scr, cons
     k8s0 = *(const f32x4*)(p.rope_sin + t8); k8s1 = *(const f32x4*)(p.rope_sin + t8 + 4);
   }
   // the aux operand (gelu' of FC1's pre-activation, 310 MB) is read exactly once: nt + sc1 keeps it out of L1 / low priority in
-  // L2 (r04 A/B on dX * gelu', same box: plain 338 us, nt 333, nt + sc1 327-330).  0 = plain loads (A/B variant)
-#ifndef VIT_EPI_AUX_POLICY
-#define VIT_EPI_AUX_POLICY 18
-#endif
-#if VIT_EPI_AUX_POLICY
+  // L2 (r04 A/B on dX * gelu', same box: plain 338 us, nt 333, nt + sc1 327-330): cache policy 18 = nt | sc1
   const __amdgpu_buffer_rsrc_t rx_ = make_rsrc(p.aux_in ? (const void*)p.aux_in : (const void*)p.C, (unsigned long long)p.M * p.ldaux * 2);
-#endif
 #pragma unroll
   for (int i = 0; i < NI; ++i) {
     if (FAST == 5 && (i & 3) == 0) {
@@ -254,22 +227,9 @@ __device__ __forceinline__ void pp_epilogue(f32x4 (&acc)[NI][4], char* scr, cons
       for (int ii = 0; ii < 4; ++ii)
 #pragma unroll
         for (int rr = 0; rr < 2; ++rr)
-#if VIT_EPI_AUX_POLICY
-          au[ii][rr] = __builtin_amdgcn_raw_buffer_load_b128(rx_, (unsigned)(((long)(m0 + (i + ii) * 16 + rr * 8 + rsub) * p.ldaux + n) * 2), 0, VIT_EPI_AUX_POLICY);
-#else
-          au[ii][rr] = *(const u32x4*)(p.aux_in + (long)(m0 + (i + ii) * 16 + rr * 8 + rsub) * p.ldaux + n);
-#endif
+          au[ii][rr] = __builtin_amdgcn_raw_buffer_load_b128(rx_, (unsigned)(((long)(m0 + (i + ii) * 16 + rr * 8 + rsub) * p.ldaux + n) * 2), 0, 18);
     }
     f32x4 v[2][2];
-#ifdef VIT_EPI_NOLDS  // timing experiment (compile-time variant): no LDS transpose, values land in the wrong places
-    {
-      v[0][0] = acc[i][0]; v[0][1] = acc[i][1]; v[1][0] = acc[i][2]; v[1][1] = acc[i][3];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    }
-    if (false)
-#endif
-    {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       *(f32x4*)(scr + l15 * 256 + (((j * 4 + lg) ^ l15) << 4)) = acc[i][j];
@@ -280,7 +240,6 @@ __device__ __forceinline__ void pp_epilogue(f32x4 (&acc)[NI][4], char* scr, cons
       const int row = rr * 8 + rsub;
       v[rr][0] = *(const f32x4*)(scr + row * 256 + (((2 * cg) ^ row) << 4));
       v[rr][1] = *(const f32x4*)(scr + row * 256 + (((2 * cg + 1) ^ row) << 4));
-    }
     }
 #pragma unroll
     for (int rr = 0; rr < 2; ++rr) {
@@ -293,12 +252,6 @@ __device__ __forceinline__ void pp_epilogue(f32x4 (&acc)[NI][4], char* scr, cons
       }
       if (FAST == 4) {
         float sv[8];  // aux_out: the pre-activation (ACT_GELU) or gelu' of it (ACT_GELU_GRAD: two FMAs on top of the GELU)
-#ifdef VIT_EPI_NOGELU  // timing experiment: no GELU arithmetic (values are wrong)
-        if (true) {
-#pragma unroll
-          for (int r = 0; r < 8; ++r) sv[r] = o[r] * 0.5f;
-        } else
-#endif
         if (p.act == VIT_ACT_GELU_GRAD) {
 #pragma unroll
           for (int r = 0; r < 8; r += 2) {
@@ -315,11 +268,7 @@ __device__ __forceinline__ void pp_epilogue(f32x4 (&acc)[NI][4], char* scr, cons
             o[r] = g_[0]; o[r + 1] = g_[1];
           }
         }
-#ifdef VIT_EPI_NOAUX  // timing experiment: the second output is not stored
-        if (p.aux_out && sv[0] == 1.2345e30f) {
-#else
         if (p.aux_out) {
-#endif
           u32x4 pk = {pack2bf(sv[0], sv[1]), pack2bf(sv[2], sv[3]), pack2bf(sv[4], sv[5]), pack2bf(sv[6], sv[7])};
           EPI_STORE_AUX(m, pk);
         }
@@ -434,18 +383,17 @@ __device__ __forceinline__ void pp_epilogue(f32x4 (&acc)[NI][4], char* scr, cons
 // stream runs through tile boundaries; at a boundary the groups re-align (one extra barrier each, on opposite sides of
 // the epilogue) so that all eight waves run their epilogues concurrently, and the first four phases after it count the
 // epilogue's >= 32 stores per wave into the vmcnt budget instead of draining them.
+// NSLOT (always 8) stays in the template so that the kernel's symbol -- what profilers list and vit_last_gemm_kernel reports --
+// is the one every recorded profile and benchmark names.
 template <int A_T, int B_T, int EPI, int NSLOT>
 __global__ __launch_bounds__(512, 2) void gemm3_kernel(Gemm2Args p) {
   resolve_drop(p.drop);
   constexpr int BM = 256, BN = 256, BK = 64;
   constexpr int HALF = 128 * BK * 2;     // one half-tile image: 16 KiB
-  // NSLOT half-tile slots, stream index h lives in slot h % NSLOT and is issued in phase h - DEPTH, DEPTH = NSLOT - 3 (the
-  // first phase >= 2 after the last read of the slot it overwrites); each phase's wait leaves DEPTH - 1 half-tiles in flight.
-  // NSLOT = 8: 64 KiB in flight, separate 32 KiB epilogue scratch.  NSLOT = 10: the ring takes all 160 KiB, 96 KiB in
-  // flight (operands that miss L2 -- dW streams every byte from HBM / Infinity Cache -- are latency-bound: bytes in flight
-  // over latency), and the epilogue scratch aliases the two slots that are free at a tile boundary, B1 and A1 of the
-  // K-tile just finished (restaged in phases 1 and 2 of the next K-tile; waves 0-3 own the first, 4-7 the second, and a
-  // wave half restages only after its own epilogue, the other half's DMA into the same slot comes a barrier later).
+  // NSLOT = 8 half-tile slots, stream index h lives in slot h % NSLOT and is issued in phase h - DEPTH, DEPTH = NSLOT - 3 (the
+  // first phase >= 2 after the last read of the slot it overwrites); each phase's wait leaves DEPTH - 1 half-tiles in flight:
+  // 64 KiB, and the 32 KiB the ring leaves free are the epilogue scratch.
+  static_assert(NSLOT == 8, "the ring arithmetic below is for 8 slots (two K-tiles of four half-tiles)");
   constexpr int DEPTH = NSLOT - 3, INFL = 2 * (DEPTH - 1);
   constexpr int SCR = 4096, CW = 64;     // epilogue scratch per wave
   constexpr int XA0 = 0, XB0 = 1, XB1 = 2, XA1 = 3;
@@ -459,7 +407,7 @@ __global__ __launch_bounds__(512, 2) void gemm3_kernel(Gemm2Args p) {
   const int wr = wave >> 2, wc = wave & 3, grp = wr;
   const int l15 = lane & 15, lg = lane >> 4;
 
-  const int ntile = p.tile_limit > 0 ? p.tile_limit : p.tiles_m * p.tiles_n;
+  const int ntile = p.tiles_m * p.tiles_n;
   int split = blockIdx.y, bx = blockIdx.x;
   if (p.lin_split) {
     // split-K (dW = dY^T X: K = all tokens, a few dozen output tiles): one (tile, K-slice) per workgroup on a 1-D grid.
@@ -521,13 +469,13 @@ __global__ __launch_bounds__(512, 2) void gemm3_kernel(Gemm2Args p) {
       tn = g * hn + (u - tm * hn);
       return;
     }
-    const int t = p.lin_split ? p.tail_first + bx : round0 + pos;  // tail_first: 0 unless this launch is the tail's K-slices
+    const int t = p.lin_split ? bx : round0 + pos;
     tm = t / p.tiles_n;
     tn = t - tm * p.tiles_n;
   };
   // The K-tile stream cursor: global bases (A, B) of the next K-tile to stage.  Everything on this path is SCALAR code that
   // sits in a LOAD segment, in front of the barrier the other wave group's MFMA segment ends on, and a wave issues one
-  // instruction per ~4-5 cycles: in-kernel stamps (tools/pp_stamps.py) showed the per-K-tile bookkeeping -- bases recomputed
+  // instruction per ~4-5 cycles: in-kernel stamps (r03) showed the per-K-tile bookkeeping -- bases recomputed
   // with 64-bit multiplies, ring-slot arithmetic, three branches per phase -- costing as much as the 16 MFMAs it hides
   // behind.  So: inside an output tile the bases advance by a constant (two 64-bit adds); past the end of the walk the
   // cursor stays on the last K-tile (its re-fetches land in ring slots nobody reads again: no "is there a next K-tile"
@@ -560,7 +508,6 @@ __global__ __launch_bounds__(512, 2) void gemm3_kernel(Gemm2Args p) {
     }
   };
   // one half-tile = 2 LDS-DMA instructions per thread; destination: slot + round*8 KiB + wave*1 KiB (+ lane*16)
-  static_assert(NSLOT == 8, "the ring arithmetic below is for 8 slots (two K-tiles of four half-tiles)");
   unsigned dofs = 0;  // byte offset of the slot the next stream index goes to (stream order: A0 B0 B1 A1 per K-tile)
   // uniform 64-bit base + the thread's constant 32-bit byte offset, raw LDS address: three instructions per piece (a generic
   // `char*` destination cost an aperture compare + null check per piece, the per-lane source a 64-bit VALU add; r03)
@@ -568,9 +515,6 @@ __global__ __launch_bounds__(512, 2) void gemm3_kernel(Gemm2Args p) {
   auto issue_half = [&](const char* base, long half_off, const int (&off)[2]) {
     const unsigned dst = smem_a + dofs;
     dofs = (dofs + HALF) & (NSLOT * HALF - 1);
-#ifdef VIT_PP_DIAG  // diagnostic build only (tools/pp_diag.py): 16 = no operand DMA, 32 = no fragment reads, 64 = no MFMAs, 128 = no epilogue
-    if (p.debug & 16) return;
-#endif
     const char* sb = base + half_off * 2;
     lds_dma16_s(sb, (unsigned)off[0] * 2u, dst);
     lds_dma16_s(sb, (unsigned)off[1] * 2u, dst + 8192);
@@ -583,9 +527,6 @@ __global__ __launch_bounds__(512, 2) void gemm3_kernel(Gemm2Args p) {
 #pragma unroll
   for (int s = 0; s < 2; ++s) kc_off[s] = l15 * 128 + (((s * 4 + lg) ^ (l15 >> 1)) << 4);
   auto read_frag = [&](const char* img, int trans, int base16, int s) -> bf16x8 {
-#ifdef VIT_PP_DIAG
-    if (p.debug & 32) return (bf16x8){(short)base16, (short)s, 0, 0, 0, 0, 0, 0};
-#endif
     if (!trans) {
       return *(const bf16x8*)(img + base16 * (BK * 2) + kc_off[s]);
     } else {
@@ -603,79 +544,6 @@ __global__ __launch_bounds__(512, 2) void gemm3_kernel(Gemm2Args p) {
     for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
   bf16x8 af[4][2], b0[2][2], b1[2][2];
 
-// In-kernel stamps (diagnostic build -DVIT_PP_STAMP=1|2 only; tools/pp_stamps.py): where a barrier interval goes.
-//   slot 0 fragment reads issued AND landed   1 LDS-DMA issue   2 counted vmcnt wait   (level 1: all three in slot 2)
-//   slot 3 barrier that ends the LOAD segment + lgkmcnt   4 MFMA segment (issue)   5 closing barrier   6 epilogue + re-align
-#ifdef VIT_PP_STAMP
-  unsigned long long st_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tprev_;
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tprev_)::"memory");
-#define PP_STX(K)                                                                                \
-  {                                                                                              \
-    unsigned long long t_;                                                                       \
-    __builtin_amdgcn_sched_barrier(0);                                                           \
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");                   \
-    __builtin_amdgcn_sched_barrier(0);                                                           \
-    st_[K] += t_ - tprev_;                                                                       \
-    tprev_ = t_;                                                                                 \
-  }
-#define PP_CNT st_[7] += 1;
-#if VIT_PP_STAMP == 5
-// level 5 (least intrusive): a stamp after every closing barrier (slot 1 = everything else) and ONE more at the end of P1's
-// LOAD segment: slot 0 = loop tail + P1's fragment reads + its LDS-DMA issue + counted wait
-#define PP_ST(K) PP_ST5_##K
-#define PP_ST5_2
-#define PP_ST5_3
-#define PP_ST5_4
-#define PP_ST5_5 PP_STX(1)
-#define PP_ST5_6 PP_STX(1)
-#define PP_ST2(K)
-#define PP_ST3(PH)
-#define PP_STL(PH) PP_STL5_##PH
-#define PP_STL5_0 PP_STX(0)
-#define PP_STL5_1
-#define PP_STL5_2
-#define PP_STL5_3
-#elif VIT_PP_STAMP == 4
-// level 4: slots 0-3 = the whole LOAD segment of phases P1..P4 (P1 includes the loop tail), 4 = barrier + lgkmcnt,
-// 5 = MFMA segment, 6 = closing barrier + epilogue
-#define PP_ST(K) PP_STX(((K) == 3 ? 4 : (K) == 4 ? 5 : 6))
-#define PP_ST2(K)
-#define PP_ST3(PH)
-#define PP_STL(PH) PP_STX(PH)
-#elif VIT_PP_STAMP == 3
-// level 3: slots 0-3 = "fragment reads landed" of phases P1..P4, 4 = rest of the LOAD segment, 5 = barrier + lgkmcnt,
-// 6 = MFMA segment + closing barrier + epilogue
-#define PP_ST(K) PP_STX(((K) == 2 ? 4 : (K) == 3 ? 5 : 6))
-#define PP_ST2(K)
-#define PP_ST3(PH) PP_STX(PH)
-#define PP_STL(PH) PP_ST(2)
-#else
-#define PP_ST(K) PP_STX(K)
-#define PP_ST3(PH)
-#define PP_STL(PH) PP_ST(2)
-#if VIT_PP_STAMP >= 2
-#define PP_ST2(K) PP_STX(K)
-#else
-#define PP_ST2(K)
-#endif
-#endif
-#else
-#define PP_ST(K)
-#define PP_ST2(K)
-#define PP_ST3(PH)
-#define PP_STL(PH)
-#define PP_CNT
-#endif
-#ifdef VIT_PP_NOPRIO
-#define PP_SETPRIO1
-#else
-#define PP_SETPRIO1 __builtin_amdgcn_s_setprio(1);
-#endif
-#ifdef VIT_PP_DIAG
-#define PP_DO_MFMA (!(p.debug & 64))
-#else
-#define PP_DO_MFMA true
-#endif
 #define PP_READ_A(IMG)                                                                           \
   _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_) _Pragma("unroll") for (int s_ = 0; s_ < 2; ++s_) \
       af[i_][s_] = read_frag(IMG, A_T, wr * 64 + i_ * 16, s_);
@@ -688,29 +556,21 @@ __global__ __launch_bounds__(512, 2) void gemm3_kernel(Gemm2Args p) {
   __builtin_amdgcn_s_barrier();                                                                  \
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                             \
   __builtin_amdgcn_sched_barrier(0);                                                             \
-  PP_ST(3)                                                                                       \
-  PP_SETPRIO1                                                                 \
-  if (PP_DO_MFMA)                                                                                \
+  __builtin_amdgcn_s_setprio(1);                                                                 \
   _Pragma("unroll") for (int s_ = 0; s_ < 2; ++s_) _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_) \
       _Pragma("unroll") for (int j_ = 0; j_ < 2; ++j_)                                            \
           acc[HA * 4 + i_][HB * 2 + j_] =                                                        \
               __builtin_amdgcn_mfma_f32_16x16x32_bf16(BF[j_][s_], af[i_][s_], acc[HA * 4 + i_][HB * 2 + j_], 0, 0, 0); \
   __builtin_amdgcn_s_setprio(0);                                                                 \
   __builtin_amdgcn_sched_barrier(0);                                                             \
-  PP_ST(4)                                                                                       \
-  __builtin_amdgcn_s_barrier();                                                                  \
-  PP_ST(5)                                                                                       \
-  PP_CNT
+  __builtin_amdgcn_s_barrier();
 // stage one half-tile and leave four half-tiles in flight: vmcnt(INFL), or vmcnt(RELAX) in the K-tile after an epilogue
 // (`relaxed` != 0): its stores were issued after the three older half-tiles still in flight -- count them in instead of
 // draining them.  One asm statement with its own two-instruction branch: an if / else in C++ made the compiler clone the
 // K-tile body (256 VGPRs + spills).
-#define PP_STAGE(PH, BASE, HOFF, OFF)                                                            \
+#define PP_STAGE(BASE, HOFF, OFF)                                                                \
   {                                                                                              \
-  PP_ST2(0)                                                                                      \
-  PP_ST3(PH)                                                                                     \
   issue_half(BASE, HOFF, OFF);                                                                   \
-  PP_ST2(1)                                                                                      \
   asm volatile("s_cmp_lg_u32 %0, 0\n\t"                                                          \
                "s_cbranch_scc1 .Lpp_relaxed_%=\n\t"                                              \
                "s_waitcnt vmcnt(%1)\n\t"                                                         \
@@ -718,22 +578,21 @@ __global__ __launch_bounds__(512, 2) void gemm3_kernel(Gemm2Args p) {
                ".Lpp_relaxed_%=:\n\t"                                                            \
                "s_waitcnt vmcnt(%2)\n"                                                           \
                ".Lpp_waited_%=:" ::"s"(relaxed), "n"(INFL), "n"(RELAX) : "scc", "memory");        \
-  PP_STL(PH)                                                                                     \
   }
 // Two forms of one K-tile, chosen per operand layout (MERGED below).
 // FOUR phases of 16 MFMAs.  Phase x issues stream index 4 it + 6 + x: B1, A1 of K-tile it+1, then A0, B0 of K-tile it+2
 #define PP_KTILE4                                                                                \
   PP_READ_B(b0, sp + XB0 * HALF)                                                                 \
   PP_READ_A(sp + XA0 * HALF)                                                                     \
-  PP_STAGE(0, bb1, halfB, offB)                                                                  \
+  PP_STAGE(bb1, halfB, offB)                                                                     \
   PP_MFMA(0, 0, b0)                                                                              \
   PP_READ_B(b1, sp + XB1 * HALF)                                                                 \
-  PP_STAGE(1, a1, halfA, offA)                                                                   \
+  PP_STAGE(a1, halfA, offA)                                                                      \
   PP_MFMA(0, 1, b1)                                                                              \
   PP_READ_A(sp + XA1 * HALF)                                                                     \
-  PP_STAGE(2, a2, 0, offA)                                                                       \
+  PP_STAGE(a2, 0, offA)                                                                          \
   PP_MFMA(1, 1, b1)                                                                              \
-  PP_STAGE(3, bb2, 0, offB)                                                                      \
+  PP_STAGE(bb2, 0, offB)                                                                         \
   PP_MFMA(1, 0, b0)
 // TWO phases per K-tile, 32 MFMAs each (half the barriers):
 //   I   reads B0, A0, B1 (16 fragments)  issues A1 of K-tile it+1           MFMA (A0,B0), (A0,B1)
@@ -752,14 +611,12 @@ __global__ __launch_bounds__(512, 2) void gemm3_kernel(Gemm2Args p) {
                ".Lpp_relaxed_%=:\n\t"                                                            \
                "s_waitcnt vmcnt(%2)\n"                                                           \
                ".Lpp_waited_%=:\n\t"                                                             \
-               "s_waitcnt lgkmcnt(0)" ::"s"(relaxed), "n"(INFL), "n"(RX) : "scc", "memory");       \
-  PP_ST(2)
+               "s_waitcnt lgkmcnt(0)" ::"s"(relaxed), "n"(INFL), "n"(RX) : "scc", "memory");
 #define PP_MFMA2(HA, BFA, HBA, BFB, HBB)                                                         \
   __builtin_amdgcn_sched_barrier(0);                                                             \
   __builtin_amdgcn_s_barrier();                                                                  \
   __builtin_amdgcn_sched_barrier(0);                                                             \
-  PP_ST(3)                                                                                       \
-  PP_SETPRIO1                                                                                    \
+  __builtin_amdgcn_s_setprio(1);                                                                 \
   _Pragma("unroll") for (int s_ = 0; s_ < 2; ++s_) _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_) \
       _Pragma("unroll") for (int j_ = 0; j_ < 2; ++j_)                                            \
           acc[HA * 4 + i_][HBA * 2 + j_] =                                                       \
@@ -770,10 +627,7 @@ __global__ __launch_bounds__(512, 2) void gemm3_kernel(Gemm2Args p) {
               __builtin_amdgcn_mfma_f32_16x16x32_bf16(BFB[j_][s_], af[i_][s_], acc[HA * 4 + i_][HBB * 2 + j_], 0, 0, 0); \
   __builtin_amdgcn_s_setprio(0);                                                                 \
   __builtin_amdgcn_sched_barrier(0);                                                             \
-  PP_ST(4)                                                                                       \
-  __builtin_amdgcn_s_barrier();                                                                  \
-  PP_ST(5)                                                                                       \
-  PP_CNT
+  __builtin_amdgcn_s_barrier();
 #define PP_KTILE2                                                                                \
   PP_READ_B(b0, sp + XB0 * HALF)                                                                 \
   PP_READ_A(sp + XA0 * HALF)                                                                     \
@@ -835,35 +689,13 @@ __global__ __launch_bounds__(512, 2) void gemm3_kernel(Gemm2Args p) {
       tile_coords(jt, tm, tn);
       if (grp == 0) __builtin_amdgcn_s_barrier();  // re-align: the other group finishes its last MFMA segment
       char* scr = smem + 8 * HALF + wave * SCR;
-#if defined(VIT_EPI_NONE)  // timing experiment (compile-time variant): no epilogue at all
-      if (true) {
-        if (acc[0][0][0] == 1.2345f) p.C[0] = 1;  // keep the accumulators alive
-      } else
-#elif defined(VIT_PP_DIAG)
-      if (p.debug & 128) {
-        if (acc[0][0][0] == 1.2345f) p.C[0] = 1;  // keep the accumulators alive
-      } else
-#endif
       if constexpr (EPI >= 3) pp_epilogue<EPI, 8>(acc, scr, p, tm * BM + wr * 128, tn * BN + wc * 64, split, lane);
       else tile_epilogue<8, 4, CW, EPI>(acc, scr, p, tm * BM + wr * 128, tn * BN + wc * 64, split, lane);
       if (grp == 1) __builtin_amdgcn_s_barrier();  // re-stagger
       relaxed = 1;
-      PP_ST(6)
     }
   }
   if (grp == 0) __builtin_amdgcn_s_barrier();  // balance the stagger barrier of the other group
-#ifdef VIT_PP_STAMP
-  if (p.stamps && (int)blockIdx.x == p.stamp_block && lane == 0) {
-#pragma unroll
-    for (int k = 0; k < 8; ++k) p.stamps[wave * 8 + k] = st_[k];
-  }
-#endif
-#undef PP_ST
-#undef PP_ST2
-#undef PP_ST3
-#undef PP_STL
-#undef PP_STX
-#undef PP_CNT
 #undef PP_READ_A
 #undef PP_READ_B
 #undef PP_MFMA
@@ -875,260 +707,11 @@ __global__ __launch_bounds__(512, 2) void gemm3_kernel(Gemm2Args p) {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the re-fetches past the end of the walk are still landing in the LDS
 }
 
-// ------------------------------------------------------------------------------------------------ half-tile tail kernel
-// The tiles of a partial last round (591 tiles = 2 rounds of 256 + 79) would keep 79 workgroups busy for a whole tile-time
-// while 177 CUs idle.  This kernel runs them as 2 x 79 HALF tiles instead: workgroup u takes tile tail_first + u/2 and, in
-// each wave row, the 64-row half h = u & 1 -- every wave computes a 64 x 64 block, the workgroup 128 rows x 256 columns.
-// Same ping-pong structure with TWO phases per K-tile, P1 = (A_h, B0), P2 = (A_h, B1), three half-tiles per K-tile in the
-// stream order A B0 B1, each issued three phases before its first read (odd phases issue one half-tile, even phases
-// two), 8-slot ring (slot = stream index % 8: restaged >= 2 phases after the last read), vmcnt(6) = three half-tiles in
-// flight at every wait.  A separate code object on purpose: the main kernel's register allocation is untouched.
-template <int A_T, int B_T, int EPI>
-__global__ __launch_bounds__(512, 2) void gemm3h_kernel(Gemm2Args p) {
-  resolve_drop(p.drop);
-  constexpr int BM = 256, BN = 256, BK = 64;
-  constexpr int HALF = 128 * BK * 2, NSLOT = 8;
-  constexpr int SCR = 4096, CW = 64;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wr = wave >> 2, wc = wave & 3, grp = wr;
-  const int l15 = lane & 15, lg = lane >> 4;
-  // XCD-contiguous unit order: the two halves of a tile (same B half-tiles at the same time) land on one XCD
-  const int total = 2 * p.tail_n, lin = blockIdx.x;
-  const int q_ = total >> 3, r_ = total & 7, xcd = lin & 7, within = lin >> 3;
-  const int unit = (xcd < r_ ? xcd * (q_ + 1) : r_ * (q_ + 1) + (xcd - r_) * q_) + within;
-  const int t = p.tail_first + (unit >> 1), h = unit & 1;
-  const int tm = t / p.tiles_n, tn = t - tm * p.tiles_n;
-  const int nk = p.K / BK;
-
-  int offA[2], offB[2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    if (A_T == 0) {
-      const int rimg = i * 64 + wave * 8 + (lane >> 3);
-      offA[i] = (i * 128 + wave * 8 + (lane >> 3)) * (int)p.lda + (((lane & 7) ^ ((rimg >> 1) & 7)) << 3);
-    } else {
-      const int k = i * 32 + wave * 4 + (lane >> 4);
-      const int c16 = (lane & 15) ^ (tr_swz2(k) >> 1);
-      offA[i] = k * (int)p.lda + (c16 >> 3) * 128 + ((c16 & 7) << 3);
-    }
-    if (B_T == 0) {
-      const int rimg = i * 64 + wave * 8 + (lane >> 3);
-      offB[i] = ((rimg >> 5) * 64 + (rimg & 31)) * (int)p.ldb + (((lane & 7) ^ ((rimg >> 1) & 7)) << 3);
-    } else {
-      const int k = i * 32 + wave * 4 + (lane >> 4);
-      const int c16 = (lane & 15) ^ (tr_swz2(k) >> 1);
-      offB[i] = k * (int)p.ldb + (c16 >> 2) * 64 + ((c16 & 3) << 3);
-    }
-  }
-  const long halfA = ((A_T == 0) ? 64 * p.lda : 64) * h, halfB = (B_T == 0) ? 32 * p.ldb : 32;
-  // operand bases of the next K-tile to stage, advanced by a constant per K-tile; past the last K-tile they stay (the
-  // re-fetched half-tiles land in ring slots nobody reads again), so no phase carries an "is there a next K-tile" branch --
-  // the same scalar diet as gemm3_kernel's loop (one instruction per ~4-5 cycles per wave: bookkeeping is not free)
-  const char* ca = ((A_T == 0) ? p.A + ((long)tm * BM * p.lda) * 2 : p.A + ((long)tm * BM) * 2) + halfA * 2;
-  const char* cb = (B_T == 0) ? p.B + ((long)tn * BN * p.ldb) * 2 : p.B + ((long)tn * BN) * 2;
-  const long dA = (A_T == 0) ? (long)BK * 2 : (long)BK * p.lda * 2, dB = (B_T == 0) ? (long)BK * 2 : (long)BK * p.ldb * 2;
-  int ckt = 0;
-  auto cursor_next = [&](const char*& ab, const char*& bb) {
-    ab = ca;
-    bb = cb;
-    if (ckt + 1 < nk) {
-      ++ckt;
-      ca += dA;
-      cb += dB;
-    }
-  };
-
-  unsigned dofs = 0;
-  const unsigned smem_a = lds_addr_of(smem) + wave * 1024;
-  auto issue_half = [&](const char* base, long off_el, const int (&off)[2]) {
-    const unsigned dst = smem_a + dofs;
-    dofs = (dofs + HALF) & (NSLOT * HALF - 1);
-    const char* sb = base + off_el * 2;
-    lds_dma16_s(sb, (unsigned)off[0] * 2u, dst);
-    lds_dma16_s(sb, (unsigned)off[1] * 2u, dst + 8192);
-  };
-
-  const int tq = l15 >> 2, tp = l15 & 3;
-  const int tr_f = (tq | ((lg & 1) << 2)) << 2;
-  int kc_off[2];
-#pragma unroll
-  for (int s = 0; s < 2; ++s) kc_off[s] = l15 * 128 + (((s * 4 + lg) ^ (l15 >> 1)) << 4);
-  auto read_frag = [&](const char* img, int trans, int base16, int s) -> bf16x8 {
-    if (!trans) {
-      return *(const bf16x8*)(img + base16 * (BK * 2) + kc_off[s]);
-    } else {
-      const char* pa = img + (s * 32 + lg * 8 + tq) * 256 + ((((base16 >> 2) + tp) ^ tr_f) << 3);
-      bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_AS bf16x4*)pa);
-      bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_AS bf16x4*)(pa + 4 * 256));
-      return (bf16x8){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    }
-  };
-
-  f32x4 acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  bf16x8 af[4][2], bq[2][2];
-
-#define HT_MFMA(HB)                                                                              \
-  __builtin_amdgcn_sched_barrier(0);                                                             \
-  __builtin_amdgcn_s_barrier();                                                                  \
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                             \
-  __builtin_amdgcn_sched_barrier(0);                                                             \
-  __builtin_amdgcn_s_setprio(1);                                                                 \
-  _Pragma("unroll") for (int s_ = 0; s_ < 2; ++s_) _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_) \
-      _Pragma("unroll") for (int j_ = 0; j_ < 2; ++j_)                                            \
-          acc[i_][HB * 2 + j_] =                                                                 \
-              __builtin_amdgcn_mfma_f32_16x16x32_bf16(bq[j_][s_], af[i_][s_], acc[i_][HB * 2 + j_], 0, 0, 0); \
-  __builtin_amdgcn_s_setprio(0);                                                                 \
-  __builtin_amdgcn_sched_barrier(0);                                                             \
-  __builtin_amdgcn_s_barrier();
-
-  // prologue: everything first read in phases 1..3 = A B0 B1 of K-tile 0, A B0 of K-tile 1 (stream indices 0..4)
-  const char *a1, *b1, *a2, *b2;  // bases of K-tiles kt + 1, kt + 2 (clamped to the last one)
-  {
-    const char *a0, *b0;
-    cursor_next(a0, b0);
-    issue_half(a0, 0, offA);
-    issue_half(b0, 0, offB);
-    issue_half(b0, halfB, offB);
-    cursor_next(a1, b1);
-    issue_half(a1, 0, offA);
-    issue_half(b1, 0, offB);
-    asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    cursor_next(a2, b2);
-  }
-  __builtin_amdgcn_s_barrier();
-  if (grp == 1) __builtin_amdgcn_s_barrier();
-
-  unsigned rofs = 0;  // byte offset of A of the current K-tile in the ring (stream index 3 kt)
-  constexpr unsigned RING = NSLOT * HALF - 1;
-  for (int kt = 0; kt < nk; ++kt) {
-    const char* sA = smem + rofs;
-    const char* sB0 = smem + ((rofs + HALF) & RING);
-    const char* sB1 = smem + ((rofs + 2 * HALF) & RING);
-    // P1 = (A, B0); issues B1 of K-tile kt + 1 (first read three phases on)
-#pragma unroll
-    for (int j_ = 0; j_ < 2; ++j_)
-#pragma unroll
-      for (int s_ = 0; s_ < 2; ++s_) bq[j_][s_] = read_frag(sB0, B_T, wc * 32 + j_ * 16, s_);
-#pragma unroll
-    for (int i_ = 0; i_ < 4; ++i_)
-#pragma unroll
-      for (int s_ = 0; s_ < 2; ++s_) af[i_][s_] = read_frag(sA, A_T, wr * 64 + i_ * 16, s_);
-    issue_half(b1, halfB, offB);
-    asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    HT_MFMA(0)
-    // P2 = (A, B1); issues A and B0 of K-tile kt + 2
-#pragma unroll
-    for (int j_ = 0; j_ < 2; ++j_)
-#pragma unroll
-      for (int s_ = 0; s_ < 2; ++s_) bq[j_][s_] = read_frag(sB1, B_T, wc * 32 + j_ * 16, s_);
-    issue_half(a2, 0, offA);
-    issue_half(b2, 0, offB);
-    asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    HT_MFMA(1)
-    rofs = (rofs + 3 * HALF) & RING;
-    a1 = a2;
-    b1 = b2;
-    cursor_next(a2, b2);
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the clamped re-fetches are still landing in the ring
-  if (grp == 0) __builtin_amdgcn_s_barrier();  // balance the stagger barrier: everyone is done with the ring
-#undef HT_MFMA
-  char* scr = smem + 8 * HALF + wave * SCR;
-  const int m0 = tm * BM + wr * 128 + h * 64, n0 = tn * BN + wc * 64;
-  if constexpr (EPI >= 3) pp_epilogue<EPI, 4>(acc, scr, p, m0, n0, 0, lane);
-  else tile_epilogue<4, 4, CW, EPI>(acc, scr, p, m0, n0, 0, lane);
-}
-
 template <int AT, int BT, int EPI>
-static int launch_half(const Gemm2Args& a, hipStream_t st) {
+static int launch_stag(const Gemm2Args& a, dim3 grid, hipStream_t st) {
   constexpr int smem = 160 * 1024;
   static bool attr_done = false;
-  auto fn = gemm3h_kernel<AT, BT, EPI>;
-  if (!attr_done) {
-    VIT_HIP(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-    attr_done = true;
-  }
-  hipLaunchKernelGGL(fn, dim3(2 * a.tail_n), dim3(512), smem, st, a);
-  VIT_LAUNCH_CHECK();
-  return VIT_OK;
-}
-// instantiated for Y = X W^T with bias / dropout (3) or GELU (4) and for dX = dY W (6); the GELU kind only on request
-// (gemm_half_tail = 2): at 9.2 rounds the 0.2 of a round it could save is less than the second launch costs (measured)
-static int launch_half_cfg(const Gemm2Args& a, int epi, hipStream_t st) {
-  if (epi == 3) return launch_half<0, 0, 3>(a, st);
-  if (epi == 4) return launch_half<0, 0, 4>(a, st);
-  return launch_half<0, 1, 6>(a, st);
-}
-
-// Sum of the tail tiles' K-slices + the epilogue the ping-pong kernel would have run (EPI 3: +bias, dropout -> bf16; 6: plain ->
-// bf16): block = 8 rows x 256 columns of one tile, a thread owns 8 consecutive columns; slices are added in index order.
-template <int EPI>
-__global__ __launch_bounds__(256) void tail_reduce_kernel(Gemm2Args p) {
-  resolve_drop(p.drop);
-  const int tl = blockIdx.x >> 5, r = ((blockIdx.x & 31) << 3) + (threadIdx.x >> 5), cg = threadIdx.x & 31;
-  const int t = p.tail_first + tl, tm = t / p.tiles_n, tn = t - tm * p.tiles_n;
-  const float* src = p.slab + (long)tl * 65536 + r * 256 + cg * 8;
-  f32x4 v0 = *(const f32x4*)src, v1 = *(const f32x4*)(src + 4);
-  for (int s = 1; s < p.splits; ++s) {
-    const float* q = src + (long)s * p.slab_tiles * 65536;
-    v0 += *(const f32x4*)q;
-    v1 += *(const f32x4*)(q + 4);
-  }
-  const long m = (long)tm * 256 + r;
-  const int n = tn * 256 + cg * 8;
-  float o[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
-  if (EPI == 3) {
-    if (p.bias) {
-      const f32x4 b0 = *(const f32x4*)(p.bias + n), b1 = *(const f32x4*)(p.bias + n + 4);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        o[i] += b0[i];
-        o[4 + i] += b1[i];
-      }
-    }
-    if (p.drop.thr) {
-      const unsigned half_cols = (unsigned)(p.N >> 1);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        float k0, k1;
-        drop_pair(p.drop, (unsigned long long)m, half_cols, (unsigned)n + 2 * i, k0, k1);
-        o[2 * i] *= k0;
-        o[2 * i + 1] *= k1;
-      }
-    }
-  }
-  const u32x4 pk = {pack2bf(o[0], o[1]), pack2bf(o[2], o[3]), pack2bf(o[4], o[5]), pack2bf(o[6], o[7])};
-  *(u32x4*)(p.C + (m * p.ldc + n) * 2) = pk;
-}
-static int launch_tail_reduce(const Gemm2Args& a, int epi, hipStream_t st) {
-  if (epi == 3) hipLaunchKernelGGL(tail_reduce_kernel<3>, dim3(a.slab_tiles * 32), dim3(256), 0, st, a);
-  else hipLaunchKernelGGL(tail_reduce_kernel<6>, dim3(a.slab_tiles * 32), dim3(256), 0, st, a);
-  VIT_LAUNCH_CHECK();
-  return VIT_OK;
-}
-
-int g_split_tail = 1;  // vit_set_option("gemm_split_tail"): K-slices instead of half tiles for a short tail of a long-K GEMM
-int g_grp2 = 1;  // vit_set_option("gemm_ngroups"): 1 = two N-groups for weights larger than an L2 (see tile_coords)
-// vit_set_option("gemm_half_tail").  Default 0 since r05: the second launch shortens the N = 768 products themselves (-5...9 % in
-// the micro-benchmark) but spends 5 % more CU-time (a half tile costs 0.7 of a tile), and the step is power-limited: with it off,
-// one launch of ceil(tiles / rounds) workgroups leaves 59 CUs idle for the kernel and every OTHER kernel of the step runs 1-3 %
-// faster (FC1 299 -> 292 us, attention backward 288 -> 281, dW 145.3 -> 143.3; step -0.4 ms at ViT-B on three boxes, ViT-L with
-// its second stream 53.6 -> 51.7 ms)
-int g_half_tail = 0;
-int g_balance_wgs = 1;  // vit_set_option("gemm_balance_wgs")
-int g_pp_slots = 8;  // vit_set_option("gemm_pp_slots"): half-tile slots of the ping-pong ring, 8 (default) or 10
-template <int AT, int BT, int EPI, int NSLOT>
-static int launch_stag_n(const Gemm2Args& a, dim3 grid, hipStream_t st) {
-  constexpr int smem = 160 * 1024;
-  static bool attr_done = false;
-  auto fn = gemm3_kernel<AT, BT, EPI, NSLOT>;
+  auto fn = gemm3_kernel<AT, BT, EPI, 8>;
   if (!attr_done) {
     VIT_HIP(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
     attr_done = true;
@@ -1136,10 +719,6 @@ static int launch_stag_n(const Gemm2Args& a, dim3 grid, hipStream_t st) {
   hipLaunchKernelGGL(fn, grid, dim3(512), smem, st, a);
   VIT_LAUNCH_CHECK();
   return VIT_OK;
-}
-template <int AT, int BT, int EPI>
-static int launch_stag(const Gemm2Args& a, dim3 grid, hipStream_t st) {
-  return launch_stag_n<AT, BT, EPI, 8>(a, grid, st);
 }
 static int launch_stag_cfg(const Gemm2Args& a, int at, int bt, int epi, dim3 grid, hipStream_t st) {
   if (epi == 1) return launch_stag<0, 0, 1>(a, grid, st);
@@ -1149,12 +728,7 @@ static int launch_stag_cfg(const Gemm2Args& a, int at, int bt, int epi, dim3 gri
   if (epi == 5) return launch_stag<0, 1, 5>(a, grid, st);
   if (epi == 6) return launch_stag<0, 1, 6>(a, grid, st);
   if (epi == 8) return launch_stag<0, 0, 8>(a, grid, st);
-  if (epi == 7) {
-    if (at && bt) return launch_stag<1, 1, 7>(a, grid, st);
-    if (!at && !bt) return launch_stag<0, 0, 7>(a, grid, st);  // the next two: K-slices of a forward / dX GEMM's tail tiles
-    if (!at && bt) return launch_stag<0, 1, 7>(a, grid, st);
-    return VIT_ERR_ARG;
-  }
+  if (epi == 7) return launch_stag<1, 1, 7>(a, grid, st);  // chosen only for a_trans && b_trans
   if (!at && !bt) return launch_stag<0, 0, 0>(a, grid, st);
   if (!at && bt) return launch_stag<0, 1, 0>(a, grid, st);
   if (at && !bt) return launch_stag<1, 0, 0>(a, grid, st);
@@ -1162,24 +736,11 @@ static int launch_stag_cfg(const Gemm2Args& a, int at, int bt, int epi, dim3 gri
 }
 
 extern thread_local int g_colsum_fused, g_rope_fused;  // gemm.hip
-#ifdef VIT_PP_STAMP
-unsigned long long* g_pp_stamps = nullptr;
-int g_pp_stamp_block = 0;
-#endif
-int g_gemm2_mode = -1;  // -1: read VIT_GEMM2 from the environment on first use
-#ifdef VIT_PP_DIAG
-int g_gemm2_debug = 0;  // diagnostic twin build only: vit_debug_pp_diag()
-#endif
+int g_gemm2_mode = 1;  // vit_set_option("gemm_core"): 0 = generic 128x128 core only, else the ping-pong kernel where eligible
 
 // returns 1 if handled (rc in *rc), 0 if the shape is not eligible
 int gemm2_try_launch(vit_handle h, const vit_gemm_desc* d, hipStream_t st, int* rc) {
-  if (g_gemm2_mode < 0) {
-    const char* e = getenv("VIT_GEMM2");
-    g_gemm2_mode = e ? atoi(e) : 1;
-  }
-  // 0 = off (generic 128x128 core only); 1 = automatic, 5 = the same choice named explicitly: the 256x256x64 ping-pong kernel
-  const int mode = g_gemm2_mode;
-  if (mode == 0) return 0;
+  if (g_gemm2_mode == 0) return 0;
   if (d->M % 256 || d->N % 256 || d->K % 64) return 0;  // other shapes stay on the register-staged 128x128 core
   if (d->lda * 256 >= (1L << 30) || d->ldb * 256 >= (1L << 30)) return 0;  // int offsets inside a tile
   int epi = 0;
@@ -1190,15 +751,13 @@ int gemm2_try_launch(vit_handle h, const vit_gemm_desc* d, hipStream_t st, int* 
     if (d->a_trans || !d->b_trans) return 0;
     epi = 2;
   }
-  constexpr int cfg = 5;
-  const int bn = 256;
   const int slots = ctx_num_cus(h);  // one workgroup per CU
 
   Gemm2Args a;
   a.A = (const char*)d->A; a.B = (const char*)d->B; a.C = (char*)d->C;
   a.lda = d->lda; a.ldb = d->ldb; a.ldc = d->ldc;
   a.M = d->M; a.N = d->N; a.K = d->K;
-  a.tiles_m = d->M / 256; a.tiles_n = d->N / bn;
+  a.tiles_m = d->M / 256; a.tiles_n = d->N / 256;
   const int ntile = a.tiles_m * a.tiles_n;
   const int ktiles = d->K / 64;
   int splits = d->split_k;
@@ -1226,7 +785,6 @@ int gemm2_try_launch(vit_handle h, const vit_gemm_desc* d, hipStream_t st, int* 
     a.slab = (float*)ws;
   }
   a.nblk = std::min(ntile, slots);
-  a.tile_limit = 0; a.tail_first = 0; a.tail_n = 0; a.slab_tiles = 0;
   a.bias = d->bias;
   a.aux_in = (const short*)d->aux_in; a.aux_out = (short*)d->aux_out; a.ldaux = d->ldaux;
   a.residual = d->residual; a.ldres = d->ldres;
@@ -1239,87 +797,55 @@ int gemm2_try_launch(vit_handle h, const vit_gemm_desc* d, hipStream_t st, int* 
   a.act = d->act; a.c_dtype = d->c_dtype;
   a.drop = make_drop_h(h, d->dropout_p, d->seed, d->site);
   a.rpb = d->rows_per_batch; a.orb = d->out_batch_rows; a.roff = d->out_row_offset;
-#ifdef VIT_PP_DIAG
-  a.debug = g_gemm2_debug;
-#endif
-#ifdef VIT_PP_STAMP
-  a.stamps = g_pp_stamps;
-  a.stamp_block = g_pp_stamp_block;
-#endif
 
   dim3 grid(a.nblk, splits);
   a.lin_split = 0;
   a.colsum_part = nullptr;
-  if (cfg == 5 && splits > 1 && a.nblk == ntile) {
+  if (splits > 1 && a.nblk == ntile) {
     a.lin_split = 1;
     grid = dim3(ntile * splits, 1);
   }
-  int epi5 = epi;  // ping-pong kernel: the specialised epilogue when the descriptor is one of the five hot kinds
-  if (cfg == 5) {
-    const bool plain = !a.residual && a.rpb == 0 && d->alpha == 1.0f;
-    if (epi == 1 && plain && a.bias && d->c_dtype == VIT_BF16 && !a.drop.thr && splits == 1) epi5 = 4;
-    else if (epi == 2 && plain && !a.bias && d->c_dtype == VIT_BF16 && !a.drop.thr && splits == 1) epi5 = 5;
-    else if (epi == 0 && plain && d->c_dtype == VIT_BF16 && !d->a_trans && !d->b_trans && splits == 1) epi5 = 3;
-    else if (epi == 0 && plain && !a.bias && !a.drop.thr && d->c_dtype == VIT_BF16 && !d->a_trans && d->b_trans &&
-             splits == 1) epi5 = 6;
-    else if (epi == 0 && plain && !a.bias && !a.drop.thr && d->c_dtype == VIT_F32 && d->a_trans && d->b_trans) epi5 = 7;
-    // rotary embedding requested: the rotating epilogue where a wave's 64 columns are whole heads, else the caller (gemm_launch)
-    // runs the separate pass behind this launch
-    if (d->rope_cos) {
-      if (epi5 == 3 && !a.drop.thr && (d->rope_dh == 16 || d->rope_dh == 32 || d->rope_dh == 64) && (d->rope_cols % 64) == 0 &&
-          d->rope_T >= 9)  // the epilogue steps its angles by table row 8
-        epi5 = 8;
-    }
-    // the bf16 fast epilogues store through 32-bit buffer offsets (raw buffer stores, sc1): outputs past 2 GiB keep the
-    // generic epilogue (a clamped descriptor would drop the stores beyond it silently)
-    if (((epi5 >= 3 && epi5 <= 6) || epi5 == 8) &&
-        ((unsigned long long)d->M * d->ldc * 2 >= 0x7FFFFFF0ull ||
-         ((d->aux_out || d->aux_in) && (unsigned long long)d->M * d->ldaux * 2 >= 0x7FFFFFF0ull)))  // aux_in: epilogue 5's loads
-      epi5 = epi;
+  // the specialised epilogue when the descriptor is one of the five hot kinds
+  int epi5 = epi;
+  const bool plain = !a.residual && a.rpb == 0 && d->alpha == 1.0f;
+  if (epi == 1 && plain && a.bias && d->c_dtype == VIT_BF16 && !a.drop.thr && splits == 1) epi5 = 4;
+  else if (epi == 2 && plain && !a.bias && d->c_dtype == VIT_BF16 && !a.drop.thr && splits == 1) epi5 = 5;
+  else if (epi == 0 && plain && d->c_dtype == VIT_BF16 && !d->a_trans && !d->b_trans && splits == 1) epi5 = 3;
+  else if (epi == 0 && plain && !a.bias && !a.drop.thr && d->c_dtype == VIT_BF16 && !d->a_trans && d->b_trans &&
+           splits == 1) epi5 = 6;
+  else if (epi == 0 && plain && !a.bias && !a.drop.thr && d->c_dtype == VIT_F32 && d->a_trans && d->b_trans) epi5 = 7;
+  // rotary embedding requested: the rotating epilogue where a wave's 64 columns are whole heads, else the caller (gemm_launch)
+  // runs the separate pass behind this launch
+  if (d->rope_cos) {
+    if (epi5 == 3 && !a.drop.thr && (d->rope_dh == 16 || d->rope_dh == 32 || d->rope_dh == 64) && (d->rope_cols % 64) == 0 &&
+        d->rope_T >= 9)  // the epilogue steps its angles by table row 8
+      epi5 = 8;
   }
-  // the tiles of a partial last round go to the half-tile kernel (two workgroups per tile) when the epilogue is one of
-  // the kinds instantiated for it and nothing else rides on the launch
-  int half_tail = 0;
-  if (cfg == 5 && g_half_tail && (epi5 == 3 || epi5 == 6 || (epi5 == 4 && g_half_tail > 1)) && splits == 1 && ntile > slots && !d->colsum_out) {
-    const int tail = ntile % slots;
-    if (tail > 0 && 2 * tail <= slots && d->K / 64 >= 4) half_tail = tail;
-  }
-  if (cfg == 5 && g_balance_wgs && splits == 1 && ntile - half_tail > slots) {
+  // the bf16 fast epilogues store through 32-bit buffer offsets (raw buffer stores, sc1): outputs past 2 GiB keep the
+  // generic epilogue (a clamped descriptor would drop the stores beyond it silently)
+  if (((epi5 >= 3 && epi5 <= 6) || epi5 == 8) &&
+      ((unsigned long long)d->M * d->ldc * 2 >= 0x7FFFFFF0ull ||
+       ((d->aux_out || d->aux_in) && (unsigned long long)d->M * d->ldaux * 2 >= 0x7FFFFFF0ull)))  // aux_in: epilogue 5's loads
+    epi5 = epi;
+  if (splits == 1 && ntile > slots) {
     // multi-round persistent walk: the makespan is ceil(tiles / slots) tile-times whatever the workgroup count, so launch
-    // just enough workgroups for that many rounds: the idle CUs' power budget goes to the busy ones' clock
-    a.nblk = cdiv(ntile - half_tail, cdiv(ntile - half_tail, slots));
+    // just enough workgroups for that many rounds: the idle CUs' power budget goes to the busy ones' clock.  This holds
+    // for a partial last round too (591 tiles on 256 CUs: 3 rounds of 197 workgroups).  Running that round's tiles as
+    // half tiles on twice as many workgroups shortened the product itself but cost 5 % more CU-time, and the step is
+    // power-limited: with one launch every OTHER kernel of the step ran 1-3 % faster (ViT-B step -0.4 ms, ViT-L with its
+    // second stream 53.6 -> 51.7 ms).
+    a.nblk = cdiv(ntile, cdiv(ntile, slots));
     grid = dim3(a.nblk, splits);
   }
   a.grp2 = 0;
-  if (cfg == 5 && g_grp2 && splits == 1 && !half_tail && !a.lin_split && (a.tiles_n % 2) == 0 &&
-      (size_t)d->N * d->K * 2 > (size_t)4 << 20 && ntile > slots && (ntile % 2) == 0) {
-    a.grp2 = 1;
+  if (splits == 1 && (a.tiles_n % 2) == 0 && (size_t)d->N * d->K * 2 > (size_t)4 << 20 && ntile > slots && (ntile % 2) == 0) {
+    a.grp2 = 1;  // weights larger than an L2: two N-groups of XCDs (see tile_coords)
     if (a.nblk & 1) {  // each round must split into two equal halves
       a.nblk += 1;
       grid = dim3(a.nblk, splits);
     }
   }
-  if (half_tail) {
-    a.tile_limit = ntile - half_tail;
-    a.tail_first = ntile - half_tail;
-    a.tail_n = half_tail;
-  }
-  // A SHORT tail of a LONG-K product (ViT-L: 36 of 292 tiles, K = 3072 / 4096) runs as K-slices instead: every workgroup does a
-  // whole 256 x 256 tile at the main loop's efficiency over K / s, s = slots / tail, and a small kernel adds the slices and runs
-  // the epilogue.  The f32 partials cost 2 x s x 256 KiB of traffic per tile, so it only pays from s >= 4 (priced in DESIGN
-  // section 7: a wash at ViT-B's 79-tile tails with s = 3).
-  int st_splits = 0, st_kps = 0;
-  if (half_tail && g_split_tail && (epi5 == 3 || epi5 == 6)) {
-    const int s_ = slots / half_tail;
-    if (s_ >= (g_split_tail >= 2 ? 3 : 4) && ktiles / s_ >= 6) {  // gemm_split_tail = 2: from 3 slices (ViT-B's 79-tile tails; measured a wash)
-      st_kps = cdiv(ktiles, s_) * 64;
-      st_splits = cdiv(d->K, st_kps);
-      size_t wsb = 0;
-      void* ws = ctx_workspace(h, &wsb);
-      if (!ws || wsb < (size_t)st_splits * half_tail * 65536 * sizeof(float)) st_splits = 0;
-    }
-  }
-  if (d->colsum_out && cfg == 5 && (epi5 == 3 || epi5 == 5 || epi5 == 6)) {
+  if (d->colsum_out && (epi5 == 3 || epi5 == 5 || epi5 == 6)) {
     size_t wsb = 0;
     void* ws = ctx_workspace(h, &wsb);
     if (ws && wsb >= (size_t)a.tiles_m * 2 * d->N * sizeof(float)) a.colsum_part = (float*)ws;
@@ -1330,20 +856,6 @@ int gemm2_try_launch(vit_handle h, const vit_gemm_desc* d, hipStream_t st, int* 
   }
   if (epi5 == 8) g_rope_fused = 1;
   int r = launch_stag_cfg(a, d->a_trans, d->b_trans, epi5, grid, st);
-  if (r == VIT_OK && half_tail && st_splits > 1) {
-    Gemm2Args b = a;
-    size_t wsb = 0;
-    b.slab = (float*)ctx_workspace(h, &wsb);
-    b.slab_tiles = half_tail;
-    b.splits = st_splits; b.k_per_split = st_kps;
-    b.lin_split = 1; b.grp2 = 0;
-    b.tile_limit = half_tail;  // the kernel's tile count; tile ids are tail_first + 0 .. half_tail - 1
-    b.nblk = half_tail;
-    r = launch_stag_cfg(b, 0, d->b_trans, 7, dim3(half_tail * st_splits), st);
-    if (r == VIT_OK) r = launch_tail_reduce(b, epi5, st);
-  } else if (r == VIT_OK && half_tail) {
-    r = launch_half_cfg(a, epi5, st);
-  }
   if (r == VIT_OK && a.colsum_part) {
     r = launch_reduce_partials(a.colsum_part, a.tiles_m * 2, d->N, d->colsum_out, d->N, d->colsum_out, 0, st);
     g_colsum_fused = 1;

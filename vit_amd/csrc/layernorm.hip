@@ -6,10 +6,6 @@
 
 #include "common.h"
 
-#ifndef VIT_LNF_BLOCKS4
-#define VIT_LNF_BLOCKS4 1792
-#endif
-
 namespace vit {
 
 void* ctx_workspace(vit_handle h, size_t* bytes);
@@ -218,8 +214,9 @@ template <int OUT_BF16, int RES>
 static int ln_fwd_dispatch(const float* x, const float* g, const float* b, void* y, float* mean, float* rstd, int rows,
                            int D, float eps, hipStream_t st, const void* delta = nullptr, float* xsum = nullptr) {
   const int nv = cdiv(D, 256);
-  // one round of resident 4-wave blocks: 8 per CU up to D = 768 (<= 64 VGPRs), 7 at D = 1024 (72 VGPRs)
-  const int blocks = std::min(cdiv(rows, 4), nv >= 4 ? VIT_LNF_BLOCKS4 : 2048);
+  // one round of resident 4-wave blocks over 256 CUs: 8 per CU up to D = 768 (<= 64 VGPRs), 7 at D = 1024 (72 VGPRs)
+  constexpr int BLOCKS_NARROW = 2048, BLOCKS_WIDE = 1792;
+  const int blocks = std::min(cdiv(rows, 4), nv >= 4 ? BLOCKS_WIDE : BLOCKS_NARROW);
 #define LAUNCH(NV) hipLaunchKernelGGL((ln_fwd_kernel<NV, OUT_BF16, RES>), dim3(blocks), dim3(256), 0, st, x, g, b, y, mean, rstd, rows, D, eps, delta, xsum)
   if (nv <= 1) LAUNCH(1);
   else if (nv <= 2) LAUNCH(2);
