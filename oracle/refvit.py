@@ -23,7 +23,7 @@ from __future__ import annotations
 
 import math
 from dataclasses import dataclass, field
-from typing import Dict, List, Optional
+from typing import Callable, Dict, List, Optional
 
 import numpy as np
 import torch
@@ -287,18 +287,25 @@ def forward(
     p_attn: Optional[float] = None,
     output_hidden_states: bool = False,
     output_attentions: bool = False,
+    masks: Optional[Callable[[int, tuple], torch.Tensor]] = None,
 ) -> RefOutput:
     """MyViT.forward (specvit.py:68-94) over HF ViTModel.forward semantics.
 
-    Dropout uses torch's CPU generator when `training`; parity tests run it with p=0 or training=False because dropout
-    masks are implementation-defined (hard parts)."""
+    Dropout, when `training`: without `masks`, torch's CPU generator (F.dropout; the reference's masks are
+    implementation-defined).  With `masks` -- a callable (site, shape) -> float32 multiplier, e.g.
+    oracle.dropmask.engine_masks -- each dropout becomes `t * masks(site, t.shape)` at the engine's site numbers: 0 for the
+    embedding, 1 + 4 * layer + {0: attention probabilities (shape [B, H, T, T]), 1: attention-output projection, 2: FC2}."""
     ph = cfg.hidden_dropout_prob if p_hidden is None else p_hidden
     pa = cfg.attention_probs_dropout_prob if p_attn is None else p_attn
     B = x.size(0)
     D, H, dh = cfg.hidden_size, cfg.num_attention_heads, cfg.head_dim
 
-    def drop(t, p):
-        return F.dropout(t, p=p, training=training) if (training and p > 0) else t
+    def drop(t, p, site):
+        if not training:
+            return t
+        if masks is not None:
+            return t * masks(site, tuple(t.shape)).to(t.dtype)
+        return F.dropout(t, p=p, training=True) if p > 0 else t
 
     # --- embeddings (embedding.py:79-100)
     tok = tokenize(cfg, sd, x)
@@ -307,7 +314,7 @@ def forward(
         h = h + sd["vit.embeddings.position_embeddings"]
     elif cfg.pos_encoding_type not in (None, "none", "rope"):
         raise ValueError(f"Unsupported pos_encoding_type '{cfg.pos_encoding_type}'")
-    h = drop(h, ph)
+    h = drop(h, ph, 0)
 
     hs = [h] if output_hidden_states else None
     atts = [] if output_attentions else None
@@ -334,15 +341,15 @@ def forward(
         probs = F.softmax(scores, dim=-1)
         if output_attentions:
             atts.append(probs)
-        ctx = torch.matmul(drop(probs, pa), v)
+        ctx = torch.matmul(drop(probs, pa, 1 + 4 * i), v)
         ctx = ctx.transpose(1, 2).contiguous().view(B, T, D)
         a = F.linear(ctx, sd[pre + "attention.output.dense.weight"], sd[pre + "attention.output.dense.bias"])
-        h = drop(a, ph) + res
+        h = drop(a, ph, 2 + 4 * i) + res
         res = h
         y = F.layer_norm(h, (D,), sd[pre + "layernorm_after.weight"], sd[pre + "layernorm_after.bias"], cfg.layer_norm_eps)
         y = F.gelu(F.linear(y, sd[pre + "intermediate.dense.weight"], sd[pre + "intermediate.dense.bias"]))  # erf GELU
         y = F.linear(y, sd[pre + "output.dense.weight"], sd[pre + "output.dense.bias"])
-        h = drop(y, ph) + res
+        h = drop(y, ph, 3 + 4 * i) + res
         if output_hidden_states:
             hs.append(h)
     last = F.layer_norm(h, (D,), sd["vit.layernorm.weight"], sd["vit.layernorm.bias"], cfg.layer_norm_eps)
@@ -389,10 +396,11 @@ class RefTrainer:
         self.p_hidden, self.p_attn = p_hidden, p_attn
         self.last_grad_norm = None
 
-    def step(self, flux: torch.Tensor, labels: torch.Tensor) -> float:
+    def step(self, flux: torch.Tensor, labels: torch.Tensor, masks: Optional[Callable] = None) -> float:
+        """`masks`: as in forward() (this step's dropout masks; used when the trainer runs with training=True)."""
         self.opt.zero_grad(set_to_none=True)
         out = forward(self.cfg, self.params, flux, labels, training=self.training, p_hidden=self.p_hidden,
-                      p_attn=self.p_attn)
+                      p_attn=self.p_attn, masks=masks)
         out.loss.backward()
         with_grad = [p for p in self.params.values() if p.grad is not None]  # the pooler never gets one
         self.last_grad_norm = float(torch.nn.utils.clip_grad_norm_(with_grad, self.grad_clip))

@@ -216,3 +216,35 @@ def test_deep_c3_training_steps(dev, precision):
         tl, tg = (5e-4, 5e-4) if precision == "32" else (5e-2, 5e-2)
         assert abs(float(loss) - g["step_losses"][s]) <= tl * g["step_losses"][s] + (0 if precision == "32" else 2e-3)
         assert abs(gn - g["step_grad_norms"][s]) <= tg * g["step_grad_norms"][s]
+
+
+# ------------------------------------------------------------------ train mode, dropout on, at the benchmarked geometries
+_train_cache = {}
+
+
+@pytest.mark.parametrize("tag,precision", [("c3", "bf16-mixed"), ("c3", "32"), ("c5", "bf16-mixed"), ("s4", "bf16-mixed"),
+                                           ("s4", "32")])
+def test_deep_train_mode_dropout_matches_oracle(dev, tag, precision):
+    """Dropout on against the oracle with the masks oracle/dropmask.py restates (tests/test_parity_gpu.py::check_train_parity):
+    C3 at B = 4 is the benchmarked geometry (the pipelined attention backward <true,12,true>, the ping-pong dropout
+    epilogues, zero-padded GEMM rows); C5 at B = 2 (bf16-mixed) runs the ViT-L resident attention pair at T 577; s4 is the
+    6-layer sweep corner.  Gates: this file's eval-mode gates, and for bf16 the worst hidden state and worst gradient tensor
+    within 1.5 x the same model's eval-mode ones + 1e-3."""
+    from test_parity_gpu import check_train_parity, oracle_pass, step_masks
+
+    o = oracle_run(tag)
+    rc, step = o["rc"], 3
+    if tag not in _train_cache:
+        _train_cache.clear()
+        _train_cache[tag] = oracle_pass(rc, o["sd"], o["flux"], o["labels"], masks=step_masks(rc, step))
+    model = build(o, dev, precision)
+    tol = bf16_factor(tag) * float(np.max(o["ref_bf16_grad_err"])) + 1e-3
+    # the loss gate of test_deep_eval_forward: 3e-2 + the MSE floor 4 sqrt(loss) e_logits rms(logits), relative to the loss,
+    # with the logits error at the bf16 hidden-state gate
+    lg = o["logits"].double()
+    floor = 4.0 * o["loss"] ** 0.5 * 1.5e-2 * float(lg.pow(2).mean().sqrt()) / o["loss"]
+    g = o["g"]  # logits: test_deep_eval_forward's yardstick, the reference's own bf16-autocast error
+    e_ref_bf16 = max(rel(g["bf16_logits"], g["logits"]), rel(g["bf16_last_rows"], g["last_rows"]))
+    check_train_parity(tag, rc, o["sd"], model, o["flux"].to(dev), o["labels"].to(dev), precision, step=step,
+                       bf16_grad_tol=tol, bf16_loss_tol=3e-2 + floor, bf16_logits_tol=bf16_factor(tag) * e_ref_bf16 + 1e-3,
+                       oracle_eval=o, oracle_train=_train_cache[tag])
