@@ -52,7 +52,7 @@ int vit_set_workspace(vit_handle h, void* ws, size_t bytes);
  *   "gemm_core": 0 = generic 128x128 core only, 1 = automatic (default): tile-aligned problems (M, N multiples of 256, K of
  *                64) run the 256x256x64 ping-pong core (wave halves one barrier out of phase: LOAD segment beside MFMA
  *                segment, ring of 8 half-tiles, 4 in flight); 5 = the same choice named explicitly.
- *   "attn_split": workgroups per (batch, head) in the resident attention kernels (T <= 256), default 2.
+ *   "attn_split": workgroups per (batch, head) in the resident attention kernels (T <= 592 at head_dim 64), default 2.
  *   "attn_bwd_fused": attention backward form: non-zero (default 4) = the pair-pipelined single kernel where it fits (head_dim
  *                64, 64 <= T <= 208), the dQ + dK/dV pair elsewhere; 0 = the dQ + dK/dV pair everywhere.  (The values 1 .. 3
  *                named the single-kernel forms of round 2, removed in round 4; they are accepted and mean the default.)
@@ -184,32 +184,23 @@ int vit_layernorm_bwd_fused(vit_handle h, const void* dy, int dy_dtype, const fl
  * io_dtype = VIT_BF16: the MFMA flash kernels (qkv / ctx / dctx / dqkv bf16).  io_dtype = VIT_F32: the same tensors in
  * f32 and exact fp32 arithmetic (the precision='32' path; T <= 4096).
  */
-int vit_attention_fwd(vit_handle h, const void* qkv, void* ctx, float* lse, int io_dtype, int B, int H, int T, int dh,
-                      float scale, float dropout_p, uint64_t seed, uint64_t site, vit_stream stream);
+/* ctx_lo (bf16 [B*T, H*dh], may be NULL): the forward also stores the rounding residual ctx_exact - bf16(ctx_exact), so that
+ * the backward can form delta = rowsum(dctx * (ctx + ctx_lo)) with the context kept to ~16 mantissa bits.  Why: the softmax
+ * backward is dS = P o (dP - delta); the reference (autocast, vit_with_rope.py:63-81 under basemodule.py:233) takes
+ * delta = sum_j P_j dP_j in fp32, which cancels exactly against dP.  rowsum(dctx * ctx) with an 8-bit ctx is off by an amount
+ * COMMON to a score row, which survives the sum over keys in dQ / dK once token representations share a large common
+ * component (deep layers): 5e-2 on ViT-L's late query weights against the reference's own bf16 1.1e-2; with the residual 1e-2
+ * or better (tests/test_parity_deep_gpu.py).  io_dtype = VIT_F32 ignores ctx_lo. */
+int vit_attention_fwd(vit_handle h, const void* qkv, void* ctx, void* ctx_lo, float* lse, int io_dtype, int B, int H, int T,
+                      int dh, float scale, float dropout_p, uint64_t seed, uint64_t site, vit_stream stream);
 /* dqkv: bf16 [B*T, 3*H*dh] from dctx: bf16 [B*T, H*dh]; recomputes probabilities from lse. delta: f32 [B*H, T]
- * scratch (rowsum(dctx*ctx)), written by this call. */
-int vit_attention_bwd(vit_handle h, const void* qkv, const void* ctx, const void* dctx, const float* lse,
-                      float* delta, void* dqkv, int io_dtype, int B, int H, int T, int dh, float scale,
-                      float dropout_p, uint64_t seed, uint64_t site, vit_stream stream);
-/* Same, and dqkv_colsum (f32 [3*H*dh]) = the column sums of dqkv as stored: the bias gradient of the fused QKV projection
- * (without RoPE; with it the sums must be taken after the inverse rotation).  The resident bf16 kernels sum their own rows
- * on the way out (one partial row per wave through the workspace); other paths run vit_colsum afterwards. */
-int vit_attention_bwd_colsum(vit_handle h, const void* qkv, const void* ctx, const void* dctx, const float* lse,
-                             float* delta, void* dqkv, int io_dtype, int B, int H, int T, int dh, float scale,
-                             float dropout_p, uint64_t seed, uint64_t site, float* dqkv_colsum, vit_stream stream);
-/* Training pair with the context kept to ~16 mantissa bits.  ctx_lo (bf16 [B*T, H*dh], may be NULL = the calls above):
- * the forward also stores the rounding residual ctx_exact - bf16(ctx_exact); the backward forms
- * delta = rowsum(dctx * (ctx + ctx_lo)).  Why: the softmax backward is dS = P o (dP - delta); the reference (autocast,
- * vit_with_rope.py:63-81 under basemodule.py:233) takes delta = sum_j P_j dP_j in fp32, which cancels exactly against dP.
- * rowsum(dctx * ctx) with an 8-bit ctx is off by an amount COMMON to a score row, which survives the sum over keys in dQ / dK
- * once token representations share a large common component (deep layers): 5e-2 on ViT-L's late query weights against
- * the reference's own bf16 1.1e-2; with the residual 1e-2 or better (tests/test_parity_deep_gpu.py).  dqkv_colsum may be
- * NULL.  io_dtype = VIT_F32 ignores ctx_lo. */
-int vit_attention_fwd_lo(vit_handle h, const void* qkv, void* ctx, void* ctx_lo, float* lse, int io_dtype, int B, int H,
-                         int T, int dh, float scale, float dropout_p, uint64_t seed, uint64_t site, vit_stream stream);
-int vit_attention_bwd_lo(vit_handle h, const void* qkv, const void* ctx, const void* ctx_lo, const void* dctx,
-                         const float* lse, float* delta, void* dqkv, int io_dtype, int B, int H, int T, int dh, float scale,
-                         float dropout_p, uint64_t seed, uint64_t site, float* dqkv_colsum, vit_stream stream);
+ * scratch (rowsum(dctx * (ctx + ctx_lo)); ctx_lo may be NULL: rowsum(dctx * ctx)), written by this call.
+ * dqkv_colsum (f32 [3*H*dh], may be NULL) = the column sums of dqkv as stored: the bias gradient of the fused QKV projection
+ * (without RoPE; with it the sums must be taken after the inverse rotation).  The resident and pipelined bf16 kernels sum
+ * their own rows on the way out (one partial row per wave through the workspace); other paths run vit_colsum afterwards. */
+int vit_attention_bwd(vit_handle h, const void* qkv, const void* ctx, const void* ctx_lo, const void* dctx, const float* lse,
+                      float* delta, void* dqkv, int io_dtype, int B, int H, int T, int dh, float scale, float dropout_p,
+                      uint64_t seed, uint64_t site, float* dqkv_colsum, vit_stream stream);
 /* Attention probabilities [B, H, T, T] f32 (eval-mode, for output_attentions=True: specvit.py:92-93). */
 int vit_attention_probs(vit_handle h, const void* qkv, float* probs, int io_dtype, int B, int H, int T, int dh,
                         float scale, vit_stream stream);

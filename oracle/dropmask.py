@@ -15,7 +15,8 @@ Layouts of the engine's sites (vit_amd/engine.py:364-395):
     before it draws;
   * site 0 = embedding dropout, site 1 + 4 * layer + {0: attention probabilities, 1: attention-output projection, 2: FC2};
   * hidden / embedding sites are [B*T, D] with row b*T + t (the CLS row included, t = 0);
-  * attention is [B*H*T, T] with row (b*H + h)*T + q and column = key (attention.hip:165, 299, 413, 1947).
+  * attention is [B*H*T, T] with row (b*H + h)*T + q and column = key (attn_fwd_kernel, attn_bwd_dq_kernel,
+    attn_bwd_dkv_kernel, attn32_row_kernel and the other forms in vit_amd/csrc/attention_*.hip).
 """
 from __future__ import annotations
 

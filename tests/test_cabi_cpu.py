@@ -54,7 +54,8 @@ def test_error_path_without_gpu():
 
 @pytest.fixture(scope="module")
 def kernel_isa(tmp_path_factory):
-    """ISA text of attention.hip and gemm2.hip as hipcc emits it for gfx950 (cross-compiled: no GPU needed)."""
+    """ISA text of the attention kernel files the tests below look into (the pipelined and the resident family, under the key
+    "attention") and of gemm2.hip, as hipcc emits it for gfx950 (cross-compiled: no GPU needed)."""
     import shutil
     import subprocess
 
@@ -64,11 +65,12 @@ def kernel_isa(tmp_path_factory):
     root = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "vit_amd", "csrc")
     d = tmp_path_factory.mktemp("isa")
     out = {}
-    for f in ("attention", "gemm2"):
+    for f in ("attention_pipe", "attention_resident", "gemm2"):
         o = d / (f + ".s")
         subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only", os.path.join(root, f + ".hip"),
                         "-o", str(o)], check=True, capture_output=True, cwd=str(d))
         out[f] = o.read_text()
+    out["attention"] = out.pop("attention_pipe") + out.pop("attention_resident")
     return out
 
 

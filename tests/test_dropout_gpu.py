@@ -4,7 +4,7 @@ The masks are a pure function of (seed, site, row, column) (vit_amd/csrc/common.
 each one in a different kernel from the one that applied it in the forward, so each kernel is checked on its own:
   * GEMM epilogues and the elementwise kernels bit for bit (integer-valued operands make every accumulation exact);
   * attention forward: the multiplier recovered with Q = K = 0 (uniform probabilities) and a one-hot V, thresholded at
-    half the scale, equals keep_mask bit for bit, on every forward form of the dispatch (attention.hip:2391-2420);
+    half the scale, equals keep_mask bit for bit, on every forward form of the dispatch (attn_plan in attention.hip);
   * attention backward: with Q = K = V = 0 and a one-hot dO block, dV[k, d] = M[i*dh + d, k] / T recovers the backward's
     own mask, on every backward form of attention_bwd_impl; the dS path against fp64 autograd with the restated mask;
   * the bound per-step record (vit_step_state_bind / vit_step_advance) of the captured step."""
@@ -297,7 +297,7 @@ def assert_keep_bits(mask, drop, B, H, T, keys_xor=None):
     assert float((kept - scale).abs().max()) < 2e-2 * scale
 
 
-# (B, H, T, dh, dtype, what) -- every forward form of vit_attention_fwd_lo
+# (B, H, T, dh, dtype, what) -- every forward form of vit_attention_fwd
 FWD_FORMS = [
     (2, 12, 197, 64, torch.bfloat16, "resident <64,RQ,true,208,12,2,4> (attn_split 2) / <64,RQ,true> (split 1)"),
     (24, 12, 197, 64, torch.bfloat16, "ViT-B heads, B*H = 288 > 256"),

@@ -636,7 +636,7 @@ def test_gemm_gelu_grad_and_mul_aux(dev, core, dt):
 
 @pytest.mark.parametrize("B,H,T,dh", [(3, 2, 129, 16), (4, 3, 197, 64), (2, 4, 50, 32), (2, 8, 122, 4)])
 def test_attention_bwd_fused_colsum(dev, B, H, T, dh):
-    """vit_attention_bwd_colsum: the per-wave column sums the resident kernels emit, reduced over the batch, must equal
+    """vit_attention_bwd with dqkv_colsum: the per-wave column sums the resident kernels emit, reduced over the batch, must equal
     vit_colsum over the stored dqkv (same bf16-rounded values, f32 sums), with and without dropout, for 1 and 2
     workgroups per head."""
     import vit_amd.functional as vf
@@ -705,7 +705,7 @@ def test_gemm_partial_last_round(dev, M, N, K):
 
 @pytest.mark.parametrize("B,H,T,dh", [(1, 2, 197, 64), (1, 2, 577, 64), (1, 1, 640, 64)])
 def test_attention_delta_residual(dev, B, H, T, dh):
-    """vit_attention_fwd_lo / vit_attention_bwd_lo: with value rows that share a large common component (what deep layers
+    """vit_attention_fwd / vit_attention_bwd with ctx_lo: with value rows that share a large common component (what deep layers
     of a transformer look like), delta = rowsum(dO * O) from the 8-bit O is off by an amount common to each score row, which
     the sum over keys in dQ / dK does not average out.  The stored residual O - bf16(O) must (a) reconstruct O to 2^-15,
     (b) leave ctx itself unchanged, (c) bring dQ / dK to the level of the fp32 formula -- resident (197, 577) and tiled

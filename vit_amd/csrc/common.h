@@ -103,11 +103,9 @@ __host__ __device__ inline DropCfg make_drop(float p, uint64_t seed, uint64_t si
   return d;
 }
 __device__ __forceinline__ unsigned drop_rowkey(const DropCfg& d, unsigned long long row) { return drop_hash(d.k0, d.k1, row); }
-// multiplier (0 or scale) for 2 adjacent columns starting at even column `col` (`half_cols` is no longer part of the hash;
-// the parameter stays for the call sites' sake).  `row` is loop-invariant at most call sites: the compiler hoists its key.
-__device__ __forceinline__ void drop_pair(const DropCfg& d, unsigned long long row, unsigned half_cols, unsigned col,
-                                          float& m0, float& m1) {
-  (void)half_cols;
+// multiplier (0 or scale) for 2 adjacent columns starting at even column `col`.  `row` is loop-invariant at most call sites:
+// the compiler hoists its key.
+__device__ __forceinline__ void drop_pair(const DropCfg& d, unsigned long long row, unsigned col, float& m0, float& m1) {
   const unsigned h = drop_bits(drop_rowkey(d, row), col >> 1);
   m0 = ((h & 0xFFFFu) >= d.thr) ? d.scale : 0.f;
   m1 = ((h >> 16) >= d.thr) ? d.scale : 0.f;

@@ -54,8 +54,8 @@ __global__ void embed_finish_kernel(float* __restrict__ tok, const float* __rest
     if (pos) v += *(const f32x4*)(pos + (long)t * D + d);
     if (drop.thr) {
       float k0, k1, k2, k3;
-      drop_pair(drop, (unsigned long long)row, (unsigned)(D >> 1), (unsigned)d, k0, k1);
-      drop_pair(drop, (unsigned long long)row, (unsigned)(D >> 1), (unsigned)d + 2, k2, k3);
+      drop_pair(drop, (unsigned long long)row, (unsigned)d, k0, k1);
+      drop_pair(drop, (unsigned long long)row, (unsigned)d + 2, k2, k3);
       v[0] *= k0; v[1] *= k1; v[2] *= k2; v[3] *= k3;
     }
     *(f32x4*)p = v;
@@ -84,8 +84,8 @@ __global__ void embed_finish_bwd_kernel(const float* __restrict__ dtok, void* __
     f32x4 v = *(const f32x4*)(dtok + row * D + d);
     if (drop.thr) {
       float k0, k1, k2, k3;
-      drop_pair(drop, (unsigned long long)row, (unsigned)(D >> 1), (unsigned)d, k0, k1);
-      drop_pair(drop, (unsigned long long)row, (unsigned)(D >> 1), (unsigned)d + 2, k2, k3);
+      drop_pair(drop, (unsigned long long)row, (unsigned)d, k0, k1);
+      drop_pair(drop, (unsigned long long)row, (unsigned)d + 2, k2, k3);
       v[0] *= k0; v[1] *= k1; v[2] *= k2; v[3] *= k3;
     }
     acc += v;
@@ -114,8 +114,8 @@ __global__ void dropout_bwd_cast_kernel(const float* __restrict__ dx, void* __re
     f32x4 v = *(const f32x4*)(dx + row * cols + c);
     if (drop.thr) {
       float k0, k1, k2, k3;
-      drop_pair(drop, (unsigned long long)row, (unsigned)(cols >> 1), (unsigned)c, k0, k1);
-      drop_pair(drop, (unsigned long long)row, (unsigned)(cols >> 1), (unsigned)c + 2, k2, k3);
+      drop_pair(drop, (unsigned long long)row, (unsigned)c, k0, k1);
+      drop_pair(drop, (unsigned long long)row, (unsigned)c + 2, k2, k3);
       v[0] *= k0; v[1] *= k1; v[2] *= k2; v[3] *= k3;
     }
     if (OUT_BF16) {

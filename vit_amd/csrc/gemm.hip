@@ -67,7 +67,7 @@ __device__ __forceinline__ void generic_epilogue(f32x4 (&acc)[4][4], const GemmA
     return;
   }
   char* Cb = p.C + (long)batch * p.c_bs * (p.c_dtype == VIT_BF16 ? 2 : 4);
-  const unsigned half_cols = (unsigned)(p.N >> 1);
+  const int N = p.N;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int m = m0 + wm * 64 + i * 16 + l15;
@@ -80,7 +80,7 @@ __device__ __forceinline__ void generic_epilogue(f32x4 (&acc)[4][4], const GemmA
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int n = n0 + wn * 64 + j * 16 + lg * 4;
-      if (n >= p.N) continue;
+      if (n >= N) continue;
       f32x4 v = acc[i][j] * p.alpha;
       if (p.bias) v += *(const f32x4*)(p.bias + n);
       if (p.act == VIT_ACT_GELU || p.act == VIT_ACT_GELU_GRAD) {
@@ -121,8 +121,8 @@ __device__ __forceinline__ void generic_epilogue(f32x4 (&acc)[4][4], const GemmA
       }
       if (p.drop.thr) {
         float k0, k1, k2, k3;
-        drop_pair(p.drop, (unsigned long long)orow, half_cols, (unsigned)n, k0, k1);
-        drop_pair(p.drop, (unsigned long long)orow, half_cols, (unsigned)n + 2, k2, k3);
+        drop_pair(p.drop, (unsigned long long)orow, (unsigned)n, k0, k1);
+        drop_pair(p.drop, (unsigned long long)orow, (unsigned)n + 2, k2, k3);
         v[0] *= k0; v[1] *= k1; v[2] *= k2; v[3] *= k3;
       }
       if (p.residual) v += *(const f32x4*)(p.residual + orow * p.ldres + n);

@@ -62,7 +62,6 @@ __device__ __forceinline__ void tile_epilogue(f32x4 (&acc)[WM][WN], char* scr, c
   const int l15 = lane & 15, lg = lane >> 4;
   constexpr int CPR = CW / 4;         // 16-byte chunks per scratch row
   constexpr int RPI = 64 / CPR;       // rows one wave-instruction covers on the way out
-  const unsigned half_cols = (unsigned)(p.N >> 1);
   float* slab = p.splits > 1 ? p.slab + (long)split * p.M * p.N : nullptr;
 #pragma unroll
   for (int i = 0; i < WM; ++i) {
@@ -122,8 +121,8 @@ __device__ __forceinline__ void tile_epilogue(f32x4 (&acc)[WM][WN], char* scr, c
         }
         if (p.drop.thr) {
           float k0, k1, k2, k3;
-          drop_pair(p.drop, (unsigned long long)orow, half_cols, (unsigned)n, k0, k1);
-          drop_pair(p.drop, (unsigned long long)orow, half_cols, (unsigned)n + 2, k2, k3);
+          drop_pair(p.drop, (unsigned long long)orow, (unsigned)n, k0, k1);
+          drop_pair(p.drop, (unsigned long long)orow, (unsigned)n + 2, k2, k3);
           v[0] *= k0; v[1] *= k1; v[2] *= k2; v[3] *= k3;
         }
         if (p.residual) v += *(const f32x4*)(p.residual + orow * p.ldres + n);
@@ -193,7 +192,6 @@ __device__ __forceinline__ void pp_epilogue(f32x4 (&acc)[NI][4], char* scr, cons
   const __amdgpu_buffer_rsrc_t ra_ = make_rsrc(p.aux_out ? (const void*)p.aux_out : (const void*)p.C, (unsigned long long)p.M * p.ldaux * 2);
 #define EPI_STORE_C(M_, PK) __builtin_amdgcn_raw_buffer_store_b128(PK, rc_, (unsigned)(((M_) * p.ldc + n) * 2), 0, 16)
 #define EPI_STORE_AUX(M_, PK) __builtin_amdgcn_raw_buffer_store_b128(PK, ra_, (unsigned)(((M_) * p.ldaux + n) * 2), 0, 16)
-  const unsigned half_cols = (unsigned)(p.N >> 1);
   f32x4 bv0 = (f32x4){0.f, 0.f, 0.f, 0.f}, bv1 = bv0;
   if ((FAST == 3 || FAST == 4 || FAST == 8) && p.bias) {
     bv0 = *(const f32x4*)(p.bias + n);
@@ -323,7 +321,7 @@ __device__ __forceinline__ void pp_epilogue(f32x4 (&acc)[NI][4], char* scr, cons
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           float k0, k1;
-          drop_pair(p.drop, (unsigned long long)m, half_cols, (unsigned)n + 2 * r, k0, k1);
+          drop_pair(p.drop, (unsigned long long)m, (unsigned)n + 2 * r, k0, k1);
           o[2 * r] *= k0;
           o[2 * r + 1] *= k1;
         }

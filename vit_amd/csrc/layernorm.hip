@@ -152,8 +152,8 @@ __global__ __launch_bounds__(1024) void ln_bwd_kernel(const void* __restrict__ d
         if (FUSE) {
           if (drop.thr) {
             float k0, k1, k2, k3;
-            drop_pair(drop, (unsigned long long)row, (unsigned)(D >> 1), (unsigned)(4 * c), k0, k1);
-            drop_pair(drop, (unsigned long long)row, (unsigned)(D >> 1), (unsigned)(4 * c) + 2, k2, k3);
+            drop_pair(drop, (unsigned long long)row, (unsigned)(4 * c), k0, k1);
+            drop_pair(drop, (unsigned long long)row, (unsigned)(4 * c) + 2, k2, k3);
             o[0] *= k0; o[1] *= k1; o[2] *= k2; o[3] *= k3;
           }
           if (FUSE == 1) {

@@ -212,8 +212,8 @@ def attention_fwd(qkv, B: int, H: int, T: int, dh: int, scale: float, dropout: D
     p, seed, site = dropout
     if ctx_lo is not None:
         _chk(ctx_lo, ctx.dtype, "attention_fwd ctx_lo")
-    check(h.lib.vit_attention_fwd_lo(h.h, qkv.data_ptr(), ctx.data_ptr(), _ptr(ctx_lo), lse.data_ptr(), _DT[qkv.dtype], B, H,
-                                     T, dh, scale, p, seed, site, _stream(qkv)), "vit_attention_fwd")
+    check(h.lib.vit_attention_fwd(h.h, qkv.data_ptr(), ctx.data_ptr(), _ptr(ctx_lo), lse.data_ptr(), _DT[qkv.dtype], B, H,
+                                  T, dh, scale, p, seed, site, _stream(qkv)), "vit_attention_fwd")
     return ctx, lse
 
 
@@ -228,10 +228,10 @@ def attention_bwd(qkv, ctx, dctx, lse, B: int, H: int, T: int, dh: int, scale: f
     p, seed, site = dropout
     if colsum_out is not None:
         _chk(colsum_out, torch.float32, "attention_bwd colsum_out")
-        h.ensure_workspace(B * 16 * 3 * H * dh * 4)
-    check(h.lib.vit_attention_bwd_lo(h.h, qkv.data_ptr(), ctx.data_ptr(), _ptr(ctx_lo), dctx.data_ptr(), lse.data_ptr(),
-                                     delta.data_ptr(), dqkv.data_ptr(), _DT[qkv.dtype], B, H, T, dh, scale, p, seed, site,
-                                     _ptr(colsum_out), _stream(qkv)), "vit_attention_bwd")
+        h.ensure_workspace(B * 16 * 3 * H * dh * 4)  # the library's true row count is AttnPlan::csum_rows (B * 21 at T = 577)
+    check(h.lib.vit_attention_bwd(h.h, qkv.data_ptr(), ctx.data_ptr(), _ptr(ctx_lo), dctx.data_ptr(), lse.data_ptr(),
+                                  delta.data_ptr(), dqkv.data_ptr(), _DT[qkv.dtype], B, H, T, dh, scale, p, seed, site,
+                                  _ptr(colsum_out), _stream(qkv)), "vit_attention_bwd")
     return dqkv
 
 
