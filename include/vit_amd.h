@@ -130,6 +130,11 @@ typedef struct vit_gemm_desc {
    * the table per row.  dropout_p must be 0 with rope (the reference rotates before any dropout). */
   const float* rope_cos; const float* rope_sin;
   int rope_T, rope_dh, rope_cols;
+  /* Row stride of the dropout key: 0 / 1 = the mask of element (out_row, n) is keyed by out_row (above); s > 1 = by out_row * s.
+   * For a product over a strided subset of a larger problem's rows (A read in place with lda = s * K, compact C: the CLS rows of
+   * the last encoder layer, s = T): the mask of compact row r is then bit for bit the one the full problem draws for its row
+   * r * s.  Such a launch runs the generic epilogue. */
+  int drop_row_stride;
 } vit_gemm_desc;
 int vit_gemm(vit_handle h, const vit_gemm_desc* d, vit_stream stream);
 /* Symbol (as rocprofv3 prints it, without the "void vit::" prefix and argument list) of the kernel the calling thread's
@@ -147,6 +152,19 @@ int vit_linear_bwd_dx(vit_handle h, const void* dy, const void* W, void* dx, int
 int vit_linear_bwd_dw(vit_handle h, const void* dy, const void* x, float* dW, int M, int N, int K, int accumulate,
                       vit_stream stream);
 
+/* Weight gradient and column sums over a strided subset of rows (the CLS rows of the last encoder layer: row_stride = T,
+ * full_rows = the padded B*T of the full tensors).  dy: [rows, N] (ld = ldy), x: [rows, K] (ld = ldx), both `dtype`; compact
+ * row b stands for row b * row_stride of full tensors whose other rows are zero (dy) / irrelevant (x).
+ * dW[N, K] (f32, dense) = sum_b dy[b]^T x[b].  Where the product over the full tensors would run the ping-pong core with
+ * split-K, the B terms are summed in that product's order (K slices, rows within a slice, then the slices), so with
+ * row_stride >= 64 the result is bit for bit the full product's (zero terms leave an f32 sum unchanged); any other shape runs
+ * the compact product through vit_gemm.  vit_colsum_rows: out[cols] = column sums of a ([rows, cols], ld = lda), likewise in
+ * the order of the column sums that ride in the ping-pong epilogue of the product that would write the full tensor. */
+int vit_linear_bwd_dw_rows(vit_handle h, const void* dy, int64_t ldy, const void* x, int64_t ldx, int dtype, float* dW,
+                           int rows, int N, int K, int64_t row_stride, int64_t full_rows, vit_stream stream);
+int vit_colsum_rows(vit_handle h, const void* a, int a_dtype, int64_t lda, float* out, int rows, int cols, int64_t row_stride,
+                    int64_t full_rows, vit_stream stream);
+
 /* ------------------------------------------------------------------------------------------- LayerNorm
  * HF nn.LayerNorm(hidden, eps=layer_norm_eps=1e-12) (builder.py:250): layernorm_before/after and vit.layernorm.
  * x: f32 [rows, D] (the residual stream is kept in fp32); y: y_dtype [rows, D]; mean/rstd: f32 [rows] (saved for bwd).
@@ -160,6 +178,12 @@ int vit_layernorm_fwd(vit_handle h, const float* x, const float* gamma, const fl
 int vit_layernorm_fwd_residual(vit_handle h, const float* x, const void* delta, int delta_dtype, float* xsum,
                                const float* gamma, const float* beta, void* y, int y_dtype, float* mean, float* rstd,
                                int rows, int D, float eps, vit_stream stream);
+/* vit_layernorm_fwd_residual over a strided subset of the stream's rows: row r of x is row r * x_row_stride of the tensor x
+ * points into (x_row_stride >= 1); delta, xsum, y, mean, rstd are compact [rows, .].  The last encoder layer's LayerNorm-after
+ * when only the CLS rows are consumed (x_row_stride = T): the head reads last_hidden[:, 0, :] alone (specvit.py:78-81). */
+int vit_layernorm_fwd_residual_rows(vit_handle h, const float* x, int64_t x_row_stride, const void* delta, int delta_dtype,
+                                    float* xsum, const float* gamma, const float* beta, void* y, int y_dtype, float* mean,
+                                    float* rstd, int rows, int D, float eps, vit_stream stream);
 /* dx[rows,D] (f32) = LN'(dy) (+ dres if not NULL: the residual branch's gradient); dgamma/dbeta (f32 [D]) are
  * reduced deterministically through the workspace; accumulate!=0 adds into them. dy: dy_dtype [rows, D]. */
 int vit_layernorm_bwd(vit_handle h, const void* dy, int dy_dtype, const float* x, const float* gamma,
@@ -173,6 +197,19 @@ int vit_layernorm_bwd_fused(vit_handle h, const void* dy, int dy_dtype, const fl
                             const float* mean, const float* rstd, const float* dres, float* dx, float* dgamma,
                             float* dbeta, int rows, int D, void* dyn, int dyn_dtype, float* dbias, float dropout_p,
                             uint64_t seed, uint64_t site, vit_stream stream);
+
+/* vit_layernorm_bwd (dyn == NULL: dyn_dtype, dbias and the dropout arguments are ignored) / vit_layernorm_bwd_fused for the
+ * two ends of a compact run of rows.  `rows` is always the row count of the FULL tensor.
+ *   row_stride s > 1: of those rows only the rows r with r % s == 0 exist; dy, x, mean, rstd, dx, dyn and dres hold them
+ *     compactly at r / s (ceil(rows / s) rows).  The dropout mask of dyn is keyed by r, and dgamma / dbeta / dbias are summed
+ *     in the order the pass over the full tensor (its other rows exact zeros) sums them: bit for bit its results.
+ *   dres_row_stride s > 0 (with row_stride 1): dres alone is compact, [ceil(rows / s), D]; row j of it is the residual
+ *     gradient of row j * s, every other row has none (nothing is read for it).  This is where the gradient of the CLS rows
+ *     re-enters the full token stream, without a zero-filled [rows, D] tensor in between. */
+int vit_layernorm_bwd_rows(vit_handle h, const void* dy, int dy_dtype, const float* x, const float* gamma, const float* mean,
+                           const float* rstd, const float* dres, int64_t dres_row_stride, float* dx, float* dgamma,
+                           float* dbeta, int rows, int D, void* dyn, int dyn_dtype, float* dbias, float dropout_p,
+                           uint64_t seed, uint64_t site, int64_t row_stride, vit_stream stream);
 
 /* ------------------------------------------------------------------------------------------- Attention
  * softmax(Q K^T * scale) -> dropout -> * V, per (batch, head); flash-style (scores never reach HBM).

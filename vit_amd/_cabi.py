@@ -44,6 +44,7 @@ class GemmDesc(C.Structure):
         ("colsum_out", C.c_void_p),
         ("rope_cos", C.c_void_p), ("rope_sin", C.c_void_p),
         ("rope_T", C.c_int), ("rope_dh", C.c_int), ("rope_cols", C.c_int),
+        ("drop_row_stride", C.c_int),
     ]
 
 
@@ -68,6 +69,10 @@ _PROTOS = {
     "vit_linear_bwd_dw": [_P, _P, _P, _P, _I, _I, _I, _I, _P],
     "vit_layernorm_fwd": [_P, _P, _P, _P, _P, _I, _P, _P, _I, _I, _F, _P],
     "vit_layernorm_fwd_residual": [_P, _P, _P, _I, _P, _P, _P, _P, _I, _P, _P, _I, _I, _F, _P],
+    "vit_linear_bwd_dw_rows": [_P, _P, _I64, _P, _I64, _I, _P, _I, _I, _I, _I64, _I64, _P],
+    "vit_colsum_rows": [_P, _P, _I, _I64, _P, _I, _I, _I64, _I64, _P],
+    "vit_layernorm_fwd_residual_rows": [_P, _P, _I64, _P, _I, _P, _P, _P, _P, _I, _P, _P, _I, _I, _F, _P],
+    "vit_layernorm_bwd_rows": [_P, _P, _I, _P, _P, _P, _P, _P, _I64, _P, _P, _P, _I, _I, _P, _I, _P, _F, _U64, _U64, _I64, _P],
     "vit_layernorm_bwd": [_P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P],
     "vit_layernorm_bwd_fused": [_P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _I, _P, _F, _U64, _U64, _P],
     "vit_attention_fwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _F, _U64, _U64, _P],

@@ -43,6 +43,7 @@ struct GemmArgs {
   int act, c_dtype;
   DropCfg drop;
   int rpb, orb, roff;
+  int drs;  // dropout key row = out_row * drs (vit_gemm_desc::drop_row_stride; 1 = the row itself)
 };
 
 __device__ __forceinline__ int tr_swz(int k) { return ((k & 3) | (((k >> 3) & 1) << 2)) << 2; }
@@ -121,8 +122,9 @@ __device__ __forceinline__ void generic_epilogue(f32x4 (&acc)[4][4], const GemmA
       }
       if (p.drop.thr) {
         float k0, k1, k2, k3;
-        drop_pair(p.drop, (unsigned long long)orow, (unsigned)n, k0, k1);
-        drop_pair(p.drop, (unsigned long long)orow, (unsigned)n + 2, k2, k3);
+        const unsigned long long krow = (unsigned long long)orow * (unsigned)p.drs;
+        drop_pair(p.drop, krow, (unsigned)n, k0, k1);
+        drop_pair(p.drop, krow, (unsigned)n + 2, k2, k3);
         v[0] *= k0; v[1] *= k1; v[2] *= k2; v[3] *= k3;
       }
       if (p.residual) v += *(const f32x4*)(p.residual + orow * p.ldres + n);
@@ -527,6 +529,7 @@ static int gemm_launch_core(vit_handle h, const vit_gemm_desc* d, hipStream_t st
   if (d->act == VIT_ACT_GELU_GRAD) VIT_CHECK(d->aux_out, VIT_ERR_ARG, "vit_gemm: ACT_GELU_GRAD needs aux_out");
   if (d->aux_out) VIT_CHECK((d->ldaux % 4) == 0 && d->ldaux >= d->N, VIT_ERR_ARG, "vit_gemm: bad ldaux");
   VIT_CHECK(d->dropout_p >= 0.f && d->dropout_p < 1.f, VIT_ERR_ARG, "vit_gemm: dropout_p out of [0,1)");
+  VIT_CHECK(d->drop_row_stride >= 0, VIT_ERR_ARG, "vit_gemm: drop_row_stride=%d", d->drop_row_stride);
 
   if (d->dropout_p > 0.f) VIT_CHECK((d->N % 2) == 0, VIT_ERR_ARG, "vit_gemm: dropout needs an even N");
   if (!f32in) {
@@ -577,6 +580,7 @@ static int gemm_launch_core(vit_handle h, const vit_gemm_desc* d, hipStream_t st
   a.drop = make_drop_h(h, d->dropout_p, d->seed, d->site);
   if (a.drop.thr) VIT_CHECK((d->N % 2) == 0, VIT_ERR_ARG, "vit_gemm: dropout needs an even N");
   a.rpb = d->rows_per_batch; a.orb = d->out_batch_rows; a.roff = d->out_row_offset;
+  a.drs = (a.drop.thr && d->drop_row_stride > 1) ? d->drop_row_stride : 1;
 
   dim3 grid(a.tiles_m * a.tiles_n, splits), block(NTHR);
   const int v = d->a_trans * 2 + d->b_trans;

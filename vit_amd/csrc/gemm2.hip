@@ -46,6 +46,7 @@ struct Gemm2Args {
   int act, c_dtype;
   DropCfg drop;
   int rpb, orb, roff;
+  int drs;  // dropout key row = out_row * drs (vit_gemm_desc::drop_row_stride; 1 = the row itself)
   int lin_split;  // ping-pong kernel, split-K with one tile per workgroup: 1-D grid of tiles x splits, XCD-contiguous
   float* colsum_part;  // ping-pong kernel, bf16 epilogues: [tiles_m * 2][N] per-wave-row column sums of C, or NULL
   int grp2;  // ping-pong kernel: XCDs 0-3 walk the lower half of the N-tiles, XCDs 4-7 the upper half (see tile_coords)
@@ -121,8 +122,9 @@ __device__ __forceinline__ void tile_epilogue(f32x4 (&acc)[WM][WN], char* scr, c
         }
         if (p.drop.thr) {
           float k0, k1, k2, k3;
-          drop_pair(p.drop, (unsigned long long)orow, (unsigned)n, k0, k1);
-          drop_pair(p.drop, (unsigned long long)orow, (unsigned)n + 2, k2, k3);
+          const unsigned long long krow = (unsigned long long)orow * (unsigned)p.drs;
+          drop_pair(p.drop, krow, (unsigned)n, k0, k1);
+          drop_pair(p.drop, krow, (unsigned)n + 2, k2, k3);
           v[0] *= k0; v[1] *= k1; v[2] *= k2; v[3] *= k3;
         }
         if (p.residual) v += *(const f32x4*)(p.residual + orow * p.ldres + n);
@@ -736,11 +738,33 @@ static int launch_stag_cfg(const Gemm2Args& a, int at, int bt, int epi, dim3 gri
 extern thread_local int g_colsum_fused, g_rope_fused;  // gemm.hip
 int g_gemm2_mode = 1;  // vit_set_option("gemm_core"): 0 = generic 128x128 core only, else the ping-pong kernel where eligible
 
+// K slices of a ping-pong product of `ntile` tiles: how many, and rows per slice (split_k as in vit_gemm_desc)
+static void pp_split_plan(int slots, int ntile, int K, int split_k, int* splits_out, int* kps_out) {
+  const int ktiles = K / 64;
+  int splits = split_k;
+  if (splits < 0) {
+    splits = 1;
+    if (ntile < slots) splits = std::min(std::max(1, slots / ntile), std::max(1, ktiles / 8));
+  }
+  if (splits < 1) splits = 1;
+  if (splits > ktiles) splits = ktiles;
+  const int kps = cdiv(ktiles, splits) * 64;
+  *splits_out = cdiv(K, kps);
+  *kps_out = kps;
+}
+
+// Does a bf16 product of this shape run the ping-pong core?  The ONE statement of that rule: gemm2_try_launch asks it, and so
+// does vit_linear_bwd_dw_rows, which must know whether the full-size product it stands in for would have.
+static bool pp_shape_ok(long M, long N, long K, long lda, long ldb) {
+  if (g_gemm2_mode == 0) return false;
+  if (M % 256 || N % 256 || K % 64) return false;  // other shapes stay on the register-staged 128x128 core
+  if (lda * 256 >= (1L << 30) || ldb * 256 >= (1L << 30)) return false;  // int offsets inside a tile
+  return true;
+}
+
 // returns 1 if handled (rc in *rc), 0 if the shape is not eligible
 int gemm2_try_launch(vit_handle h, const vit_gemm_desc* d, hipStream_t st, int* rc) {
-  if (g_gemm2_mode == 0) return 0;
-  if (d->M % 256 || d->N % 256 || d->K % 64) return 0;  // other shapes stay on the register-staged 128x128 core
-  if (d->lda * 256 >= (1L << 30) || d->ldb * 256 >= (1L << 30)) return 0;  // int offsets inside a tile
+  if (!pp_shape_ok(d->M, d->N, d->K, d->lda, d->ldb)) return 0;
   int epi = 0;
   if (d->act == VIT_ACT_GELU || d->act == VIT_ACT_GELU_GRAD) {
     if (d->a_trans || d->b_trans) return 0;
@@ -758,15 +782,8 @@ int gemm2_try_launch(vit_handle h, const vit_gemm_desc* d, hipStream_t st, int* 
   a.tiles_m = d->M / 256; a.tiles_n = d->N / 256;
   const int ntile = a.tiles_m * a.tiles_n;
   const int ktiles = d->K / 64;
-  int splits = d->split_k;
-  if (splits < 0) {
-    splits = 1;
-    if (ntile < slots) splits = std::min(std::max(1, slots / ntile), std::max(1, ktiles / 8));
-  }
-  if (splits < 1) splits = 1;
-  if (splits > ktiles) splits = ktiles;
-  const int kps = cdiv(ktiles, splits) * 64;
-  splits = cdiv(d->K, kps);
+  int splits, kps;
+  pp_split_plan(slots, ntile, d->K, d->split_k, &splits, &kps);
   a.splits = splits; a.k_per_split = kps;
   a.slab = nullptr;
   if (splits > 1) {
@@ -795,6 +812,7 @@ int gemm2_try_launch(vit_handle h, const vit_gemm_desc* d, hipStream_t st, int* 
   a.act = d->act; a.c_dtype = d->c_dtype;
   a.drop = make_drop_h(h, d->dropout_p, d->seed, d->site);
   a.rpb = d->rows_per_batch; a.orb = d->out_batch_rows; a.roff = d->out_row_offset;
+  a.drs = (a.drop.thr && d->drop_row_stride > 1) ? d->drop_row_stride : 1;
 
   dim3 grid(a.nblk, splits);
   a.lin_split = 0;
@@ -805,7 +823,7 @@ int gemm2_try_launch(vit_handle h, const vit_gemm_desc* d, hipStream_t st, int* 
   }
   // the specialised epilogue when the descriptor is one of the five hot kinds
   int epi5 = epi;
-  const bool plain = !a.residual && a.rpb == 0 && d->alpha == 1.0f;
+  const bool plain = !a.residual && a.rpb == 0 && a.drs == 1 && d->alpha == 1.0f;
   if (epi == 1 && plain && a.bias && d->c_dtype == VIT_BF16 && !a.drop.thr && splits == 1) epi5 = 4;
   else if (epi == 2 && plain && !a.bias && d->c_dtype == VIT_BF16 && !a.drop.thr && splits == 1) epi5 = 5;
   else if (epi == 0 && plain && d->c_dtype == VIT_BF16 && !d->a_trans && !d->b_trans && splits == 1) epi5 = 3;
@@ -864,4 +882,170 @@ int gemm2_try_launch(vit_handle h, const vit_gemm_desc* d, hipStream_t st, int* 
   return 1;
 }
 
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// Sums over the rows r = b * s of a tensor whose other rows are zero, given compactly (row b), evaluated in the order in which
+// the ping-pong kernels sum the full tensor.  Why: the last encoder layer's CLS tail (ViTEngine.cls_tail) replaces K = B * T
+// weight-gradient products and M = B * T column sums whose other rows are exact zeros.  A zero term leaves an f32 sum
+// unchanged, so the full result IS the sum of the B terms in the full kernel's order -- per K slice of the split-K plan row by
+// row (a 64-row K-tile holds at most one such row when s >= 64, so every MFMA adds one exact bf16 x bf16 product to its
+// accumulator), the slices then in splitk_reduce_kernel's order; per 128-row wave block of the
+// epilogue's column sums, the blocks then in reduce_partials_kernel's order.  Walking that order over the B rows keeps the
+// gradients bit for bit those of the full path (and a training run the same run whichever path computes it), at 1 / T of the
+// work.  With s < 64 several rows share an MFMA and the result is the same sum in another rounding order.
+__global__ __launch_bounds__(256) void dw_rows_kernel(const short* __restrict__ dy, long ldy, const short* __restrict__ x,
+                                                      long ldx, float* __restrict__ dW, long ldw, int B, int s, int kps,
+                                                      int splits) {
+  // 64 x 64 outputs per block, 32 x 32 (2 x 2 MFMA tiles) per wave.  One v_mfma_f32_16x16x32_bf16 per row and tile with the
+  // row in k slot 0 and zeros in the other 31: the very accumulate step the full product takes for that row (the MFMA's
+  // rounding of accumulator + product is not IEEE's in every case, so an fma would be off by an ulp once in ~20 000 elements).
+  constexpr int R = 128;  // rows staged at a time (32 KiB): the row loop below then runs from the LDS without a global wait
+  __shared__ __attribute__((aligned(16))) short ys[R][64];
+  __shared__ __attribute__((aligned(16))) short xs[R][64];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, l15 = lane & 15, lg = lane >> 4;
+  const int wn = (wave >> 1) * 32, wk = (wave & 1) * 32;
+  const int n0 = blockIdx.x * 64, k0 = blockIdx.y * 64;
+  f32x4 acc[2][2], tot[2][2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) acc[i][j] = tot[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  int sp = 0;  // current K slice: rows b with b * s < (sp + 1) * kps
+  int bend = (int)min((long)B, ((long)(sp + 1) * kps + s - 1) / s);
+  auto flush = [&]() {  // slice sp is complete: slab 0 starts the total, the others are added to it (splitk_reduce_kernel)
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        tot[i][j] = sp == 0 ? acc[i][j] : tot[i][j] + acc[i][j];
+        acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+      }
+    ++sp;
+    bend = sp >= splits - 1 ? B : (int)min((long)B, ((long)(sp + 1) * kps + s - 1) / s);
+  };
+  if (splits == 1) bend = B;
+  const int lr = t >> 3, lc = (t & 7) * 8;  // staging: thread loads 8 bf16 of rows lr, lr + 32, .. of each operand
+  for (int b0 = 0; b0 < B; b0 += R) {
+    __syncthreads();
+    {
+      u32x4 vy[R / 32], vx[R / 32];
+#pragma unroll
+      for (int q = 0; q < R / 32; ++q) {
+        const int b = b0 + lr + 32 * q;
+        vy[q] = vx[q] = (u32x4){0u, 0u, 0u, 0u};
+        if (b < B) {
+          vy[q] = *(const u32x4*)(dy + (long)b * ldy + n0 + lc);
+          vx[q] = *(const u32x4*)(x + (long)b * ldx + k0 + lc);
+        }
+      }
+#pragma unroll
+      for (int q = 0; q < R / 32; ++q) {
+        *(u32x4*)&ys[lr + 32 * q][lc] = vy[q];
+        *(u32x4*)&xs[lr + 32 * q][lc] = vx[q];
+      }
+    }
+    __syncthreads();
+    const int nb = min(R, B - b0);
+    int bb = 0;
+    while (bb < nb) {
+      while (b0 + bb >= bend) flush();  // (the last slice's end is B, so this stops)
+      const int seg = min(nb, bend - b0);  // the staged rows of slice sp: a loop without slice tests
+#pragma unroll 4
+      for (; bb < seg; ++bb) {
+        bf16x8 yf[2], xf[2];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+          yf[i] = (bf16x8){0, 0, 0, 0, 0, 0, 0, 0};
+          xf[i] = (bf16x8){0, 0, 0, 0, 0, 0, 0, 0};
+          if (lg == 0) {
+            yf[i][0] = ys[bb][wn + i * 16 + l15];
+            xf[i][0] = xs[bb][wk + i * 16 + l15];
+          }
+        }
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+          for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(yf[i], xf[j], acc[i][j], 0, 0, 0);
+      }
+    }
+  }
+  while (sp < splits) flush();
+  // D fragment: lane holds rows 4 * lg + r of the first operand's index, column l15 of the second's
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        dW[(long)(n0 + wn + i * 16 + 4 * lg + r) * ldw + k0 + wk + j * 16 + l15] = tot[i][j][r];
+}
+
+// part[p][n] = sum of the compact rows that fall into the 128-row block p of the full tensor (the epilogue's wave rows)
+__global__ void colsum_rows_part_kernel(const short* __restrict__ a, long lda, float* __restrict__ part, int nblk, int N,
+                                        int B, int s) {
+  const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
+  if (i >= (long)nblk * N) return;
+  const int p = (int)(i / N), n = (int)(i - (long)p * N);
+  const int b0 = (int)(((long)p * 128 + s - 1) / s), b1 = (int)min((long)B, ((long)(p + 1) * 128 + s - 1) / s);
+  float v = 0.f;
+  for (int b = b0; b < b1; ++b) v += bf2f(a[(long)b * lda + n]);
+  part[i] = v;
+}
+
+int gemm_launch(vit_handle h, const vit_gemm_desc* d, hipStream_t st);  // gemm.hip
+
 }  // namespace vit
+
+extern "C" {
+
+int vit_linear_bwd_dw_rows(vit_handle h, const void* dy, int64_t ldy, const void* x, int64_t ldx, int dtype, float* dW,
+                           int rows, int N, int K, int64_t row_stride, int64_t full_rows, vit_stream stream) {
+  using namespace vit;
+  VIT_CHECK(h && dy && x && dW, VIT_ERR_ARG, "vit_linear_bwd_dw_rows: null pointer");
+  VIT_CHECK(rows > 0 && N > 0 && K > 0 && row_stride >= 1 && full_rows >= (int64_t)(rows - 1) * row_stride + 1 &&
+                full_rows <= 0x7FFFFFFF && ldy >= N && ldx >= K,
+            VIT_ERR_ARG, "vit_linear_bwd_dw_rows: rows=%d N=%d K=%d row_stride=%lld full_rows=%lld", rows, N, K,
+            (long long)row_stride, (long long)full_rows);
+  hipStream_t st = (hipStream_t)stream;
+  // the full product dW[N, K] = dY[full_rows, N]^T X[full_rows, K] (both operands transposed: ld = N and K) on the ping-pong
+  // core is what the order below restates; the kernel itself needs 16-byte rows
+  if (dtype == VIT_BF16 && pp_shape_ok(N, K, full_rows, N, K) && (ldy % 8) == 0 && (ldx % 8) == 0 &&
+      ((uintptr_t)dy % 16) == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)dW % 16) == 0) {
+    int splits, kps;
+    pp_split_plan(ctx_num_cus(h), (N / 256) * (K / 256), (int)full_rows, -1, &splits, &kps);
+    hipLaunchKernelGGL(dw_rows_kernel, dim3(N / 64, K / 64), dim3(256), 0, st, (const short*)dy, (long)ldy, (const short*)x,
+                       (long)ldx, dW, (long)K, rows, (int)row_stride, kps, splits);
+    VIT_LAUNCH_CHECK();
+    return VIT_OK;
+  }
+  vit_gemm_desc d = {};  // any other shape: the compact product (the same sum, the GEMM core's own order)
+  d.M = N; d.N = K; d.K = rows; d.ab_dtype = dtype; d.a_trans = 1; d.b_trans = 1;
+  d.A = dy; d.lda = ldy; d.B = x; d.ldb = ldx; d.C = dW; d.ldc = K; d.c_dtype = VIT_F32; d.alpha = 1.f; d.split_k = 1;
+  return gemm_launch(h, &d, st);
+}
+
+int vit_colsum_rows(vit_handle h, const void* a, int a_dtype, int64_t lda, float* out, int rows, int cols, int64_t row_stride,
+                    int64_t full_rows, vit_stream stream) {
+  using namespace vit;
+  VIT_CHECK(h && a && out, VIT_ERR_ARG, "vit_colsum_rows: null pointer");
+  VIT_CHECK(rows > 0 && cols > 0 && lda >= cols && row_stride >= 1 && full_rows >= (int64_t)(rows - 1) * row_stride + 1 &&
+                full_rows <= 0x7FFFFFFF,
+            VIT_ERR_ARG, "vit_colsum_rows: rows=%d cols=%d row_stride=%lld full_rows=%lld", rows, cols, (long long)row_stride,
+            (long long)full_rows);
+  hipStream_t st = (hipStream_t)stream;
+  // the full tensor's column sums ride in the ping-pong epilogue iff the product that writes it is tile-aligned
+  if (a_dtype == VIT_BF16 && pp_shape_ok(full_rows, cols, 64, 64, 64)) {  // K of that product: a multiple of 64 at these widths
+    const int nblk = (int)(full_rows / 128);
+    size_t wsb = 0;
+    float* part = (float*)ctx_workspace(h, &wsb);
+    if (part && wsb >= (size_t)nblk * cols * sizeof(float)) {
+      hipLaunchKernelGGL(colsum_rows_part_kernel, dim3((unsigned)cdiv((long)nblk * cols, 256)), dim3(256), 0, st,
+                         (const short*)a, (long)lda, part, nblk, cols, rows, (int)row_stride);
+      VIT_LAUNCH_CHECK();
+      return launch_reduce_partials(part, nblk, cols, out, cols, out, 0, st);
+    }
+  }
+  return vit_colsum(h, a, a_dtype, lda, out, rows, cols, 0, stream);
+}
+
+}  // extern "C"

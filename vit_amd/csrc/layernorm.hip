@@ -18,14 +18,14 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x
                                                      const float* __restrict__ beta, void* __restrict__ y,
                                                      float* __restrict__ mean, float* __restrict__ rstd, int rows,
                                                      int D, float eps, const void* __restrict__ delta,
-                                                     float* __restrict__ xsum) {
+                                                     float* __restrict__ xsum, long x_ld) {
   const int lane = threadIdx.x & 63;
   const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const int nwaves = (gridDim.x * blockDim.x) >> 6;
   const int nvec = D >> 2;
   const float invD = 1.0f / (float)D;
   for (int row = wave; row < rows; row += nwaves) {
-    const float* xr = x + (long)row * D;
+    const float* xr = x + (long)row * x_ld;  // x_ld = D, or a multiple of it: a strided subset of the stream's rows
     f32x4 v[NV];
     float s = 0.f;
 #pragma unroll
@@ -76,6 +76,17 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x
   }
 }
 
+// Row maps of the backward at the two ends of a compact run of rows (vit_layernorm_bwd_rows); {0, 0} = none.
+// compact_stride s > 0: `rows` counts the rows of the FULL tensor, of which only the rows r with r % s == 0 exist; dy, x, mean,
+// rstd, dx, dyn (and dres, unless dres_stride says otherwise) hold them compactly at r / s.  The kernel walks the full row
+// space with the full tensor's grid and skips the absent rows, so every wave meets its rows in the order it would meet them
+// in the full tensor (whose other rows contribute exact zeros) and the partial sums -- dgamma, dbeta, dbias -- come out bit for
+// bit the full pass's; the dropout key row is r itself.
+struct RowMap {
+  int compact_stride;
+  int dres_stride;  // 0 = dres is laid out like dx; s > 0 = dres is compact while dx is full: row j of it belongs to row j * s
+};
+
 // backward: dx = rstd * (g - mean(g) - xhat * mean(g*xhat)) + dres,  g = dy*gamma, xhat = (x-mean)*rstd
 // per-wave running sums of dy*xhat (dgamma) and dy (dbeta) over the rows the wave visits; block-combined through LDS
 // and written as one partial row per block: part[blk][0][D] (dgamma), part[blk][1][D] (dbeta).
@@ -88,12 +99,14 @@ __global__ __launch_bounds__(1024) void ln_bwd_kernel(const void* __restrict__ d
                                                      const float* __restrict__ gamma, const float* __restrict__ mean,
                                                      const float* __restrict__ rstd, const float* __restrict__ dres,
                                                      float* __restrict__ dx, float* __restrict__ part, int rows, int D,
-                                                     void* __restrict__ dyn, DropCfg drop) {
+                                                     void* __restrict__ dyn, DropCfg drop, RowMap rm) {
   resolve_drop(drop);
   constexpr int NP = FUSE ? 3 : 2;
   extern __shared__ __attribute__((aligned(16))) float red[];  // [4 waves][NP][D], used by four waves at a time
   const int lane = threadIdx.x & 63, wib = threadIdx.x >> 6;
-  const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  // the same in every lane of a wave, and said so: the row index and what is derived from it (row base offsets, the row's
+  // statistics, the compact-dres row, the dropout key row) stay in scalar registers
+  const int wave = __builtin_amdgcn_readfirstlane((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
   const int nwaves = (gridDim.x * blockDim.x) >> 6;
   const int nvec = D >> 2;
   const float invD = 1.0f / (float)D;
@@ -116,7 +129,18 @@ __global__ __launch_bounds__(1024) void ln_bwd_kernel(const void* __restrict__ d
     if (FUSE) dbias[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
   }
   for (int row = wave; row < rows; row += nwaves) {
-    const float mu = mean[row], rs = rstd[row];
+    int idx = row;  // where the row lives in the tensors
+    if (rm.compact_stride) {
+      idx = row / rm.compact_stride;
+      if (idx * rm.compact_stride != row) continue;
+    }
+    const float mu = mean[idx], rs = rstd[idx];
+    // the residual gradient of this row: laid out like dx, or compact and present for every dres_stride-th row only
+    const float* dr = dres ? dres + (long)idx * D : nullptr;
+    if (rm.dres_stride) {
+      const int j = row / rm.dres_stride;
+      dr = (dres && j * rm.dres_stride == row) ? dres + (long)j * D : nullptr;
+    }
     f32x4 xh[NV], g[NV];
     float s1 = 0.f, s2 = 0.f;
 #pragma unroll
@@ -125,12 +149,12 @@ __global__ __launch_bounds__(1024) void ln_bwd_kernel(const void* __restrict__ d
       if (c < nvec) {
         f32x4 d;
         if (DY_BF16) {
-          bf16x4 t = *(const bf16x4*)((const short*)dy + (long)row * D + 4 * c);
+          bf16x4 t = *(const bf16x4*)((const short*)dy + (long)idx * D + 4 * c);
           d = (f32x4){bf2f(t[0]), bf2f(t[1]), bf2f(t[2]), bf2f(t[3])};
         } else {
-          d = *(const f32x4*)((const float*)dy + (long)row * D + 4 * c);
+          d = *(const f32x4*)((const float*)dy + (long)idx * D + 4 * c);
         }
-        xh[i] = (*(const f32x4*)(x + (long)row * D + 4 * c) - mu) * rs;
+        xh[i] = (*(const f32x4*)(x + (long)idx * D + 4 * c) - mu) * rs;
         g[i] = d * (GAM_LDS ? *(const f32x4*)(gam_s + 4 * c) : gam[GAM_LDS ? 0 : i]);
         dg[i] += d * xh[i];
         db[i] += d;
@@ -147,8 +171,8 @@ __global__ __launch_bounds__(1024) void ln_bwd_kernel(const void* __restrict__ d
       const int c = lane + 64 * i;
       if (c < nvec) {
         f32x4 o = (g[i] - c1 - xh[i] * c2) * rs;
-        if (dres) o += *(const f32x4*)(dres + (long)row * D + 4 * c);
-        *(f32x4*)(dx + (long)row * D + 4 * c) = o;
+        if (dr) o += *(const f32x4*)(dr + 4 * c);
+        *(f32x4*)(dx + (long)idx * D + 4 * c) = o;
         if (FUSE) {
           if (drop.thr) {
             float k0, k1, k2, k3;
@@ -158,12 +182,12 @@ __global__ __launch_bounds__(1024) void ln_bwd_kernel(const void* __restrict__ d
           }
           if (FUSE == 1) {
             u32x2 pk = {pack2bf(o[0], o[1]), pack2bf(o[2], o[3])};
-            *(u32x2*)((short*)dyn + (long)row * D + 4 * c) = pk;
+            *(u32x2*)((short*)dyn + (long)idx * D + 4 * c) = pk;
             // sum what was stored (bf16-rounded), exactly like colsum over the bf16 tensor would
             dbias[i] += (f32x4){bf2f((short)(pk[0] & 0xFFFF)), bf2f((short)(pk[0] >> 16)), bf2f((short)(pk[1] & 0xFFFF)),
                                 bf2f((short)(pk[1] >> 16))};
           } else {
-            *(f32x4*)((float*)dyn + (long)row * D + 4 * c) = o;
+            *(f32x4*)((float*)dyn + (long)idx * D + 4 * c) = o;
             dbias[i] += o;
           }
         }
@@ -212,12 +236,14 @@ __global__ __launch_bounds__(1024) void ln_bwd_kernel(const void* __restrict__ d
 
 template <int OUT_BF16, int RES>
 static int ln_fwd_dispatch(const float* x, const float* g, const float* b, void* y, float* mean, float* rstd, int rows,
-                           int D, float eps, hipStream_t st, const void* delta = nullptr, float* xsum = nullptr) {
+                           int D, float eps, hipStream_t st, const void* delta = nullptr, float* xsum = nullptr,
+                           long x_ld = 0) {
+  if (x_ld == 0) x_ld = D;
   const int nv = cdiv(D, 256);
   // one round of resident 4-wave blocks over 256 CUs: 8 per CU up to D = 768 (<= 64 VGPRs), 7 at D = 1024 (72 VGPRs)
   constexpr int BLOCKS_NARROW = 2048, BLOCKS_WIDE = 1792;
   const int blocks = std::min(cdiv(rows, 4), nv >= 4 ? BLOCKS_WIDE : BLOCKS_NARROW);
-#define LAUNCH(NV) hipLaunchKernelGGL((ln_fwd_kernel<NV, OUT_BF16, RES>), dim3(blocks), dim3(256), 0, st, x, g, b, y, mean, rstd, rows, D, eps, delta, xsum)
+#define LAUNCH(NV) hipLaunchKernelGGL((ln_fwd_kernel<NV, OUT_BF16, RES>), dim3(blocks), dim3(256), 0, st, x, g, b, y, mean, rstd, rows, D, eps, delta, xsum, x_ld)
   if (nv <= 1) LAUNCH(1);
   else if (nv <= 2) LAUNCH(2);
   else if (nv <= 3) LAUNCH(3);
@@ -232,11 +258,11 @@ static int ln_fwd_dispatch(const float* x, const float* g, const float* b, void*
 template <int DY_BF16, int FUSE>
 static int ln_bwd_dispatch(const void* dy, const float* x, const float* g, const float* mean, const float* rstd,
                            const float* dres, float* dx, float* part, int rows, int D, int blocks, int threads,
-                           void* dyn, DropCfg drop, hipStream_t st) {
+                           void* dyn, DropCfg drop, RowMap rm, hipStream_t st) {
   const int nv = cdiv(D, 256);
   const size_t sh = (size_t)4 * (FUSE ? 3 : 2) * D * sizeof(float) + (FUSE && nv >= 4 ? (size_t)D * sizeof(float) : 0);
   if (sh > 64 * 1024) { set_error("vit_layernorm_bwd: D=%d needs %zu bytes of LDS", D, sh); return VIT_ERR_UNSUPPORTED; }
-#define LAUNCH(NV) hipLaunchKernelGGL((ln_bwd_kernel<NV, DY_BF16, FUSE>), dim3(blocks), dim3(threads), sh, st, dy, x, g, mean, rstd, dres, dx, part, rows, D, dyn, drop)
+#define LAUNCH(NV) hipLaunchKernelGGL((ln_bwd_kernel<NV, DY_BF16, FUSE>), dim3(blocks), dim3(threads), sh, st, dy, x, g, mean, rstd, dres, dx, part, rows, D, dyn, drop, rm)
   if (nv <= 1) LAUNCH(1);
   else if (nv <= 2) LAUNCH(2);
   else if (nv <= 3) LAUNCH(3);
@@ -251,7 +277,7 @@ static int ln_bwd_dispatch(const void* dy, const float* x, const float* g, const
 static int ln_bwd_common(vit_handle h, const void* dy, int dy_dtype, const float* x, const float* gamma,
                          const float* mean, const float* rstd, const float* dres, float* dx, float* dgamma,
                          float* dbeta, int rows, int D, void* dyn, int dyn_dtype, float* dbias, DropCfg drop,
-                         hipStream_t st) {
+                         hipStream_t st, RowMap rm = {0, 0}) {
   // 16 waves per CU: with only two waves per SIMD the pass was latency-bound at 4.3 TB/s (bytes in flight / HBM latency).
   // They are TWO blocks of 512 threads per CU when there are rows for it: a block's waves combine through the LDS four at a
   // time (36 KiB at D = 768), so the pass leaves 512 partial rows instead of 1024 and the reducer needs no first stage (25
@@ -267,13 +293,13 @@ static int ln_bwd_common(vit_handle h, const void* dy, int dy_dtype, const float
   VIT_CHECK(part && wsb >= need, VIT_ERR_WORKSPACE, "vit_layernorm_bwd: needs %zu workspace bytes, have %zu", need, wsb);
   int rc;
   if (dyn && dyn_dtype == VIT_BF16)
-    rc = dy_dtype == VIT_BF16 ? ln_bwd_dispatch<1, 1>(dy, x, gamma, mean, rstd, dres, dx, part, rows, D, blocks, threads, dyn, drop, st)
-                              : ln_bwd_dispatch<0, 1>(dy, x, gamma, mean, rstd, dres, dx, part, rows, D, blocks, threads, dyn, drop, st);
+    rc = dy_dtype == VIT_BF16 ? ln_bwd_dispatch<1, 1>(dy, x, gamma, mean, rstd, dres, dx, part, rows, D, blocks, threads, dyn, drop, rm, st)
+                              : ln_bwd_dispatch<0, 1>(dy, x, gamma, mean, rstd, dres, dx, part, rows, D, blocks, threads, dyn, drop, rm, st);
   else if (dyn)
-    rc = dy_dtype == VIT_BF16 ? ln_bwd_dispatch<1, 2>(dy, x, gamma, mean, rstd, dres, dx, part, rows, D, blocks, threads, dyn, drop, st)
-                              : ln_bwd_dispatch<0, 2>(dy, x, gamma, mean, rstd, dres, dx, part, rows, D, blocks, threads, dyn, drop, st);
-  else rc = dy_dtype == VIT_BF16 ? ln_bwd_dispatch<1, 0>(dy, x, gamma, mean, rstd, dres, dx, part, rows, D, blocks, threads, dyn, drop, st)
-                                 : ln_bwd_dispatch<0, 0>(dy, x, gamma, mean, rstd, dres, dx, part, rows, D, blocks, threads, dyn, drop, st);
+    rc = dy_dtype == VIT_BF16 ? ln_bwd_dispatch<1, 2>(dy, x, gamma, mean, rstd, dres, dx, part, rows, D, blocks, threads, dyn, drop, rm, st)
+                              : ln_bwd_dispatch<0, 2>(dy, x, gamma, mean, rstd, dres, dx, part, rows, D, blocks, threads, dyn, drop, rm, st);
+  else rc = dy_dtype == VIT_BF16 ? ln_bwd_dispatch<1, 0>(dy, x, gamma, mean, rstd, dres, dx, part, rows, D, blocks, threads, dyn, drop, rm, st)
+                                 : ln_bwd_dispatch<0, 0>(dy, x, gamma, mean, rstd, dres, dx, part, rows, D, blocks, threads, dyn, drop, rm, st);
   if (rc != VIT_OK) return rc;
   if (!dyn) return launch_reduce_partials(part, blocks, 2 * D, dgamma, D, dbeta, 0, st, np * D);
   return launch_reduce_partials(part, blocks, 3 * D, dgamma, D, dbeta, 0, st, np * D, 2 * D, dbias);  // one launch for all three
@@ -312,6 +338,25 @@ int vit_layernorm_fwd_residual(vit_handle h, const float* x, const void* delta, 
                              : ln_fwd_dispatch<0, 2>(x, gamma, beta, y, mean, rstd, rows, D, eps, st, delta, xsum);
 }
 
+int vit_layernorm_fwd_residual_rows(vit_handle h, const float* x, int64_t x_row_stride, const void* delta, int delta_dtype,
+                                    float* xsum, const float* gamma, const float* beta, void* y, int y_dtype, float* mean,
+                                    float* rstd, int rows, int D, float eps, vit_stream stream) {
+  using namespace vit;
+  (void)h;
+  VIT_CHECK(x && delta && xsum && gamma && beta && y, VIT_ERR_ARG, "vit_layernorm_fwd_residual_rows: null pointer");
+  VIT_CHECK(rows > 0 && D > 0 && (D % 4) == 0, VIT_ERR_ARG, "vit_layernorm_fwd_residual_rows: rows=%d D=%d (D must be a multiple of 4)", rows, D);
+  VIT_CHECK(x_row_stride >= 1, VIT_ERR_ARG, "vit_layernorm_fwd_residual_rows: x_row_stride=%lld", (long long)x_row_stride);
+  VIT_CHECK((y_dtype == VIT_BF16 || y_dtype == VIT_F32) && (delta_dtype == VIT_BF16 || delta_dtype == VIT_F32), VIT_ERR_ARG,
+            "vit_layernorm_fwd_residual_rows: bad dtype");
+  hipStream_t st = (hipStream_t)stream;
+  const long x_ld = (long)x_row_stride * D;
+  if (delta_dtype == VIT_BF16)
+    return y_dtype == VIT_BF16 ? ln_fwd_dispatch<1, 1>(x, gamma, beta, y, mean, rstd, rows, D, eps, st, delta, xsum, x_ld)
+                               : ln_fwd_dispatch<0, 1>(x, gamma, beta, y, mean, rstd, rows, D, eps, st, delta, xsum, x_ld);
+  return y_dtype == VIT_BF16 ? ln_fwd_dispatch<1, 2>(x, gamma, beta, y, mean, rstd, rows, D, eps, st, delta, xsum, x_ld)
+                             : ln_fwd_dispatch<0, 2>(x, gamma, beta, y, mean, rstd, rows, D, eps, st, delta, xsum, x_ld);
+}
+
 int vit_layernorm_bwd(vit_handle h, const void* dy, int dy_dtype, const float* x, const float* gamma,
                       const float* mean, const float* rstd, const float* dres, float* dx, float* dgamma,
                       float* dbeta, int rows, int D, vit_stream stream) {
@@ -333,6 +378,27 @@ int vit_layernorm_bwd_fused(vit_handle h, const void* dy, int dy_dtype, const fl
   VIT_CHECK(dropout_p >= 0.f && dropout_p < 1.f, VIT_ERR_ARG, "vit_layernorm_bwd_fused: dropout_p out of [0,1)");
   return ln_bwd_common(h, dy, dy_dtype, x, gamma, mean, rstd, dres, dx, dgamma, dbeta, rows, D, dyn, dyn_dtype, dbias,
                        make_drop_h(h, dropout_p, seed, site), (hipStream_t)stream);
+}
+
+int vit_layernorm_bwd_rows(vit_handle h, const void* dy, int dy_dtype, const float* x, const float* gamma, const float* mean,
+                           const float* rstd, const float* dres, int64_t dres_row_stride, float* dx, float* dgamma,
+                           float* dbeta, int rows, int D, void* dyn, int dyn_dtype, float* dbias, float dropout_p,
+                           uint64_t seed, uint64_t site, int64_t row_stride, vit_stream stream) {
+  using namespace vit;
+  VIT_CHECK(dy && x && gamma && mean && rstd && dx && dgamma && dbeta && (!dyn || dbias), VIT_ERR_ARG,
+            "vit_layernorm_bwd_rows: null pointer");
+  VIT_CHECK(rows > 0 && D > 0 && (D % 4) == 0, VIT_ERR_ARG, "vit_layernorm_bwd_rows: rows=%d D=%d", rows, D);
+  VIT_CHECK(dropout_p >= 0.f && dropout_p < 1.f, VIT_ERR_ARG, "vit_layernorm_bwd_rows: dropout_p out of [0,1)");
+  VIT_CHECK(dres_row_stride >= 0 && dres_row_stride <= 0x7FFFFFFF && row_stride >= 1 && row_stride <= 0x7FFFFFFF,
+            VIT_ERR_ARG, "vit_layernorm_bwd_rows: dres_row_stride=%lld row_stride=%lld", (long long)dres_row_stride,
+            (long long)row_stride);
+  VIT_CHECK(!(row_stride > 1 && dres_row_stride > 0), VIT_ERR_ARG, "vit_layernorm_bwd_rows: a compact dres needs full rows");
+  const RowMap rm = {row_stride > 1 ? (int)row_stride : 0, (int)dres_row_stride};
+  if (!dyn)
+    return ln_bwd_common(h, dy, dy_dtype, x, gamma, mean, rstd, dres, dx, dgamma, dbeta, rows, D, nullptr, VIT_BF16, nullptr,
+                         make_drop(0.f, 0, 0), (hipStream_t)stream, rm);
+  return ln_bwd_common(h, dy, dy_dtype, x, gamma, mean, rstd, dres, dx, dgamma, dbeta, rows, D, dyn, dyn_dtype, dbias,
+                       make_drop_h(h, dropout_p, seed, site), (hipStream_t)stream, rm);
 }
 
 }  // extern "C"

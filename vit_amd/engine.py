@@ -10,11 +10,14 @@ Data layout in HBM (one MI355X, 288 GB: nothing is recomputed or re-materialised
   grads    f32 [n_total]   same offsets; every kernel that produces a parameter gradient writes its slice exactly once.
   arena    per layer: x_in f32 [M,D] (residual stream), h1/h2 bf16 [M,D] (LN outputs), qkv bf16 [M,3D], ctx bf16 [M,D],
            lse f32 [B*H,T], x1 f32 [M,D], u/g bf16 [M,4D] (pre/post GELU), LN statistics.  M = B*T token rows.
+  CLS tail c_* : compact [B, .] twins of y / x1 / h2 / u / g / x[L] / last and their statistics (and of the backward's
+           scratch): what the last layer computes behind its attention when only the head consumes it (see `cls_tail`).
 Dropout masks are regenerated from (seed, site) in backward; no mask is stored.
 """
 from __future__ import annotations
 
 import math
+import os
 from typing import Callable, Dict, List, Optional, Tuple
 
 import torch
@@ -168,6 +171,10 @@ class ViTEngine:
         # True / False / "auto": the second stream pays when the main stream's GEMMs leave a large part of the chip idle for
         # whole kernels (see _want_side)
         self.overlap_dw = "auto"
+        # The head reads one row per image (specvit.py:78-81) and everything behind the last layer's attention is row-wise, so
+        # unless the caller asked for hidden states that part of the last layer runs over the B CLS rows only, forward and
+        # backward.  False forces the full path (tests; VIT_CLS_TAIL=0: A/B runs of unmodified scripts).
+        self.cls_tail = os.environ.get("VIT_CLS_TAIL", "1") != "0"
         self._gen = 0  # bumped by every forward: the activation arena holds ONE forward, backward checks it is still that one
         self.grad_ready_cb: Optional[Callable[[int, int], None]] = None
         # Parameters are views of `flat` with their OWN version counters (nn.Parameter / .data re-pointing do not share
@@ -331,6 +338,10 @@ class ViTEngine:
             mean2=[E((M,), f32) for _ in range(nl)], rstd2=[E((M,), f32) for _ in range(nl)],
             last=E((B, T, D), f32), meanF=E((M,), f32), rstdF=E((M,), f32),
             y=G(D, b16),  # dropout(Linear(.)) of the attention-output / FC2 projection, until the next LayerNorm adds it
+            # the last layer's CLS tail: one row per image
+            c_y=E((B, D), b16), c_x1=E((B, D), f32), c_h2=E((B, D), b16), c_u=E((B, Fd), b16), c_g=E((B, Fd), b16),
+            c_mean2=E((B,), f32), c_rstd2=E((B,), f32), c_xL=E((B, D), f32), c_last=E((B, 1, D), f32),
+            c_meanF=E((B,), f32), c_rstdF=E((B,), f32),
         )
         self.tmp = {}
         if train:
@@ -338,6 +349,14 @@ class ViTEngine:
                 dxa=E((M, D), f32), dxb=E((M, D), f32), dy=G(D, b16), dy2=G(D, b16), dU=G(Fd, b16), dh=G(D, b16),
                 dqkv=G(3 * D, b16), dctx=G(D, b16), delta=E((B * H, T), f32), dpatch=E((B * N, D), b16),
                 dlast=E((B, T, D), f32),
+                c_dxa=E((B, D), f32), c_dxb=E((B, D), f32), c_dy=E((B, D), b16), c_dy2=E((B, D), b16), c_dU=E((B, Fd), b16),
+                c_dh=E((B, D), b16), c_dlast=E((B, 1, D), f32),
+                # the CLS tail's dctx: only its rows b*T are ever written, every other row keeps the zero it was allocated
+                # with -- the attention backward reads a full [M, D] gradient and no per-step fill is needed.  INVARIANT: the
+                # one writer is _backward_cls_tail's out-projection dX (B and T are fixed for the arena's life); anything
+                # else that writes this buffer breaks the tail's gradients silently (tests/test_cls_tail_gpu.py poisons the
+                # rows in between and checks that nothing rewrites them)
+                dctx_cls=G(D, b16),
             )
         self._arena_key = key
         self._arenas[train] = (key, self.act, self.tmp, Mp)
@@ -412,6 +431,7 @@ class ViTEngine:
         # that consumes them: the projection GEMM writes y = dropout(acc + bias) in the activation dtype, the LayerNorm
         # pass reads the f32 stream and y, writes the new stream and its normalised operand (vit_layernorm_fwd_residual).
         y = a["y"]
+        tail = bool(self.cls_tail) and L > 0 and not output_hidden_states
         for i in range(L):
             j = i if need_grad else 0
             pre = f"vit.encoder.layer.{i}."
@@ -430,6 +450,8 @@ class ViTEngine:
                 atts.append(vf.attention_probs(a["qkv"][j], B, H, T, dh, scale))
             if capture_ctx is not None:  # per-layer context for forward hooks on the attention modules
                 capture_ctx.append(a["ctx"][j].view(B, T, D).clone())
+            if tail and i == L - 1:
+                break
             vf.gemm(a["ctx"][j], self.w16(pre + "attention.output.dense.weight"), M=Mp, N=D, K=D, out=y,
                     bias=self.p(pre + "attention.output.dense.bias"), dropout=(ph, seed, self._site(i, 1)))
             self._ln_res(xin, y, a["x1"][j], pre + "layernorm_after", a["h2"][j], a["mean2"][j], a["rstd2"][j])
@@ -439,7 +461,25 @@ class ViTEngine:
             vf.gemm(a["g"][j], self.w16(pre + "output.dense.weight"), M=Mp, N=D, K=Fd, out=y,
                     bias=self.p(pre + "output.dense.bias"), dropout=(ph, seed, self._site(i, 2)))
             jprev = j
-        if L > 0:
+        last = a["last"]
+        if tail:
+            # the last layer behind its attention, over the rows b*T alone: ctx and the residual stream are read in place
+            # (row stride T), everything written is compact, and the dropout masks are keyed by the ORIGINAL row b*T so that
+            # they are the full path's (and oracle/dropmask.py's) bit for bit
+            i, pre = L - 1, f"vit.encoder.layer.{L - 1}."
+            j = i if need_grad else 0
+            cy, last = a["c_y"], a["c_last"]
+            vf.gemm(a["ctx"][j], self.w16(pre + "attention.output.dense.weight"), M=B, N=D, K=D, lda=T * D, out=cy,
+                    bias=self.p(pre + "attention.output.dense.bias"), dropout=(ph, seed, self._site(i, 1)), drop_row_stride=T)
+            self._ln_res(a["x"][i].view(M, D), cy, a["c_x1"], pre + "layernorm_after", a["c_h2"], a["c_mean2"], a["c_rstd2"],
+                         x_row_stride=T)
+            vf.gemm(a["c_h2"], self.w16(pre + "intermediate.dense.weight"), M=B, N=Fd, K=D, out=a["c_g"],
+                    bias=self.p(pre + "intermediate.dense.bias"), act=vf.ACT_GELU_GRAD if need_grad else ACT_GELU,
+                    aux_out=a["c_u"] if need_grad else None)
+            vf.gemm(a["c_g"], self.w16(pre + "output.dense.weight"), M=B, N=D, K=Fd, out=cy,
+                    bias=self.p(pre + "output.dense.bias"), dropout=(ph, seed, self._site(i, 2)), drop_row_stride=T)
+            self._ln_res(a["c_x1"], cy, a["c_xL"], "vit.layernorm", last.view(B, D), a["c_meanF"], a["c_rstdF"])
+        elif L > 0:
             self._ln_res(a["x1"][jprev], y, a["x"][L].view(M, D), "vit.layernorm", a["last"].view(M, D), a["meanF"],
                          a["rstdF"])
         else:
@@ -451,8 +491,9 @@ class ViTEngine:
             n_expected = B if self.loss_kind == LOSS_CE else B * c.num_labels
             if labels.numel() != n_expected:
                 raise ValueError(f"labels has {labels.numel()} elements, expected {n_expected}")
-        logits, loss = vf.head_loss_fwd(a["last"], self.p(hn + ".weight"), self.p(hn + ".bias"), labels, self.loss_kind)
-        self._last = dict(B=B, seed=seed, ph=ph, pa=pa, labels=labels, logits=logits, gen=self._gen, grad=need_grad)
+        logits, loss = vf.head_loss_fwd(last, self.p(hn + ".weight"), self.p(hn + ".bias"), labels, self.loss_kind)
+        self._last = dict(B=B, seed=seed, ph=ph, pa=pa, labels=labels, logits=logits, gen=self._gen, grad=need_grad,
+                          tail=tail)
         hs = [t.clone() for t in a["x"]] if output_hidden_states else None
         return loss, logits, hs, atts
 
@@ -469,9 +510,9 @@ class ViTEngine:
         vf.layernorm_fwd(x, self.p(name + ".weight"), self.p(name + ".bias"), self.cfg.layer_norm_eps, out=out,
                          mean=mean, rstd=rstd)
 
-    def _ln_res(self, x, delta, xsum, name, out, mean, rstd):
+    def _ln_res(self, x, delta, xsum, name, out, mean, rstd, x_row_stride=1):
         vf.layernorm_fwd_residual(x, delta, xsum, self.p(name + ".weight"), self.p(name + ".bias"),
-                                  self.cfg.layer_norm_eps, out=out, mean=mean, rstd=rstd)
+                                  self.cfg.layer_norm_eps, out=out, mean=mean, rstd=rstd, x_row_stride=x_row_stride)
 
     # ------------------------------------------------------------------ weight gradients beside the data path
     def _dw(self, *args, reads=(), **kw):
@@ -495,6 +536,16 @@ class ViTEngine:
                 for name in reads:
                     self._side_reads[name] = ev
         return out
+
+    def _dw_rows(self, dy, x, out, **kw):
+        """_dw for the CLS tail's compact weight gradients (vf.linear_bwd_dw_rows).  No read events are recorded: c_dy, c_dU
+        and c_dy2 have ONE writer per step each, which runs before this call on the main stream, and the next step's writers
+        run behind _join_side; a second writer of one of them inside a step would need _before_write like the full path's."""
+        if self.side_stream is None:
+            return vf.linear_bwd_dw_rows(dy, x, out, **kw)
+        self.side_stream.wait_stream(torch.cuda.current_stream(self.flat.device))
+        with torch.cuda.stream(self.side_stream), vf.use_handle(self._side_handle):
+            return vf.linear_bwd_dw_rows(dy, x, out, **kw)
 
     def _before_write(self, *names):
         if self.side_stream is None:
@@ -557,6 +608,37 @@ class ViTEngine:
             self.side_stream = None
 
     # ------------------------------------------------------------------ backward
+    def _backward_cls_tail(self, i: int, cdx: torch.Tensor, ph: float, seed: int) -> torch.Tensor:
+        """The last layer's backward from the final LayerNorm's input gradient down to dctx, over the B CLS rows: `cdx` is the
+        compact [B, D] gradient of the residual stream (t["c_dy"] = mask * cdx and the FC2 bias gradient came with it).  The
+        weight gradients and bias / LayerNorm parameter sums run over the B rows in the summation order of the full-size
+        passes (whose other rows are exact zeros), so they are the full path's bit for bit at T >= 64 (vit_amd.h:
+        vit_linear_bwd_dw_rows); the attention-output dX writes its B rows straight into the rows b*T of the otherwise zero
+        t["dctx_cls"].  Returns the compact residual gradient at the layer's LN-after
+        input.  Every c_* scratch buffer is written once per step, behind the join of the previous step, so the second
+        stream's readers need no _before_write."""
+        c, a, t = self.cfg, self.act, self.tmp
+        T, D, Fd = c.seq_len, c.hidden_size, c.intermediate_size
+        B = cdx.shape[0]
+        pre = f"vit.encoder.layer.{i}."
+        other = t["c_dxb"] if cdx is t["c_dxa"] else t["c_dxa"]
+        Mp = self._Mp
+        self._dw_rows(t["c_dy"], a["c_g"], self.g(pre + "output.dense.weight"), row_stride=T, full_rows=Mp)
+        vf.gemm(t["c_dy"], self.w16(pre + "output.dense.weight"), M=B, N=Fd, K=D, b_trans=True, out=t["c_dU"],
+                act=vf.ACT_MUL_AUX, aux_in=a["c_u"])
+        vf.colsum_rows(t["c_dU"], self.g(pre + "intermediate.dense.bias"), row_stride=T, full_rows=Mp)
+        self._dw_rows(t["c_dU"], a["c_h2"], self.g(pre + "intermediate.dense.weight"), row_stride=T, full_rows=Mp)
+        vf.gemm(t["c_dU"], self.w16(pre + "intermediate.dense.weight"), M=B, N=D, K=Fd, b_trans=True, out=t["c_dh"])
+        vf.layernorm_bwd_rows(t["c_dh"], a["c_x1"], self.p(pre + "layernorm_after.weight"), a["c_mean2"], a["c_rstd2"], cdx,
+                              other, self.g(pre + "layernorm_after.weight"), self.g(pre + "layernorm_after.bias"),
+                              dyn=t["c_dy2"], dbias=self.g(pre + "attention.output.dense.bias"),
+                              dropout=(ph, seed, self._site(i, 1)), row_stride=T, full_rows=B * T)
+        self._dw_rows(t["c_dy2"], a["ctx"][i], self.g(pre + "attention.output.dense.weight"), row_stride=T, full_rows=Mp,
+                      ldx=T * D)
+        vf.gemm(t["c_dy2"], self.w16(pre + "attention.output.dense.weight"), M=B, N=D, K=D, b_trans=True,
+                out=t["dctx_cls"], ldc=T * D)
+        return other
+
     def backward(self, dloss: torch.Tensor, need_dx: bool = False, gen: Optional[int] = None):
         with vf.use_handle(self.handle()):
             return self._backward(dloss, need_dx, gen)
@@ -584,13 +666,23 @@ class ViTEngine:
         hn = self.layout.head
         dloss = dloss.reshape(1).to(torch.float32).contiguous()
 
-        vf.head_loss_bwd(a["last"], self.p(hn + ".weight"), st["logits"], st["labels"], dloss, self.loss_kind,
-                         dlast=t["dlast"], dW=self.g(hn + ".weight"), db=self.g(hn + ".bias"))
+        tail = st["tail"]
+        vf.head_loss_bwd(a["c_last"] if tail else a["last"], self.p(hn + ".weight"), st["logits"], st["labels"], dloss,
+                         self.loss_kind, dlast=t["c_dlast"] if tail else t["dlast"], dW=self.g(hn + ".weight"),
+                         db=self.g(hn + ".bias"))
         self._setup_side()
         dx, dx_other = t["dxa"], t["dxb"]
+        cdx = None  # CLS tail: the compact [B, D] residual gradient that re-enters the token stream at the last layer's LN-before
         # every LayerNorm backward below also emits dy = dropout_mask * dx (bf16) and its column sums: the gradient of
         # the Linear output underneath the next "dropout(.) + residual" going down, and that Linear's bias gradient
-        if L == 0:  # no encoder layer: the final LayerNorm sits directly on the embeddings
+        if tail:
+            last_pre = f"vit.encoder.layer.{L - 1}."
+            cdx = t["c_dxa"]
+            vf.layernorm_bwd_rows(t["c_dlast"].view(B, D), a["c_xL"], self.p("vit.layernorm.weight"), a["c_meanF"],
+                                  a["c_rstdF"], None, cdx, self.g("vit.layernorm.weight"), self.g("vit.layernorm.bias"),
+                                  dyn=t["c_dy"], dbias=self.g(last_pre + "output.dense.bias"),
+                                  dropout=(ph, seed, self._site(L - 1, 2)), row_stride=T, full_rows=M)
+        elif L == 0:  # no encoder layer: the final LayerNorm sits directly on the embeddings
             vf.layernorm_bwd(t["dlast"].view(M, D), a["x"][0].view(M, D), self.p("vit.layernorm.weight"), a["meanF"],
                              a["rstdF"], dres=None, dx=dx, dgamma=self.g("vit.layernorm.weight"),
                              dbeta=self.g("vit.layernorm.bias"))
@@ -602,30 +694,35 @@ class ViTEngine:
         self._notify(self.layout.tail_start, self.layout.n_trainable)
         for i in reversed(range(L)):
             pre = f"vit.encoder.layer.{i}."
-            # x2 = dropout(g W2^T + b2) + x1      (t["dy"] = mask * dx and db2 were produced by the LN backward above)
-            self._dw(t["dy"], a["g"][i], M=D, N=Fd, K=Mp, a_trans=True, b_trans=True, out=self.g(pre + "output.dense.weight"),
-                     split_k=-1, reads=("dy",))
-            self._before_write("dU")
-            vf.gemm(t["dy"], self.w16(pre + "output.dense.weight"), M=Mp, N=Fd, K=D, b_trans=True, out=t["dU"],
-                    act=vf.ACT_MUL_AUX, aux_in=a["u"][i], colsum_out=self.g(pre + "intermediate.dense.bias"))
-            self._dw(t["dU"], a["h2"][i], M=Fd, N=D, K=Mp, a_trans=True, b_trans=True,
-                     out=self.g(pre + "intermediate.dense.weight"), split_k=-1, reads=("dU",))
-            vf.gemm(t["dU"], self.w16(pre + "intermediate.dense.weight"), M=Mp, N=D, K=Fd, b_trans=True, out=t["dh"])
-            # x1 = dropout(ctx Wo^T + bo) + x:  LN2 backward -> dx1, and dya = mask * dx1 with dbo
-            # this pass writes the OTHER dy buffer: the FC2 weight gradient still reading t["dy"] keeps running beside it
-            self._before_write("dy2")
-            vf.layernorm_bwd_fused(t["dh"], a["x1"][i], self.p(pre + "layernorm_after.weight"), a["mean2"][i],
-                                   a["rstd2"][i], dx, dx_other, self.g(pre + "layernorm_after.weight"),
-                                   self.g(pre + "layernorm_after.bias"), t["dy2"],
-                                   self.g(pre + "attention.output.dense.bias"), (ph, seed, self._site(i, 1)))
-            dx, dx_other = dx_other, dx
-            self._dw(t["dy2"], a["ctx"][i], M=D, N=D, K=Mp, a_trans=True, b_trans=True,
-                     out=self.g(pre + "attention.output.dense.weight"), split_k=-1, reads=("dy2",))
-            vf.gemm(t["dy2"], self.w16(pre + "attention.output.dense.weight"), M=Mp, N=D, K=D, b_trans=True, out=t["dctx"])
+            if cdx is not None:
+                cdx, dctx = self._backward_cls_tail(i, cdx, ph, seed), t["dctx_cls"]
+            else:
+                # x2 = dropout(g W2^T + b2) + x1      (t["dy"] = mask * dx and db2 were produced by the LN backward above)
+                self._dw(t["dy"], a["g"][i], M=D, N=Fd, K=Mp, a_trans=True, b_trans=True,
+                         out=self.g(pre + "output.dense.weight"), split_k=-1, reads=("dy",))
+                self._before_write("dU")
+                vf.gemm(t["dy"], self.w16(pre + "output.dense.weight"), M=Mp, N=Fd, K=D, b_trans=True, out=t["dU"],
+                        act=vf.ACT_MUL_AUX, aux_in=a["u"][i], colsum_out=self.g(pre + "intermediate.dense.bias"))
+                self._dw(t["dU"], a["h2"][i], M=Fd, N=D, K=Mp, a_trans=True, b_trans=True,
+                         out=self.g(pre + "intermediate.dense.weight"), split_k=-1, reads=("dU",))
+                vf.gemm(t["dU"], self.w16(pre + "intermediate.dense.weight"), M=Mp, N=D, K=Fd, b_trans=True, out=t["dh"])
+                # x1 = dropout(ctx Wo^T + bo) + x:  LN2 backward -> dx1, and dya = mask * dx1 with dbo
+                # this pass writes the OTHER dy buffer: the FC2 weight gradient still reading t["dy"] keeps running beside it
+                self._before_write("dy2")
+                vf.layernorm_bwd_fused(t["dh"], a["x1"][i], self.p(pre + "layernorm_after.weight"), a["mean2"][i],
+                                       a["rstd2"][i], dx, dx_other, self.g(pre + "layernorm_after.weight"),
+                                       self.g(pre + "layernorm_after.bias"), t["dy2"],
+                                       self.g(pre + "attention.output.dense.bias"), (ph, seed, self._site(i, 1)))
+                dx, dx_other = dx_other, dx
+                self._dw(t["dy2"], a["ctx"][i], M=D, N=D, K=Mp, a_trans=True, b_trans=True,
+                         out=self.g(pre + "attention.output.dense.weight"), split_k=-1, reads=("dy2",))
+                vf.gemm(t["dy2"], self.w16(pre + "attention.output.dense.weight"), M=Mp, N=D, K=D, b_trans=True,
+                        out=t["dctx"])
+                dctx = t["dctx"]
             self._before_write("dqkv")
             # the QKV bias gradient = column sums of dqkv: taken by the attention kernels on their way out, unless RoPE
             # sits in between (then after the inverse rotation, by the column-sum kernel)
-            vf.attention_bwd(a["qkv"][i], a["ctx"][i], t["dctx"], a["lse"][i], B, H, T, dh, scale,
+            vf.attention_bwd(a["qkv"][i], a["ctx"][i], dctx, a["lse"][i], B, H, T, dh, scale,
                              dropout=(pa, seed, self._site(i, 0)), dqkv=t["dqkv"], delta=t["delta"],
                              colsum_out=None if rope is not None else self._qkv_bias(i, self.grads), ctx_lo=a["ctx_lo"][i])
             if rope is not None:  # gradient wrt the un-rotated q, k: the inverse rotation
@@ -635,7 +732,17 @@ class ViTEngine:
                      split_k=-1, reads=("dqkv",))
             vf.gemm(t["dqkv"], self._qkv16(i), M=Mp, N=D, K=3 * D, b_trans=True, out=t["dh"])
             self._before_write("dy")  # the LayerNorm backward below rewrites t["dy"] (read by this layer's FC2 weight gradient)
-            if i > 0:
+            if cdx is not None:
+                # LN1 backward of the last layer: the compact residual gradient joins the token stream at the rows b*T (every
+                # other row has none); from here down the gradient is dense and the path is the full one
+                prev = f"vit.encoder.layer.{i - 1}."
+                vf.layernorm_bwd_rows(t["dh"], a["x"][i].view(M, D), self.p(pre + "layernorm_before.weight"), a["mean1"][i],
+                                      a["rstd1"][i], cdx, dx_other, self.g(pre + "layernorm_before.weight"),
+                                      self.g(pre + "layernorm_before.bias"), dyn=t["dy"] if i > 0 else None,
+                                      dbias=self.g(prev + "output.dense.bias") if i > 0 else None,
+                                      dropout=(ph, seed, self._site(i - 1, 2)) if i > 0 else vf.NO_DROP, dres_row_stride=T)
+                cdx = None
+            elif i > 0:
                 # LN1 backward -> dx (input of this layer = output of layer i-1), plus layer i-1's FC2 pieces
                 prev = f"vit.encoder.layer.{i - 1}."
                 vf.layernorm_bwd_fused(t["dh"], a["x"][i].view(M, D), self.p(pre + "layernorm_before.weight"),

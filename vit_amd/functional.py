@@ -67,8 +67,10 @@ def gemm(a: torch.Tensor, b: torch.Tensor, *, M: int, N: int, K: int, a_trans: b
          dropout: Dropout = NO_DROP, residual: Optional[torch.Tensor] = None, row_map: Tuple[int, int, int] = (0, 0, 0),
          out_rows: Optional[int] = None, split_k: int = 0, accumulate: bool = False,
          colsum_out: Optional[torch.Tensor] = None,
-         rope: Optional[Tuple[torch.Tensor, torch.Tensor, int, int, int]] = None) -> torch.Tensor:
-    """`rope = (cos, sin, T, head_dim, cols)`: rotary embedding of columns [0, cols) of the output (the q / k thirds of a fused QKV
+         rope: Optional[Tuple[torch.Tensor, torch.Tensor, int, int, int]] = None, drop_row_stride: int = 0) -> torch.Tensor:
+    """`drop_row_stride = s > 1`: the dropout mask of output row r is the one of row r * s (the rows are a strided subset of
+    a larger problem's: A read in place with `lda = s * K`, compact output).
+    `rope = (cos, sin, T, head_dim, cols)`: rotary embedding of columns [0, cols) of the output (the q / k thirds of a fused QKV
     projection; cos / sin: f32 [T, head_dim / 2], rows = the reference's LINEAR zero-based positions t * theta_i -- the rotating
     epilogue steps angles by a recurrence over table row 8; other tables: `rope_qk`) -- in the GEMM's epilogue where the kernel can, by a vit_rope_qk pass behind it
     otherwise (the library decides; same result contract)."""
@@ -89,6 +91,7 @@ def gemm(a: torch.Tensor, b: torch.Tensor, *, M: int, N: int, K: int, a_trans: b
     d.act = act
     d.aux_out, d.aux_in, d.ldaux = _ptr(aux_out), _ptr(aux_in), N
     d.dropout_p, d.seed, d.site = dropout
+    d.drop_row_stride = int(drop_row_stride)
     d.residual, d.ldres = _ptr(residual), N
     d.rows_per_batch, d.out_batch_rows, d.out_row_offset = row_map
     d.split_k = split_k
@@ -156,18 +159,29 @@ def layernorm_fwd(x, gamma, beta, eps: float, out_dtype=torch.bfloat16, out=None
 
 
 def layernorm_fwd_residual(x, delta, xsum, gamma, beta, eps: float, out_dtype=torch.bfloat16, out=None, mean=None,
-                           rstd=None):
-    """xsum = x + delta (f32 stream + bf16/f32 projection output); y = LayerNorm(xsum)."""
+                           rstd=None, x_row_stride: int = 1):
+    """xsum = x + delta (f32 stream + bf16/f32 projection output); y = LayerNorm(xsum).
+    `x_row_stride = s > 1`: the rows are every s-th row of x (delta, xsum, y, mean, rstd compact: x.numel() / (D s) rows)."""
     _chk(x, torch.float32, "layernorm_fwd_residual x")
     _chk(xsum, torch.float32, "layernorm_fwd_residual xsum")
-    if delta.dtype not in _DT or not delta.is_contiguous() or delta.numel() != x.numel() or xsum.numel() != x.numel():
-        raise _cabi.VitError("layernorm_fwd_residual: delta must be a contiguous bf16/f32 tensor of x's shape")
     h = _h(x)
     D = x.shape[-1]
-    rows = x.numel() // D
-    y = out if out is not None else torch.empty(x.shape, dtype=out_dtype, device=x.device)
+    rows = xsum.numel() // D
+    if x_row_stride < 1 or (rows - 1) * x_row_stride * D + D > x.numel() or (x_row_stride == 1 and x.numel() != xsum.numel()):
+        raise _cabi.VitError("layernorm_fwd_residual: x does not hold the rows that xsum and x_row_stride name")
+    if delta.dtype not in _DT or not delta.is_contiguous() or delta.numel() != xsum.numel():
+        raise _cabi.VitError("layernorm_fwd_residual: delta must be a contiguous bf16/f32 tensor of xsum's shape")
+    y = out if out is not None else torch.empty(xsum.shape, dtype=out_dtype, device=x.device)
     mean = mean if mean is not None else torch.empty(rows, dtype=torch.float32, device=x.device)
     rstd = rstd if rstd is not None else torch.empty(rows, dtype=torch.float32, device=x.device)
+    if y.numel() != xsum.numel() or mean.numel() < rows or rstd.numel() < rows:
+        raise _cabi.VitError("layernorm_fwd_residual: out / mean / rstd do not hold xsum's rows")
+    if x_row_stride != 1:
+        check(h.lib.vit_layernorm_fwd_residual_rows(h.h, x.data_ptr(), x_row_stride, delta.data_ptr(), _DT[delta.dtype],
+                                                    xsum.data_ptr(), gamma.data_ptr(), beta.data_ptr(), y.data_ptr(),
+                                                    _DT[y.dtype], _ptr(mean), _ptr(rstd), rows, D, eps, _stream(x)),
+              "vit_layernorm_fwd_residual_rows")
+        return y, mean, rstd
     check(h.lib.vit_layernorm_fwd_residual(h.h, x.data_ptr(), delta.data_ptr(), _DT[delta.dtype], xsum.data_ptr(),
                                            gamma.data_ptr(), beta.data_ptr(), y.data_ptr(), _DT[y.dtype], _ptr(mean),
                                            _ptr(rstd), rows, D, eps, _stream(x)), "vit_layernorm_fwd_residual")
@@ -200,6 +214,67 @@ def layernorm_bwd_fused(dy, x, gamma, mean, rstd, dres, dx, dgamma, dbeta, dyn, 
                                         dbeta.data_ptr(), rows, D, dyn.data_ptr(), _DT[dyn.dtype], dbias.data_ptr(), p, seed,
                                         site, _stream(x)), "vit_layernorm_bwd_fused")
     return dx, dgamma, dbeta, dyn, dbias
+
+
+def layernorm_bwd_rows(dy, x, gamma, mean, rstd, dres, dx, dgamma, dbeta, dyn=None, dbias=None, dropout: Dropout = NO_DROP,
+                       dres_row_stride: int = 0, row_stride: int = 1, full_rows: Optional[int] = None):
+    """layernorm_bwd (dyn None) / layernorm_bwd_fused at the two ends of a compact run of rows (vit_layernorm_bwd_rows):
+    `row_stride = s > 1`: the tensors hold the rows r = j * s of a full tensor of `full_rows` rows compactly (mask keyed by r,
+    parameter gradients summed in the full pass's order); `dres_row_stride = s > 0`: dres alone is compact and its row j is the
+    residual gradient of row j * s, every other row has none."""
+    _chk(x, torch.float32, "layernorm_bwd_rows x")
+    _chk(dx, torch.float32, "layernorm_bwd_rows dx")
+    h = _h(x)
+    D = x.shape[-1]
+    rows = x.numel() // D
+    if dy.numel() != x.numel() or dx.numel() != x.numel() or mean.numel() < rows or rstd.numel() < rows or \
+            (dyn is not None and (dyn.numel() != x.numel() or dbias is None)):
+        raise _cabi.VitError("layernorm_bwd_rows: dy / dx / dyn must have x's shape, mean / rstd its rows")
+    if dres is not None:
+        _chk(dres, torch.float32, "layernorm_bwd_rows dres")
+        need = x.numel() if dres_row_stride == 0 else -(-rows // dres_row_stride) * D
+        if dres_row_stride < 0 or dres.numel() < need:
+            raise _cabi.VitError(f"layernorm_bwd_rows: dres holds {dres.numel()} elements, needs {need}")
+    p, seed, site = dropout
+    if row_stride > 1:
+        full_rows = (rows - 1) * row_stride + 1 if full_rows is None else full_rows
+        if dres_row_stride or -(-full_rows // row_stride) != rows:
+            raise _cabi.VitError("layernorm_bwd_rows: row_stride needs full_rows = the full tensor's rows and a dres like dx")
+        h.ensure_workspace(1024 * 3 * D * 4)
+        rows = full_rows
+    check(h.lib.vit_layernorm_bwd_rows(h.h, dy.data_ptr(), _DT[dy.dtype], x.data_ptr(), gamma.data_ptr(), mean.data_ptr(),
+                                       rstd.data_ptr(), _ptr(dres), dres_row_stride, dx.data_ptr(), dgamma.data_ptr(),
+                                       dbeta.data_ptr(), rows, D, _ptr(dyn), _DT[dyn.dtype] if dyn is not None else VIT_BF16,
+                                       _ptr(dbias), p, seed, site, row_stride, _stream(x)), "vit_layernorm_bwd_rows")
+    return dx
+
+
+def linear_bwd_dw_rows(dy, x, out, *, row_stride: int, full_rows: int, ldx: Optional[int] = None):
+    """out[N, K] (f32) = dy^T x over compact rows that stand for the rows b * row_stride of full tensors of `full_rows` rows,
+    summed in the full product's order where that product would run the ping-pong core (vit_linear_bwd_dw_rows)."""
+    _chk(out, torch.float32, "linear_bwd_dw_rows out")
+    if dy.dtype != x.dtype or dy.dtype not in _DT:
+        raise _cabi.VitError("linear_bwd_dw_rows: operands must both be bf16 or both f32")
+    h = _h(dy)
+    rows, N = dy.shape
+    K = out.shape[1]
+    if out.shape[0] != N or not out.is_contiguous() or not dy.is_contiguous():
+        raise _cabi.VitError("linear_bwd_dw_rows: out must be a contiguous [N, K] tensor, dy contiguous")
+    check(h.lib.vit_linear_bwd_dw_rows(h.h, dy.data_ptr(), N, x.data_ptr(), ldx if ldx is not None else K, _DT[dy.dtype],
+                                       out.data_ptr(), rows, N, K, row_stride, full_rows, _stream(dy)),
+          "vit_linear_bwd_dw_rows")
+    return out
+
+
+def colsum_rows(a, out, *, row_stride: int, full_rows: int):
+    """out[cols] = column sums of compact a, in the order of the fused column sums over the full tensor (vit_colsum_rows)."""
+    _chk(out, torch.float32, "colsum_rows out")
+    h = _h(a)
+    rows, cols = a.shape
+    h.ensure_workspace(max((full_rows // 128 + 1) * cols * 4, 2048 * cols * 4))
+    check(h.lib.vit_colsum_rows(h.h, a.data_ptr(), _DT[a.dtype], a.stride(0), out.data_ptr(), rows, cols, row_stride, full_rows,
+                                _stream(a)), "vit_colsum_rows")
+    return out
 
 
 # ------------------------------------------------------------------------------------------------ attention

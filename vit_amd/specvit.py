@@ -73,9 +73,12 @@ class _ViTFunction(torch.autograd.Function):
     views of the engine's flat gradient buffer (no copies when .grad is None, i.e. zero_grad(set_to_none=True))."""
 
     @staticmethod
-    def forward(ctx, model, x, labels, training, *params):
+    def forward(ctx, model, x, labels, training, keep_hidden, *params):
         eng = model.engine
-        loss, logits, _, _ = eng.forward(x, labels, training=training, need_grad=True)
+        # keep_hidden: the caller reads eng.act["x"] afterwards, so the engine has to know BEFORE it runs that the last
+        # layer's token rows are wanted (otherwise it computes that layer's CLS rows only: ViTEngine.cls_tail)
+        loss, logits, model._kept_hidden, _ = eng.forward(x, labels, training=training, need_grad=True,
+                                                          output_hidden_states=keep_hidden)
         ctx.model = model
         ctx.gen = eng._gen
         ctx.need_dx = bool(x.requires_grad)  # a trainable input preprocessor in front of the ViT
@@ -93,7 +96,7 @@ class _ViTFunction(torch.autograd.Function):
                 grads.append(None)  # the pooler output is never used (specvit.py:78): no gradient, as in the reference
             else:
                 grads.append(eng.g(name))
-        return (None, dx, None, None, *grads)
+        return (None, dx, None, None, None, *grads)
 
 
 class MyViT(nn.Module):
@@ -110,6 +113,7 @@ class MyViT(nn.Module):
             raise ValueError(f"Unsupported task_type '{self.task_type}'")  # specvit.py:55
         self.preprocessor = preprocessor  # specvit.py:43, 72-73: applied to pixel_values before the ViT
         self.engine = ViTEngine(config, loss_name=loss_name)
+        self._kept_hidden = None
         self._loss_name = self.engine.loss_name
         self._model_name = build_model_name(config, model_name, full_config=full_config)
         self._build_tree()
@@ -198,8 +202,9 @@ class MyViT(nn.Module):
         if want_grad:
             # the loss stays differentiable whatever else is asked for (as in the reference); hidden states / attention maps
             # are read back from the activations that forward kept (maps: the probabilities before dropout)
-            loss, logits = _ViTFunction.apply(self, pixel_values, labels, training, *self._param_list)
-            hs = [t.clone() for t in eng.act["x"]] if output_hidden_states else None
+            loss, logits = _ViTFunction.apply(self, pixel_values, labels, training, bool(output_hidden_states),
+                                              *self._param_list)
+            hs, self._kept_hidden = self._kept_hidden, None  # copies of eng.act["x"], or None when not asked for
             atts = eng.saved_attentions() if output_attentions else None
             if hooked:
                 B, T, D = pixel_values.shape[0], self.config.seq_len, self.config.hidden_size
