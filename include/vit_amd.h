@@ -318,4 +318,9 @@ int vit_adamw_step(vit_handle h, float* p, const float* g, float* m, float* v, v
 #ifdef __cplusplus
 }
 #endif
+
+/* Covariance statistics of the training spectra (the file behind `warmup.cov_path`): vit_cov_accumulate, vit_cov_mean_finish,
+ * vit_cov_finish.  Set-up time entry points, outside the training step: declared in their own header, part of this ABI. */
+#include "vit_amd_cov.h"
+
 #endif /* VIT_AMD_H_ */

@@ -115,6 +115,19 @@ class DataSource:
         return self.dm.test_dataloader()
 
 
+def ensure_cov_stats(args, config) -> bool:
+    """`warmup.cov_compute: true` (off by default): when `warmup.cov_path` names a missing file, compute the covariance
+    statistics of the training split on the GPU and save them there before the module is constructed -- the reference's
+    load_or_compute_covariance (src/prepca/preprocessor_utils.py:478-531).  Without the key a missing file raises
+    FileNotFoundError in get_model as before; with more than one rank it is an error that names `launch.sh cov`."""
+    from scripts.cov import chunk_rows_of, training_flux
+    from vit_amd.covstats import ensure_cov_file
+
+    world = max(int(os.environ.get("WORLD_SIZE", "1") or 1), int(args.gpu or 1))
+    return ensure_cov_file(config, lambda: training_flux(config, getattr(args, "synthetic", None)), world_size=world,
+                           chunk_rows=chunk_rows_of(config))
+
+
 def build(args, for_test=False):
     seed_everything(args.seed)
     config = load_config(args.config)
@@ -124,6 +137,7 @@ def build(args, for_test=False):
     train["gpus"] = args.gpu
     train["debug"] = args.debug
     train["save"] = False if for_test else bool(getattr(args, "save", False))  # pure evaluation never saves (test.py:41)
+    ensure_cov_stats(args, config)
     module = ViTLModule(config=config)
     return config, module, DataSource(args, config, module)
 

@@ -86,6 +86,9 @@ _PROTOS = {
     "vit_embed_finish_bwd": [_P, _P, _P, _I, _P, _P, _I, _I, _I, _F, _U64, _U64, _I, _P],
     "vit_dropout_bwd_cast": [_P, _P, _P, _I, _I, _I, _F, _U64, _U64, _P],
     "vit_colsum": [_P, _P, _I, _I64, _P, _I, _I, _I, _P],
+    "vit_cov_accumulate": [_P, _P, _I64, _P, _P, _I, _I, _P],
+    "vit_cov_finish": [_P, _P, _P, _I, _I64, _P],
+    "vit_cov_mean_finish": [_P, _P, _I, _I64, _P],
     "vit_cast_f32_bf16": [_P, _P, _P, _I64, _P],
     "vit_cast_bf16_f32": [_P, _P, _P, _I64, _F, _P],
     "vit_head_loss_fwd": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
@@ -101,10 +104,21 @@ _lock = threading.Lock()
 
 
 def declared_symbols(header_path: str = HEADER_PATH):
-    """Every function the C header declares (used by the CPU test that checks the library exports them all)."""
-    text = open(header_path).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(vit_[a-z0-9_]+)\s*\(", text)))
+    """Every function the C header declares, the headers it includes from its own directory (vit_amd_cov.h) included (used by
+    the CPU test that checks the library exports them all)."""
+    seen, names, todo = set(), set(), [os.path.abspath(header_path)]
+    while todo:
+        path = todo.pop()
+        if path in seen:
+            continue
+        seen.add(path)
+        text = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
+        names.update(re.findall(r"\b(vit_[a-z0-9_]+)\s*\(", text))
+        for inc in re.findall(r'#include\s+"([^"]+)"', text):
+            sub = os.path.join(os.path.dirname(path), inc)
+            if os.path.exists(sub):
+                todo.append(sub)
+    return sorted(names)
 
 
 def load():

@@ -410,6 +410,48 @@ def colsum(a, out=None, accumulate: bool = False):
     return out
 
 
+# ------------------------------------------------------------------------------------------------ covariance statistics
+COV_WORKSPACE_BYTES = 4096 * 128 * 128 * 4  # upper bound of vit_cov_accumulate's slabs: slices x tiles < 2048 + 2048 tiles
+
+
+def cov_accumulate(x, mean, acc, *, rows: Optional[int] = None, cols: Optional[int] = None):
+    """acc[L, L] += (x - mean)^T (x - mean) over x's rows, upper 128 x 128 tiles only (vit_cov_accumulate).  x: f32 [n, >= L]
+    with unit column stride, used in place through its row stride; mean: f32 with at least L elements."""
+    h = _h(x)
+    if x.dtype != torch.float32 or x.dim() != 2 or x.stride(1) != 1:
+        raise _cabi.VitError("cov_accumulate: x must be a 2-D f32 tensor with unit column stride")
+    _chk(mean, torch.float32, "cov_accumulate mean")
+    _chk(acc, torch.float32, "cov_accumulate acc")
+    n = x.shape[0] if rows is None else rows
+    L = x.shape[1] if cols is None else cols
+    if n > x.shape[0] or L > x.shape[1] or mean.numel() < L or tuple(acc.shape) != (L, L):
+        raise _cabi.VitError(f"cov_accumulate: x {tuple(x.shape)}, mean {mean.numel()}, acc {tuple(acc.shape)} do not fit n={n} L={L}")
+    h.ensure_workspace(COV_WORKSPACE_BYTES)
+    check(h.lib.vit_cov_accumulate(h.h, x.data_ptr(), x.stride(0) if n > 1 else max(L, x.stride(0)), mean.data_ptr(),
+                                   acc.data_ptr(), n, L, _stream(x)), "vit_cov_accumulate")
+    return acc
+
+
+def cov_mean_finish(colsum, n_total: int, cols: Optional[int] = None):
+    """colsum[:L] /= n_total in place (vit_cov_mean_finish): column sums -> the mean."""
+    _chk(colsum, torch.float32, "cov_mean_finish colsum")
+    h = _h(colsum)
+    check(h.lib.vit_cov_mean_finish(h.h, colsum.data_ptr(), colsum.numel() if cols is None else cols, int(n_total),
+                                    _stream(colsum)), "vit_cov_mean_finish")
+    return colsum
+
+
+def cov_finish(acc, n_total: int, out=None):
+    """cov = acc / (n_total - 1), lower triangle mirrored from the upper: bitwise symmetric (vit_cov_finish)."""
+    _chk(acc, torch.float32, "cov_finish acc")
+    h = _h(acc)
+    L = acc.shape[0]
+    out = out if out is not None else torch.empty((L, L), dtype=torch.float32, device=acc.device)
+    _chk(out, torch.float32, "cov_finish out")
+    check(h.lib.vit_cov_finish(h.h, acc.data_ptr(), out.data_ptr(), L, int(n_total), _stream(acc)), "vit_cov_finish")
+    return out
+
+
 def cast_f32_bf16(src, out=None):
     _chk(src, torch.float32, "cast_f32_bf16 src")
     h = _h(src)
