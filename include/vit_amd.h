@@ -65,7 +65,23 @@ int vit_set_option(const char* name, int value);
  * that two engines of one process (training + evaluation, an engine's second-stream handle) do not depend on the order
  * in which they were configured.  "reserve_cus": -1 (default) = follow the process-wide value above, 0 .. 128 = this handle's
  * own.  The remaining vit_set_option options select kernel forms and stay process-wide.
- * Reference: none (Lightning's 'ddp' overlaps NCCL with kernels that do not own whole SMs, src/hardware_utils.py:86-95). */
+ * Reference: none (Lightning's 'ddp' overlaps NCCL with kernels that do not own whole SMs, src/hardware_utils.py:86-95).
+ * "grad_accumulate": 0 (default) | 1.  While it is 1, every PARAMETER-GRADIENT output of a call through this handle stores
+ * old + new where it stores new at 0: gradient accumulation over micro-batches, in place in the caller's gradient buffer
+ * (Lightning's accumulate_grad_batches; autograd's `p.grad +=` for a buffer the kernels own).  `new` is bit for bit the value
+ * overwrite mode stores, and the add is ONE f32 add in the producer's final write or reduce stage: no float atomics, no second
+ * buffer, no extra pass over a weight matrix, deterministic (a second run from the same old values is bit-identical).
+ * The outputs it covers: vit_gemm's colsum_out always, and its C when the product has the weight-gradient form dW = dY^T X
+ * (a_trans != 0 and an f32 C; OR-ed with vit_gemm_desc.accumulate -- forward products and the dX products of the fp32 path
+ * also write an f32 C and are never touched); vit_linear_bwd_dw / _dw_rows' dW; vit_colsum_rows' out; dgamma / dbeta / dbias
+ * of the three vit_layernorm_bwd* forms; vit_attention_bwd's dqkv_colsum; vit_embed_finish_bwd's dcls / dpos and
+ * vit_head_loss_bwd's dW / db (OR-ed with their `accumulate` argument).  vit_colsum keeps its own `accumulate` argument alone.
+ * Activation gradients (dx, dyn, dqkv, dlast_hidden, ...) are always overwritten.
+ * Where each add sits: split-K products -- in the slab reduction (slab 0 + slab 1 + ... in slice order, times alpha, THEN
+ * + old C); single-slice products -- the epilogue's residual port reads old C; vit_linear_bwd_dw_rows -- the final store of
+ * the slice total; every vector output -- the last stage of the partial-row reducer.  A vit_gemm whose C accumulates AND that
+ * carries colsum_out (two parameter gradients from one descriptor; no training step issues it) runs the product into a
+ * scratch matrix taken from the end of the workspace (M * N * 4 more bytes), sums its columns and adds it into C. */
 int vit_handle_set_option(vit_handle h, const char* name, int value);
 
 /* Per-step state in device memory, for a training step captured as a hipGraph (HIP streams and graphs instead of a tracing
@@ -116,7 +132,9 @@ typedef struct vit_gemm_desc {
   const float* residual; int64_t ldres;   /* f32, indexed by out_row */
   int rows_per_batch, out_batch_rows, out_row_offset;
   int split_k;             /* 0/1 = off; >1 = that many K slices; -1 = choose */
-  int accumulate;          /* split_k path: C += result instead of C = result */
+  int accumulate;          /* C (f32) += result instead of C = result: in the split-K slab reduction (slabs summed in slice
+                            * order, scaled by alpha, old C added last), else through the epilogue's residual port (no residual
+                            * then); OR-ed with the handle's "grad_accumulate" for products of the weight-gradient form */
   float* colsum_out;       /* optional f32 [N]: column sums of C as stored (a Linear's bias gradient when C is the gradient
                             * of its output); summed inside the epilogue where the kernel can, else by a vit_colsum pass */
   /* Rotary position embedding of the fused QKV projection's output (src/models/vit_with_rope.py:58-60, rope.py:116-131):
@@ -158,8 +176,10 @@ int vit_linear_bwd_dw(vit_handle h, const void* dy, const void* x, float* dW, in
  * dW[N, K] (f32, dense) = sum_b dy[b]^T x[b].  Where the product over the full tensors would run the ping-pong core with
  * split-K, the B terms are summed in that product's order (K slices, rows within a slice, then the slices), so with
  * row_stride >= 64 the result is bit for bit the full product's (zero terms leave an f32 sum unchanged); any other shape runs
- * the compact product through vit_gemm.  vit_colsum_rows: out[cols] = column sums of a ([rows, cols], ld = lda), likewise in
- * the order of the column sums that ride in the ping-pong epilogue of the product that would write the full tensor. */
+ * the compact product through vit_gemm -- except f32 operands (precision '32'), which run the full product's own kernel, split-K
+ * plan and MFMA sequence with the absent rows read as zero: bit for bit the full product wherever rows x max(ldy, ldx) x 4 bytes stay below 2 GiB (beyond that: the compact product).  vit_colsum_rows: out[cols] = column sums of a ([rows, cols], ld = lda), likewise in
+ * the order of the column sums that ride in the ping-pong epilogue of the product that would write the full tensor (f32: in
+ * the order of vit_colsum over the full tensor). */
 int vit_linear_bwd_dw_rows(vit_handle h, const void* dy, int64_t ldy, const void* x, int64_t ldx, int dtype, float* dW,
                            int rows, int N, int K, int64_t row_stride, int64_t full_rows, vit_stream stream);
 int vit_colsum_rows(vit_handle h, const void* a, int a_dtype, int64_t lda, float* out, int rows, int cols, int64_t row_stride,
@@ -185,7 +205,8 @@ int vit_layernorm_fwd_residual_rows(vit_handle h, const float* x, int64_t x_row_
                                     float* xsum, const float* gamma, const float* beta, void* y, int y_dtype, float* mean,
                                     float* rstd, int rows, int D, float eps, vit_stream stream);
 /* dx[rows,D] (f32) = LN'(dy) (+ dres if not NULL: the residual branch's gradient); dgamma/dbeta (f32 [D]) are
- * reduced deterministically through the workspace; accumulate!=0 adds into them. dy: dy_dtype [rows, D]. */
+ * reduced deterministically through the workspace; the handle's "grad_accumulate" option (vit_handle_set_option) adds into
+ * them -- and into dbias of the fused / rows forms below -- instead of overwriting. dy: dy_dtype [rows, D]. */
 int vit_layernorm_bwd(vit_handle h, const void* dy, int dy_dtype, const float* x, const float* gamma,
                       const float* mean, const float* rstd, const float* dres, float* dx, float* dgamma,
                       float* dbeta, int rows, int D, vit_stream stream);

@@ -171,6 +171,7 @@ class Handle:
         h = C.c_void_p()
         check(self.lib.vit_create(C.byref(h), device_index), "vit_create")
         self.h = h
+        self.options = {}  # name -> last value given to set_option (what the wrappers size workspaces by)
         self._ws = None
         self.set_workspace(workspace_bytes)
 
@@ -182,8 +183,10 @@ class Handle:
         self.workspace_bytes = nbytes
 
     def set_option(self, name: str, value: int):
-        """Launch geometry of the calls made through THIS handle (vit_handle_set_option): 'reserve_cus'."""
+        """Per-handle options (vit_handle_set_option): 'reserve_cus' (launch geometry of the calls made through THIS handle),
+        'grad_accumulate' (parameter-gradient outputs store old + new)."""
         check(self.lib.vit_handle_set_option(self.h, name.encode(), int(value)), f"vit_handle_set_option({name})")
+        self.options[name] = int(value)
 
     def ensure_workspace(self, nbytes: int):
         if nbytes > self.workspace_bytes:

@@ -11,9 +11,11 @@ struct vit_ctx {
   int device;
   void* ws;
   size_t ws_bytes;
+  size_t ws_hidden;        // bytes at the end of the workspace lent out by ctx_reserve_tail (not counted in ws_bytes)
   const void* step_state;  // device memory: vit::StepState, or NULL (vit_step_state_bind)
   int num_cus;             // compute units of the device (read once in vit_create): grid size of the persistent kernels
   int reserve_cus;         // vit_handle_set_option("reserve_cus"): -1 = the process default (vit_set_option), else this handle's own
+  int grad_accumulate;     // vit_handle_set_option("grad_accumulate"): parameter-gradient outputs store old + new
 };
 
 namespace vit {
@@ -53,6 +55,24 @@ int ctx_num_cus(vit_handle h) {
   return std::max(1, dflt - g_reserve_cus);
 }
 
+int ctx_grad_accumulate(vit_handle h) { return h ? h->grad_accumulate : 0; }
+
+// Take at least `bytes` off the END of the handle's workspace for the caller (256-byte aligned start) and hide them from
+// ctx_workspace until ctx_release_tail gives them back: a scratch region that the kernels launched in between (which size
+// their own partials from the front of the workspace) cannot overlap.  Host-side bookkeeping only; NULL when the workspace
+// is too small.  One reservation at a time.
+void* ctx_reserve_tail(vit_handle h, size_t bytes) {
+  if (!h || !h->ws || h->ws_hidden || h->ws_bytes < bytes) return nullptr;
+  const size_t keep = (h->ws_bytes - bytes) & ~(size_t)255;
+  h->ws_hidden = h->ws_bytes - keep;
+  h->ws_bytes = keep;
+  return (char*)h->ws + keep;
+}
+void ctx_release_tail(vit_handle h) {
+  h->ws_bytes += h->ws_hidden;
+  h->ws_hidden = 0;
+}
+
 void* ctx_workspace(vit_handle h, size_t* bytes) {
   if (!h) {
     *bytes = 0;
@@ -83,9 +103,11 @@ int vit_create(vit_handle* out, int device) {
   c->device = device;
   c->ws = nullptr;
   c->ws_bytes = 0;
+  c->ws_hidden = 0;
   c->step_state = nullptr;
   c->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
   c->reserve_cus = -1;
+  c->grad_accumulate = 0;
   *out = c;
   return VIT_OK;
 }
@@ -134,7 +156,12 @@ int vit_handle_set_option(vit_handle h, const char* name, int value) {
     h->reserve_cus = value;
     return VIT_OK;
   }
-  vit::set_error("vit_handle_set_option: '%s' is not a per-handle option (only launch geometry is: reserve_cus)", name);
+  if (strcmp(name, "grad_accumulate") == 0) {
+    VIT_CHECK(value == 0 || value == 1, VIT_ERR_ARG, "vit_handle_set_option: grad_accumulate takes 0 or 1");
+    h->grad_accumulate = value;
+    return VIT_OK;
+  }
+  vit::set_error("vit_handle_set_option: '%s' is not a per-handle option (reserve_cus, grad_accumulate)", name);
   return VIT_ERR_ARG;
 }
 
@@ -150,6 +177,7 @@ int vit_set_workspace(vit_handle h, void* ws, size_t bytes) {
   VIT_CHECK(((uintptr_t)ws & 255) == 0, VIT_ERR_ARG, "vit_set_workspace: workspace must be 256-byte aligned");
   h->ws = ws;
   h->ws_bytes = bytes;
+  h->ws_hidden = 0;
   return VIT_OK;
 }
 

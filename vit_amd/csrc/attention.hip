@@ -114,11 +114,11 @@ int vit_attention_bwd(vit_handle h, const void* qkv, const void* ctx, const void
     rc = pl.form == ATTN_PIPE ? launch_attn_pipe(a, pl, st)
          : pl.form == ATTN_RESIDENT ? launch_attn_resident(a, pl, st) : launch_attn_tiled(a, pl, st);
     if (rc == VIT_OK && a.csum_part)
-      return launch_reduce_partials(a.csum_part, pl.csum_rows, D3, dqkv_colsum, D3, dqkv_colsum, 0, st);
+      return launch_reduce_partials(a.csum_part, pl.csum_rows, D3, dqkv_colsum, D3, dqkv_colsum, ctx_grad_accumulate(h), st);
   }
   // no kernel partials (f32, tiled form, workspace too small): column sums over the stored dqkv
   if (rc != VIT_OK || !dqkv_colsum) return rc;
-  return vit_colsum(h, dqkv, io_dtype, D3, dqkv_colsum, B * T, D3, 0, stream);
+  return vit_colsum(h, dqkv, io_dtype, D3, dqkv_colsum, B * T, D3, ctx_grad_accumulate(h), stream);
 }
 
 int vit_attention_probs(vit_handle h, const void* qkv, float* probs, int io_dtype, int B, int H, int T, int dh,

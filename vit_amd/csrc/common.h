@@ -292,6 +292,9 @@ __device__ __forceinline__ void lds_dma4_s(const void* sbase /* wave-uniform */,
 struct StepState { unsigned key0, key1; float lr, bc1, rsqrt_bc2; unsigned step; };
 const StepState* ctx_step_state(vit_handle h);
 int ctx_num_cus(vit_handle h);  // compute units of the handle's device (api.hip)
+// vit_handle_set_option("grad_accumulate"): non-zero = every parameter-gradient output of a call through this handle stores
+// old + new (new = what overwrite mode stores, bit for bit; one f32 add in the producer's final write or reduce stage)
+int ctx_grad_accumulate(vit_handle h);
 static inline DropCfg make_drop_h(vit_handle h, float p, uint64_t seed, uint64_t site) {
   DropCfg d = make_drop(p, seed, site);
   const StepState* s = h ? ctx_step_state(h) : nullptr;

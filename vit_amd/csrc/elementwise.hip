@@ -8,6 +8,8 @@
 namespace vit {
 
 void* ctx_workspace(vit_handle h, size_t* bytes);
+int colsum_strided(vit_handle h, const void* a, int a_dtype, int64_t lda, float* out, int rows, int cols, int64_t row_stride,
+                   int held, int accumulate, hipStream_t st);
 
 static inline int grid_for(long n, int block = 256, int cap = 4096) {
   return (int)std::max<long>(1, std::min<long>((n + block - 1) / block, cap));
@@ -128,16 +130,23 @@ __global__ void dropout_bwd_cast_kernel(const float* __restrict__ dx, void* __re
 }
 
 // ------------------------------------------------------------------------------------------ column sums
-// stage 1: block (64 x 4): 64 lanes x 4 columns each = 256 columns, 4 row-lanes; grid.y row chunks
+// stage 1: block (64 x 4): 64 lanes x 4 columns each = 256 columns, 4 row-lanes; grid.y row chunks.
+// rs > 1: of the `rows` rows only the rows r with r % rs == 0 exist, held at row r / rs of a; the others are skipped, which
+// leaves each f32 sum what adding their exact zeros leaves it (vit_colsum_rows: the full tensor's sums in the full pass's order)
 template <int BF16>
 __global__ __launch_bounds__(256) void colsum_stage1_kernel(const void* __restrict__ a, long lda, float* __restrict__ part,
-                                                            int rows, int cols) {
+                                                            int rows, int cols, int rs, int held) {
   __shared__ f32x4 red[4][64];
   const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
   const int c = (blockIdx.x * 64 + tx) << 2;
   f32x4 acc = {0.f, 0.f, 0.f, 0.f};
   if (c < cols) {
-    for (int r = blockIdx.y * 4 + ty; r < rows; r += gridDim.y * 4) {
+    for (int lr = blockIdx.y * 4 + ty; lr < rows; lr += gridDim.y * 4) {
+      int r = lr;
+      if (rs > 1) {
+        r = lr / rs;
+        if (r * rs != lr || r >= held) continue;  // `held` compact rows exist; the full tensor's pad rows beyond them are zeros
+      }
       if (BF16) {
         bf16x4 t = *(const bf16x4*)((const short*)a + (long)r * lda + c);
         acc += (f32x4){bf2f(t[0]), bf2f(t[1]), bf2f(t[2]), bf2f(t[3])};
@@ -621,6 +630,7 @@ int vit_embed_finish_bwd(vit_handle h, const float* dtokens, void* dpatch_out, i
   const size_t need = (size_t)ny * T * D * sizeof(float);
   VIT_CHECK(part && wsb >= need, VIT_ERR_WORKSPACE, "vit_embed_finish_bwd: needs %zu workspace bytes, have %zu", need, wsb);
   hipStream_t st = (hipStream_t)stream;
+  accumulate = accumulate || ctx_grad_accumulate(h);
   const dim3 grid(cdiv((long)T * (D / 4), 256), ny);
   if (dpatch_dtype == VIT_BF16)
     hipLaunchKernelGGL(embed_finish_bwd_kernel<1>, grid, dim3(256), 0, st, dtokens, dpatch_out, part, B, T, D,
@@ -653,6 +663,16 @@ int vit_dropout_bwd_cast(vit_handle h, const float* dx, void* dy, int dy_dtype, 
 
 int vit_colsum(vit_handle h, const void* a, int a_dtype, int64_t lda, float* out, int rows, int cols, int accumulate,
                vit_stream stream) {
+  return vit::colsum_strided(h, a, a_dtype, lda, out, rows, cols, 1, rows, accumulate, (hipStream_t)stream);
+}
+
+}  // extern "C"
+
+namespace vit {
+// vit_colsum over `rows` rows of which, with row_stride s > 1, only the rows r = j * s, j < held, exist (compactly, at row j of a)
+int colsum_strided(vit_handle h, const void* a, int a_dtype, int64_t lda, float* out, int rows, int cols, int64_t row_stride,
+                   int held, int accumulate, hipStream_t st) {
+  const int rs = (int)row_stride;
   VIT_CHECK(a && out, VIT_ERR_ARG, "vit_colsum: null pointer");
   VIT_CHECK(rows > 0 && cols > 0 && (cols % 4) == 0 && (lda % 4) == 0 && lda >= cols, VIT_ERR_ARG,
             "vit_colsum: rows=%d cols=%d lda=%ld", rows, cols, (long)lda);
@@ -662,14 +682,16 @@ int vit_colsum(vit_handle h, const void* a, int a_dtype, int64_t lda, float* out
   float* part = (float*)ctx_workspace(h, &wsb);
   const size_t need = (size_t)gy * cols * sizeof(float);
   VIT_CHECK(part && wsb >= need, VIT_ERR_WORKSPACE, "vit_colsum: needs %zu workspace bytes, have %zu", need, wsb);
-  hipStream_t st = (hipStream_t)stream;
   if (a_dtype == VIT_BF16)
-    hipLaunchKernelGGL(colsum_stage1_kernel<1>, dim3(gx, gy), dim3(256), 0, st, a, (long)lda, part, rows, cols);
+    hipLaunchKernelGGL(colsum_stage1_kernel<1>, dim3(gx, gy), dim3(256), 0, st, a, (long)lda, part, rows, cols, rs, held);
   else
-    hipLaunchKernelGGL(colsum_stage1_kernel<0>, dim3(gx, gy), dim3(256), 0, st, a, (long)lda, part, rows, cols);
+    hipLaunchKernelGGL(colsum_stage1_kernel<0>, dim3(gx, gy), dim3(256), 0, st, a, (long)lda, part, rows, cols, rs, held);
   VIT_LAUNCH_CHECK();
   return launch_reduce_partials(part, gy, cols, out, cols, out, accumulate, st);
 }
+}  // namespace vit
+
+extern "C" {
 
 int vit_cast_f32_bf16(vit_handle h, const float* src, void* dst, int64_t n, vit_stream stream) {
   (void)h;
@@ -725,7 +747,7 @@ int vit_head_loss_bwd(vit_handle h, const float* last_hidden, const float* W, co
                      D, C, loss_kind);
   VIT_LAUNCH_CHECK();
   hipLaunchKernelGGL(head_bwd_params_kernel, dim3(cdiv((long)C * D, 256)), dim3(256), 0, st, last_hidden, dlog, dW, db,
-                     B, T, D, C, accumulate);
+                     B, T, D, C, accumulate || ctx_grad_accumulate(h));
   VIT_LAUNCH_CHECK();
   return VIT_OK;
 }

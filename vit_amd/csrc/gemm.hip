@@ -44,6 +44,11 @@ struct GemmArgs {
   DropCfg drop;
   int rpb, orb, roff;
   int drs;  // dropout key row = out_row * drs (vit_gemm_desc::drop_row_stride; 1 = the row itself)
+  // x3 kernel, both operands transposed (dW = dY^T X): krs > 1 = of the K rows only the rows k with k % krs == 0 exist, held at
+  // row k / krs of A and B (krs_rows of them); every other row reads as zero.  The product then IS the one over the full
+  // tensors whose other rows are exact zeros -- same tiles, same K slices, same MFMA sequence, hence the same bits
+  // (vit_linear_bwd_dw_rows in precision '32').  0 = off.
+  int krs, krs_rows;
 };
 
 __device__ __forceinline__ int tr_swz(int k) { return ((k & 3) | (((k >> 3) & 1) << 2)) << 2; }
@@ -345,9 +350,12 @@ __global__ __launch_bounds__(NTHR, 2) void gemm_f32x3_kernel(GemmArgs p) {
   const char* Ab;
   const char* Bb;
   unsigned long long a_bytes, b_bytes;
+  const bool strided = A_T == 1 && B_T == 1 && p.krs > 1;  // compact K rows (GemmArgs::krs): addressed from the operands' first row
   if (A_T == 0) { Ab = p.A + ((long)batch * p.a_bs + (long)m0 * p.lda + k_begin) * 4; a_bytes = (unsigned long long)(p.M - m0) * p.lda * 4; }
+  else if (strided) { Ab = p.A; a_bytes = (unsigned long long)p.krs_rows * p.lda * 4; }
   else { Ab = p.A + ((long)batch * p.a_bs + (long)k_begin * p.lda + m0) * 4; a_bytes = (unsigned long long)klen * p.lda * 4; }
   if (B_T == 0) { Bb = p.B + ((long)batch * p.b_bs + (long)n0 * p.ldb + k_begin) * 4; b_bytes = (unsigned long long)(p.N - n0) * p.ldb * 4; }
+  else if (strided) { Bb = p.B; b_bytes = (unsigned long long)p.krs_rows * p.ldb * 4; }
   else { Bb = p.B + ((long)batch * p.b_bs + (long)k_begin * p.ldb + n0) * 4; b_bytes = (unsigned long long)klen * p.ldb * 4; }
   const __amdgpu_buffer_rsrc_t ra = make_rsrc(Ab, a_bytes);
   const __amdgpu_buffer_rsrc_t rb = make_rsrc(Bb, b_bytes);
@@ -371,12 +379,22 @@ __global__ __launch_bounds__(NTHR, 2) void gemm_f32x3_kernel(GemmArgs p) {
   auto issue = [&](int kt) {
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
-      const bool ok = (A_T == 0) ? (kt * XBK + kcA[i] < klen) : okA[i];
-      const unsigned vo = ok ? voffA[i] + (unsigned)kt * a_step : OOB;
+      bool ok = (A_T == 0) ? (kt * XBK + kcA[i] < klen) : okA[i];
+      unsigned vo = ok ? voffA[i] + (unsigned)kt * a_step : OOB;
+      bool okb = (B_T == 0) ? (kt * XBK + kcB[i] < klen) : okB[i];
+      unsigned vb = okb ? voffB[i] + (unsigned)kt * b_step : OOB;
+      if (strided) {  // K row k lives at row k / krs iff k is a multiple of krs and below k_end; host: krs_rows * ld * 4 < 2^31
+        const int q = tid + NTHR * i, c16 = q & 15;
+        const int k = k_begin + kt * XBK + (q >> 4);
+        const int ph = k / p.krs;
+        const bool here = k < k_end && ph * p.krs == k && ph < p.krs_rows;
+        ok = ok && here;
+        okb = okb && here;
+        vo = ok ? (unsigned)ph * (unsigned)(p.lda * 4) + (unsigned)((m0 + c16 * 8) * 4) : OOB;
+        vb = okb ? (unsigned)ph * (unsigned)(p.ldb * 4) + (unsigned)((n0 + c16 * 8) * 4) : OOB;
+      }
       sa[i][0] = __builtin_amdgcn_raw_buffer_load_b128(ra, vo, 0, 0);
       sa[i][1] = __builtin_amdgcn_raw_buffer_load_b128(ra, ok ? vo + 16 : OOB, 0, 0);
-      const bool okb = (B_T == 0) ? (kt * XBK + kcB[i] < klen) : okB[i];
-      const unsigned vb = okb ? voffB[i] + (unsigned)kt * b_step : OOB;
       sb[i][0] = __builtin_amdgcn_raw_buffer_load_b128(rb, vb, 0, 0);
       sb[i][1] = __builtin_amdgcn_raw_buffer_load_b128(rb, okb ? vb + 16 : OOB, 0, 0);
     }
@@ -447,7 +465,9 @@ __global__ __launch_bounds__(NTHR, 2) void gemm_f32x3_kernel(GemmArgs p) {
   generic_epilogue<1>(acc, p, m0, n0, wm, wn, l15, lg, z, batch);
 }
 
-// C (f32) (+)= alpha * sum over split slabs; one float4 per thread
+// C (f32) (+)= alpha * sum over split slabs; one float4 per thread.  Summation order: slab 0 + slab 1 + ... in slice order, the
+// sum scaled by alpha, and with `accumulate` the old C added LAST: old + new, where new is bit for bit what overwrite mode
+// stores (the one f32 add of gradient accumulation sits here, in the pass that writes C anyway).
 __global__ void splitk_reduce_kernel(const float* __restrict__ slab, float* __restrict__ C, long ldc, int M, int N,
                                      int splits, float alpha, int accumulate) {
   const long nvec = (long)M * (N >> 2);
@@ -465,7 +485,20 @@ __global__ void splitk_reduce_kernel(const float* __restrict__ slab, float* __re
   }
 }
 
+// C[M, N] (ld = ldc) += src[M, N] (dense): the second half of gemm_accumulate_with_colsum below
+__global__ void add_into_kernel(float* __restrict__ C, long ldc, const float* __restrict__ src, int M, int N) {
+  const long nvec = (long)M * (N >> 2);
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < nvec; i += (long)gridDim.x * blockDim.x) {
+    const long m = i / (N >> 2);
+    const int n = (int)(i - m * (N >> 2)) << 2;
+    float* c = C + m * ldc + n;
+    *(f32x4*)c = *(const f32x4*)c + *(const f32x4*)(src + m * N + n);
+  }
+}
+
 void* ctx_workspace(vit_handle h, size_t* bytes);
+void* ctx_reserve_tail(vit_handle h, size_t bytes);   // api.hip
+void ctx_release_tail(vit_handle h);
 int gemm2_try_launch(vit_handle h, const vit_gemm_desc* d, hipStream_t st, int* rc);  // gemm2.hip
 
 int launch_splitk_reduce(const float* slab, float* C, long ldc, int M, int N, int splits, float alpha, int accumulate,
@@ -481,11 +514,49 @@ static bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 thread_local int g_colsum_fused = 0;  // set by a core whose epilogue produced d->colsum_out itself
 thread_local int g_rope_fused = 0;    // set by a core whose epilogue applied d->rope_* itself
-static int gemm_launch_core(vit_handle h, const vit_gemm_desc* d, hipStream_t st);
+// compact K rows of an x3 weight-gradient product (GemmArgs::krs / krs_rows); stride 0 = the descriptor's rows as they are
+struct KRows { int stride, rows; };
+int gemm_launch(vit_handle h, const vit_gemm_desc* d, hipStream_t st, int k_row_stride = 0, int k_rows = 0);
+static int gemm_launch_core(vit_handle h, const vit_gemm_desc* d, hipStream_t st, KRows kr = {0, 0});
 
-int gemm_launch(vit_handle h, const vit_gemm_desc* d, hipStream_t st) {
+// grad_accumulate with BOTH outputs of one descriptor being parameter gradients (an f32 C that accumulates and colsum_out):
+// the column sums are those of the NEW product, which an accumulated C no longer holds.  The product goes to a scratch matrix
+// at the end of the workspace in overwrite mode (the same kernels as a plain call: `new` bit for bit), its column sums are
+// added into colsum_out, and one pass adds it into C.  The engine never issues this combination (its weight-gradient products
+// carry no column sums), so no weight matrix of a training step takes the extra pass.
+static int gemm_accumulate_with_colsum(vit_handle h, const vit_gemm_desc* d, hipStream_t st) {
+  VIT_CHECK(d->c_dtype == VIT_F32 && d->rows_per_batch == 0 && !d->rope_cos && !d->residual, VIT_ERR_ARG,
+            "vit_gemm: accumulate with colsum_out needs an f32 C and no row map, rope or residual");
+  const size_t bytes = (((size_t)d->M * d->N * sizeof(float)) + 255) & ~(size_t)255;
+  float* scr = (float*)ctx_reserve_tail(h, bytes);
+  VIT_CHECK(scr, VIT_ERR_WORKSPACE, "vit_gemm: accumulate with colsum_out needs %zu more workspace bytes", bytes);
+  vit_gemm_desc t = *d;
+  t.C = scr; t.ldc = d->N; t.accumulate = 0; t.colsum_out = nullptr;
+  int rc = gemm_launch_core(h, &t, st);
+  if (rc == VIT_OK) rc = vit_colsum(h, scr, VIT_F32, d->N, d->colsum_out, d->M, d->N, 1, (vit_stream)st);
+  ctx_release_tail(h);
+  if (rc != VIT_OK) return rc;
+  const long nvec = (long)d->M * (d->N / 4);
+  hipLaunchKernelGGL(add_into_kernel, dim3((int)std::min<long>((nvec + 255) / 256, 2048)), dim3(256), 0, st, (float*)d->C,
+                     (long)d->ldc, scr, d->M, d->N);
+  VIT_LAUNCH_CHECK();
+  return VIT_OK;
+}
+
+int gemm_launch(vit_handle h, const vit_gemm_desc* d, hipStream_t st, int k_row_stride, int k_rows) {
   g_colsum_fused = 0;
   g_rope_fused = 0;
+  // vit_handle_set_option("grad_accumulate"): colsum_out is always a parameter gradient (a bias gradient); C is one iff the
+  // product has the weight-gradient form dW = dY^T X (a_trans, f32 C) -- a forward product or a dX of the fp32 path also has
+  // an f32 C, and activation gradients never accumulate.  OR-ed with the descriptor's own `accumulate`.
+  const int accum = d ? ctx_grad_accumulate(h) : 0;
+  vit_gemm_desc dd;
+  if (accum && d->a_trans && d->c_dtype == VIT_F32 && !d->accumulate) {
+    dd = *d;
+    dd.accumulate = 1;
+    d = &dd;
+  }
+  if (accum && d->accumulate && d->colsum_out) return gemm_accumulate_with_colsum(h, d, st);
   if (d && d->rope_cos) {
     VIT_CHECK(d->rope_sin && d->rope_T > 0 && d->rope_dh >= 8 && (d->rope_dh % 8) == 0 && d->rope_cols > 0 &&
                   (d->rope_cols % (2 * d->rope_dh)) == 0 && d->rope_cols <= d->N && d->rows_per_batch == 0 && !d->colsum_out &&
@@ -494,16 +565,16 @@ int gemm_launch(vit_handle h, const vit_gemm_desc* d, hipStream_t st) {
                            "projection (a bias is fine) without dropout, row map, column sums, residual or split-K: the pass "
                            "behind a dropped-out product would rotate AFTER the dropout, which is not the reference's order");
   }
-  int rc = gemm_launch_core(h, d, st);
+  int rc = gemm_launch_core(h, d, st, KRows{k_row_stride, k_rows});
   if (rc == VIT_OK && d->rope_cos && !g_rope_fused)  // the core had no rotating epilogue for this shape: the separate pass
     rc = vit_rope_qk(h, d->C, d->c_dtype, d->rope_cos, d->rope_sin, d->M, d->rope_T, d->rope_cols / (2 * d->rope_dh), d->rope_dh,
                      d->ldc, 0, (vit_stream)st);
   if (rc != VIT_OK || !d->colsum_out || g_colsum_fused) return rc;
   VIT_CHECK(d->rows_per_batch == 0, VIT_ERR_ARG, "vit_gemm: colsum_out with a row map is not supported");
-  return vit_colsum(h, d->C, d->c_dtype, d->ldc, d->colsum_out, d->M, d->N, 0, (vit_stream)st);
+  return vit_colsum(h, d->C, d->c_dtype, d->ldc, d->colsum_out, d->M, d->N, accum, (vit_stream)st);
 }
 
-static int gemm_launch_core(vit_handle h, const vit_gemm_desc* d, hipStream_t st) {
+static int gemm_launch_core(vit_handle h, const vit_gemm_desc* d, hipStream_t st, KRows kr) {
   VIT_CHECK(d && d->A && d->B && d->C, VIT_ERR_ARG, "vit_gemm: null operand");
   VIT_CHECK(d->M > 0 && d->N > 0 && d->K > 0, VIT_ERR_ARG, "vit_gemm: empty problem M=%d N=%d K=%d", d->M, d->N, d->K);
   VIT_CHECK(d->ab_dtype == VIT_BF16 || d->ab_dtype == VIT_F32, VIT_ERR_ARG, "vit_gemm: bad ab_dtype");
@@ -532,6 +603,10 @@ static int gemm_launch_core(vit_handle h, const vit_gemm_desc* d, hipStream_t st
   VIT_CHECK(d->drop_row_stride >= 0, VIT_ERR_ARG, "vit_gemm: drop_row_stride=%d", d->drop_row_stride);
 
   if (d->dropout_p > 0.f) VIT_CHECK((d->N % 2) == 0, VIT_ERR_ARG, "vit_gemm: dropout needs an even N");
+  if (kr.stride > 1)  // checked before any core is chosen: only the x3 kernel reads compact K rows
+    VIT_CHECK(f32in && d->a_trans && d->b_trans && kr.rows > 0 &&
+                  (unsigned long long)kr.rows * (unsigned long long)std::max(d->lda, d->ldb) * 4 < 0x7FFFFFF0ull,
+              VIT_ERR_ARG, "vit_gemm: compact K rows need f32 operands, both transposed, below 2 GiB");
   if (!f32in) {
     int rc2 = VIT_OK;  // tile-aligned problems go to the LDS-DMA / persistent core
     if (gemm2_try_launch(h, d, st, &rc2)) return rc2;
@@ -581,6 +656,11 @@ static int gemm_launch_core(vit_handle h, const vit_gemm_desc* d, hipStream_t st
   if (a.drop.thr) VIT_CHECK((d->N % 2) == 0, VIT_ERR_ARG, "vit_gemm: dropout needs an even N");
   a.rpb = d->rows_per_batch; a.orb = d->out_batch_rows; a.roff = d->out_row_offset;
   a.drs = (a.drop.thr && d->drop_row_stride > 1) ? d->drop_row_stride : 1;
+  a.krs = a.krs_rows = 0;
+  if (kr.stride > 1) {
+    a.krs = kr.stride;
+    a.krs_rows = kr.rows;
+  }
 
   dim3 grid(a.tiles_m * a.tiles_n, splits), block(NTHR);
   const int v = d->a_trans * 2 + d->b_trans;

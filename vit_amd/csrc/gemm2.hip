@@ -873,7 +873,7 @@ int gemm2_try_launch(vit_handle h, const vit_gemm_desc* d, hipStream_t st, int* 
   if (epi5 == 8) g_rope_fused = 1;
   int r = launch_stag_cfg(a, d->a_trans, d->b_trans, epi5, grid, st);
   if (r == VIT_OK && a.colsum_part) {
-    r = launch_reduce_partials(a.colsum_part, a.tiles_m * 2, d->N, d->colsum_out, d->N, d->colsum_out, 0, st);
+    r = launch_reduce_partials(a.colsum_part, a.tiles_m * 2, d->N, d->colsum_out, d->N, d->colsum_out, ctx_grad_accumulate(h), st);
     g_colsum_fused = 1;
   }
   if (r == VIT_OK && splits > 1)
@@ -895,7 +895,7 @@ int gemm2_try_launch(vit_handle h, const vit_gemm_desc* d, hipStream_t st, int* 
 // work.  With s < 64 several rows share an MFMA and the result is the same sum in another rounding order.
 __global__ __launch_bounds__(256) void dw_rows_kernel(const short* __restrict__ dy, long ldy, const short* __restrict__ x,
                                                       long ldx, float* __restrict__ dW, long ldw, int B, int s, int kps,
-                                                      int splits) {
+                                                      int splits, int accumulate) {
   // 64 x 64 outputs per block, 32 x 32 (2 x 2 MFMA tiles) per wave.  One v_mfma_f32_16x16x32_bf16 per row and tile with the
   // row in k slot 0 and zeros in the other 31: the very accumulate step the full product takes for that row (the MFMA's
   // rounding of accumulator + product is not IEEE's in every case, so an fma would be off by an ulp once in ~20 000 elements).
@@ -976,8 +976,10 @@ __global__ __launch_bounds__(256) void dw_rows_kernel(const short* __restrict__ 
 #pragma unroll
     for (int j = 0; j < 2; ++j)
 #pragma unroll
-      for (int r = 0; r < 4; ++r)
-        dW[(long)(n0 + wn + i * 16 + 4 * lg + r) * ldw + k0 + wk + j * 16 + l15] = tot[i][j][r];
+      for (int r = 0; r < 4; ++r) {
+        float* o = dW + (long)(n0 + wn + i * 16 + 4 * lg + r) * ldw + k0 + wk + j * 16 + l15;
+        *o = accumulate ? *o + tot[i][j][r] : tot[i][j][r];  // old + new: the total is complete before the one add
+      }
 }
 
 // part[p][n] = sum of the compact rows that fall into the 128-row block p of the full tensor (the epilogue's wave rows)
@@ -992,7 +994,10 @@ __global__ void colsum_rows_part_kernel(const short* __restrict__ a, long lda, f
   part[i] = v;
 }
 
-int gemm_launch(vit_handle h, const vit_gemm_desc* d, hipStream_t st);  // gemm.hip
+// gemm.hip; k_row_stride > 1: the K rows of an x3 weight-gradient product are compact (GemmArgs::krs), k_rows of them
+int gemm_launch(vit_handle h, const vit_gemm_desc* d, hipStream_t st, int k_row_stride = 0, int k_rows = 0);
+int colsum_strided(vit_handle h, const void* a, int a_dtype, int64_t lda, float* out, int rows, int cols, int64_t row_stride,
+                   int held, int accumulate, hipStream_t st);          // elementwise.hip
 
 }  // namespace vit
 
@@ -1014,9 +1019,19 @@ int vit_linear_bwd_dw_rows(vit_handle h, const void* dy, int64_t ldy, const void
     int splits, kps;
     pp_split_plan(ctx_num_cus(h), (N / 256) * (K / 256), (int)full_rows, -1, &splits, &kps);
     hipLaunchKernelGGL(dw_rows_kernel, dim3(N / 64, K / 64), dim3(256), 0, st, (const short*)dy, (long)ldy, (const short*)x,
-                       (long)ldx, dW, (long)K, rows, (int)row_stride, kps, splits);
+                       (long)ldx, dW, (long)K, rows, (int)row_stride, kps, splits, ctx_grad_accumulate(h));
     VIT_LAUNCH_CHECK();
     return VIT_OK;
+  }
+  if (dtype == VIT_F32 && row_stride > 1 &&
+      (unsigned long long)rows * (unsigned long long)std::max(ldy, ldx) * 4 < 0x7FFFFFF0ull) {
+    // precision '32': the full product over full_rows rows on the x3 kernel with its own split-K plan, the K rows read from
+    // the compact operands and every other row as zero (GemmArgs::krs): the full path's weight gradient bit for bit, at the
+    // full product's MFMA time but none of its operand traffic
+    vit_gemm_desc d = {};
+    d.M = N; d.N = K; d.K = (int)full_rows; d.ab_dtype = VIT_F32; d.a_trans = 1; d.b_trans = 1;
+    d.A = dy; d.lda = ldy; d.B = x; d.ldb = ldx; d.C = dW; d.ldc = K; d.c_dtype = VIT_F32; d.alpha = 1.f; d.split_k = -1;
+    return gemm_launch(h, &d, st, (int)row_stride, rows);
   }
   vit_gemm_desc d = {};  // any other shape: the compact product (the same sum, the GEMM core's own order)
   d.M = N; d.N = K; d.K = rows; d.ab_dtype = dtype; d.a_trans = 1; d.b_trans = 1;
@@ -1042,10 +1057,12 @@ int vit_colsum_rows(vit_handle h, const void* a, int a_dtype, int64_t lda, float
       hipLaunchKernelGGL(colsum_rows_part_kernel, dim3((unsigned)cdiv((long)nblk * cols, 256)), dim3(256), 0, st,
                          (const short*)a, (long)lda, part, nblk, cols, rows, (int)row_stride);
       VIT_LAUNCH_CHECK();
-      return launch_reduce_partials(part, nblk, cols, out, cols, out, 0, st);
+      return launch_reduce_partials(part, nblk, cols, out, cols, out, ctx_grad_accumulate(h), st);
     }
   }
-  return vit_colsum(h, a, a_dtype, lda, out, rows, cols, 0, stream);
+  if (a_dtype == VIT_F32 && row_stride > 1)  // precision '32': vit_colsum's order over the full tensor (absent rows add nothing)
+    return colsum_strided(h, a, a_dtype, lda, out, (int)full_rows, cols, row_stride, rows, ctx_grad_accumulate(h), st);
+  return vit_colsum(h, a, a_dtype, lda, out, rows, cols, ctx_grad_accumulate(h), stream);
 }
 
 }  // extern "C"

@@ -301,8 +301,9 @@ static int ln_bwd_common(vit_handle h, const void* dy, int dy_dtype, const float
   else rc = dy_dtype == VIT_BF16 ? ln_bwd_dispatch<1, 0>(dy, x, gamma, mean, rstd, dres, dx, part, rows, D, blocks, threads, dyn, drop, rm, st)
                                  : ln_bwd_dispatch<0, 0>(dy, x, gamma, mean, rstd, dres, dx, part, rows, D, blocks, threads, dyn, drop, rm, st);
   if (rc != VIT_OK) return rc;
-  if (!dyn) return launch_reduce_partials(part, blocks, 2 * D, dgamma, D, dbeta, 0, st, np * D);
-  return launch_reduce_partials(part, blocks, 3 * D, dgamma, D, dbeta, 0, st, np * D, 2 * D, dbias);  // one launch for all three
+  const int accum = ctx_grad_accumulate(h);  // dgamma / dbeta / dbias += : the add sits in the reducer's one store per column
+  if (!dyn) return launch_reduce_partials(part, blocks, 2 * D, dgamma, D, dbeta, accum, st, np * D);
+  return launch_reduce_partials(part, blocks, 3 * D, dgamma, D, dbeta, accum, st, np * D, 2 * D, dbias);  // one launch for all three
 }
 
 }  // namespace vit

@@ -106,6 +106,11 @@ class GradAllReducer:
         self._pending = []
         self._seen = 0
         self.bytes_reduced = 0
+        self.collectives = 0  # collectives launched so far (all-reduce / reduce-scatter pieces)
+        # Gradient accumulation (train.accumulate_grad_batches): only the micro-batch that is followed by the optimizer step
+        # exchanges -- Lightning's `no_sync` on the others.  While False, bucket_ready does nothing; the exchange of the
+        # stepping micro-batch then carries the locally accumulated sum, overlapped with that last backward as ever.
+        self.armed = True
         self.mode = "allreduce"
         # what one step puts on the wire (for bench.py's `comm` object)
         self.calls_per_step = sum(-(-(hi - lo) // max_bucket_elems) for lo, hi in buckets if hi > lo)
@@ -131,7 +136,7 @@ class GradAllReducer:
 
     def bucket_ready(self, lo: int, hi: int):
         """Engine callback (called on the host right after the kernels that complete grads[lo:hi] were enqueued)."""
-        if not self.active or hi <= lo:
+        if not self.active or not self.armed or hi <= lo:
             return
         g = self._get()
         backend = dist.get_backend(self.group)
@@ -155,6 +160,7 @@ class GradAllReducer:
                 # in the last bit); the multiplicative scale exists only for the bf16 cast-back kernel
                 self._pending.append((w, t, back, (1.0 / self.world) if back is not None else None))
             self.bytes_reduced += t.numel() * t.element_size()
+            self.collectives += 1
         self._seen += 1
 
     def finish(self):
@@ -201,7 +207,7 @@ class ShardedGradReducer(GradAllReducer):
         return self.active and self._sharded_of[(lo, hi)]
 
     def bucket_ready(self, lo: int, hi: int):
-        if not self.active or hi <= lo:
+        if not self.active or not self.armed or hi <= lo:
             return
         if not self.is_sharded(lo, hi) or dist.get_backend(self.group) != "nccl":
             return super().bucket_ready(lo, hi)
@@ -210,6 +216,7 @@ class ShardedGradReducer(GradAllReducer):
         w = dist.reduce_scatter_tensor(g[a:b], g[lo:hi], op=dist.ReduceOp.AVG, group=self.group, async_op=True)
         self._pending.append((w, g[a:b], None, 1.0))
         self.bytes_reduced += (hi - lo) * 4
+        self.collectives += 1
 
     def all_gather_params(self, flat: torch.Tensor):
         """After the sharded update: every rank receives the other ranks' updated slices of the sharded buckets."""

@@ -7,7 +7,9 @@ Data layout in HBM (one MI355X, 288 GB: nothing is recomputed or re-materialised
                            reads them as one [3D, D] matrix.  Pooler last (never receives a gradient: specvit.py:78).
   shadow   bf16 [n_total]  same offsets; what the MFMA GEMMs read.  Refreshed by the fused AdamW kernel, or by one cast
                            pass whenever the f32 buffer was modified behind our back (load_state_dict, a torch optimizer).
-  grads    f32 [n_total]   same offsets; every kernel that produces a parameter gradient writes its slice exactly once.
+  grads    f32 [n_total]   same offsets; every kernel that produces a parameter gradient writes its slice exactly once --
+                           or, in a backward with accumulate=True, adds to it exactly once (gradient accumulation over
+                           micro-batches: the kernels' final stores read the old value).
   arena    per layer: x_in f32 [M,D] (residual stream), h1/h2 bf16 [M,D] (LN outputs), qkv bf16 [M,3D], ctx bf16 [M,D],
            lse f32 [B*H,T], x1 f32 [M,D], u/g bf16 [M,4D] (pre/post GELU), LN statistics.  M = B*T token rows.
   CLS tail c_* : compact [B, .] twins of y / x1 / h2 / u / g / x[L] / last and their statistics (and of the backward's
@@ -175,6 +177,7 @@ class ViTEngine:
         # unless the caller asked for hidden states that part of the last layer runs over the B CLS rows only, forward and
         # backward.  False forces the full path (tests; VIT_CLS_TAIL=0: A/B runs of unmodified scripts).
         self.cls_tail = os.environ.get("VIT_CLS_TAIL", "1") != "0"
+        self._accum = False  # True inside backward(accumulate=True): the handles' "grad_accumulate" option is on
         self._gen = 0  # bumped by every forward: the activation arena holds ONE forward, backward checks it is still that one
         self.grad_ready_cb: Optional[Callable[[int, int], None]] = None
         # Parameters are views of `flat` with their OWN version counters (nn.Parameter / .data re-pointing do not share
@@ -606,6 +609,8 @@ class ViTEngine:
                 self._side_handle.set_option("reserve_cus", self.reserve_cus)
         elif not on:
             self.side_stream = None
+        if self._accum and self._side_handle is not None:  # a side handle created inside an accumulating backward
+            self._side_handle.set_option("grad_accumulate", 1)
 
     # ------------------------------------------------------------------ backward
     def _backward_cls_tail(self, i: int, cdx: torch.Tensor, ph: float, seed: int) -> torch.Tensor:
@@ -639,9 +644,26 @@ class ViTEngine:
                 out=t["dctx_cls"], ldc=T * D)
         return other
 
-    def backward(self, dloss: torch.Tensor, need_dx: bool = False, gen: Optional[int] = None):
+    def _set_accumulate(self, on: bool):
+        for h in (self._main_handle, self._side_handle):
+            if h is not None:
+                h.set_option("grad_accumulate", int(on))
+
+    def backward(self, dloss: torch.Tensor, need_dx: bool = False, gen: Optional[int] = None, accumulate: bool = False):
+        """`accumulate=True`: every parameter-gradient slice of self.grads receives old + new instead of new (the
+        "grad_accumulate" option of both handles is on for the length of the pass and cleared afterwards, also on error);
+        activation gradients are overwritten as ever.  False runs the same kernels with the same arguments as before the option
+        existed: nothing is set."""
         with vf.use_handle(self.handle()):
-            return self._backward(dloss, need_dx, gen)
+            if not accumulate:
+                return self._backward(dloss, need_dx, gen)
+            self._accum = True
+            try:
+                self._set_accumulate(True)
+                return self._backward(dloss, need_dx, gen)
+            finally:
+                self._accum = False
+                self._set_accumulate(False)
 
     def _backward(self, dloss: torch.Tensor, need_dx: bool = False, gen: Optional[int] = None):
         """Fill self.grads (every trainable slice exactly once) for the last forward; calls grad_ready_cb(lo, hi) as
@@ -727,7 +749,7 @@ class ViTEngine:
                              colsum_out=None if rope is not None else self._qkv_bias(i, self.grads), ctx_lo=a["ctx_lo"][i])
             if rope is not None:  # gradient wrt the un-rotated q, k: the inverse rotation
                 vf.rope_qk(t["dqkv"], rope[0], rope[1], T, H, dh, inverse=True)
-                vf.colsum(t["dqkv"], out=self._qkv_bias(i, self.grads))
+                vf.colsum(t["dqkv"], out=self._qkv_bias(i, self.grads), accumulate=self._accum)
             self._dw(t["dqkv"], a["h1"][i], M=3 * D, N=D, K=Mp, a_trans=True, b_trans=True, out=self._qkv_wgrad(i),
                      split_k=-1, reads=("dqkv",))
             vf.gemm(t["dqkv"], self._qkv16(i), M=Mp, N=D, K=3 * D, b_trans=True, out=t["dh"])
@@ -759,7 +781,7 @@ class ViTEngine:
         dpos = self.g(e + "position_embeddings").view(T, D) if c.pos_encoding_type == "learned" else None
         vf.embed_finish_bwd(dx.view(B, T, D), self.g(e + "cls_token").view(D), dpos, dropout=(ph, seed, 0),
                             dpatch=t["dpatch"])  # dtype follows the buffer
-        vf.colsum(t["dpatch"], out=self.g(e + "patch_embeddings.projection.bias"))
+        vf.colsum(t["dpatch"], out=self.g(e + "patch_embeddings.projection.bias"), accumulate=self._accum)
         vf.gemm(t["dpatch"], a["patches"], M=D, N=P, K=B * N, a_trans=True, b_trans=True,
                 out=self.g(e + "patch_embeddings.projection.weight").view(D, P), split_k=-1)
         self._join_side()

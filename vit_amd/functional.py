@@ -60,6 +60,18 @@ NO_DROP: Dropout = (0.0, 0, 0)
 
 
 # ------------------------------------------------------------------------------------------------ GEMM
+def _splitk_slabs(M: int, N: int, K: int, split_k: int, dtype) -> int:
+    """Slabs a split-K product may write: `split_k` itself, or for -1 an upper bound over the automatic choices of both GEMM
+    cores (gemm.hip: K tiles of 64, of 32 for f32 operands; gemm2.hip).  The one place the wrappers size that workspace from."""
+    if split_k >= 0:
+        return max(1, split_k)
+    tiles = -(-M // 128) * -(-N // 128)
+    ktiles = -(-K // (32 if dtype == torch.float32 else 64))
+    n = min(max(1, 512 // tiles), max(1, ktiles // 4)) if tiles < 256 else 1
+    t2 = max(1, (M // 256) * max(1, N // 256))
+    return max(n, min(max(1, 256 // t2), max(1, -(-K // 64) // 8)) + 1)
+
+
 def gemm(a: torch.Tensor, b: torch.Tensor, *, M: int, N: int, K: int, a_trans: bool = False, b_trans: bool = False,
          lda: Optional[int] = None, ldb: Optional[int] = None, out: Optional[torch.Tensor] = None,
          out_dtype=torch.bfloat16, ldc: Optional[int] = None, alpha: float = 1.0, bias: Optional[torch.Tensor] = None,
@@ -96,12 +108,15 @@ def gemm(a: torch.Tensor, b: torch.Tensor, *, M: int, N: int, K: int, a_trans: b
     d.rows_per_batch, d.out_batch_rows, d.out_row_offset = row_map
     d.split_k = split_k
     d.accumulate = int(accumulate)
+    extra = 0  # bytes behind the kernels' own partials
     if colsum_out is not None:  # column sums of C (a bias gradient): fused into the epilogue or a vit_colsum pass
         _chk(colsum_out, torch.float32, "gemm colsum_out")
         if colsum_out.numel() != N:
             raise _cabi.VitError(f"gemm: colsum_out must have N={N} elements")
         d.colsum_out = colsum_out.data_ptr()
-        h.ensure_workspace(max(2 * (-(-M // 256)), 2048) * N * 4)
+        if h.options.get("grad_accumulate") and a_trans and out.dtype == torch.float32:
+            extra = M * N * 4 + 256  # an accumulating C beside column sums: the product's scratch matrix (vit_amd.h)
+        h.ensure_workspace(max(2 * (-(-M // 256)), 2048) * N * 4 + extra)
     if rope is not None:
         cos, sin, rT, rdh, rcols = rope
         _chk(cos, torch.float32, "gemm rope cos")
@@ -110,14 +125,7 @@ def gemm(a: torch.Tensor, b: torch.Tensor, *, M: int, N: int, K: int, a_trans: b
             raise _cabi.VitError(f"gemm: rope tables must be [T={rT}, head_dim/2={rdh // 2}]")
         d.rope_cos, d.rope_sin, d.rope_T, d.rope_dh, d.rope_cols = cos.data_ptr(), sin.data_ptr(), int(rT), int(rdh), int(rcols)
     if split_k != 0 and split_k != 1:
-        if split_k < 0:  # upper bound over the automatic choices of both GEMM cores (gemm.hip / gemm2.hip)
-            tiles = -(-M // 128) * -(-N // 128)
-            ktiles = -(-K // 64)
-            split_k = min(max(1, 512 // tiles), max(1, ktiles // 4)) if tiles < 256 else 1
-            t2 = max(1, (M // 256) * max(1, N // 256))
-            split_k = max(split_k, min(max(1, 256 // t2), max(1, ktiles // 8)) + 1)
-        h.ensure_workspace(split_k * M * N * 4)
-        split_k = d.split_k
+        h.ensure_workspace(_splitk_slabs(M, N, K, split_k, a.dtype) * M * N * 4 + extra)
     check(h.lib.vit_gemm(h.h, C.byref(d), _stream(a)), "vit_gemm")
     return out
 
@@ -260,6 +268,8 @@ def linear_bwd_dw_rows(dy, x, out, *, row_stride: int, full_rows: int, ldx: Opti
     K = out.shape[1]
     if out.shape[0] != N or not out.is_contiguous() or not dy.is_contiguous():
         raise _cabi.VitError("linear_bwd_dw_rows: out must be a contiguous [N, K] tensor, dy contiguous")
+    if dy.dtype == torch.float32 and row_stride > 1:  # the full product's split-K slabs
+        h.ensure_workspace(_splitk_slabs(N, K, full_rows, -1, dy.dtype) * N * K * 4)
     check(h.lib.vit_linear_bwd_dw_rows(h.h, dy.data_ptr(), N, x.data_ptr(), ldx if ldx is not None else K, _DT[dy.dtype],
                                        out.data_ptr(), rows, N, K, row_stride, full_rows, _stream(dy)),
           "vit_linear_bwd_dw_rows")

@@ -91,7 +91,10 @@ class BaseLightningModule(_Base):
         if "onecycle" in schedule:
             train = cfg.get("train") or {}
             per_step = int(train.get("batch_size", 64))
-            opt["steps_per_epoch"] = -(-int(data.get("num_samples", 32000)) // per_step)
+            # optimizer steps, not batches: train.accumulate_grad_batches micro-batches share one (the last group of an
+            # epoch may be short and still steps)
+            accum = int(train.get("accumulate_grad_batches", 1) or 1)
+            opt["steps_per_epoch"] = -(-(-(-int(data.get("num_samples", 32000)) // per_step)) // accum)
             opt["epochs"] = int(train.get("ep", 100))
         return OptModule.from_config(opt)(self.model)
 

@@ -70,7 +70,13 @@ def _trunc_normal_(t: torch.Tensor, std: float):
 
 class _ViTFunction(torch.autograd.Function):
     """Whole-model autograd node: forward/backward are the engine's kernel sequences; parameter gradients come back as
-    views of the engine's flat gradient buffer (no copies when .grad is None, i.e. zero_grad(set_to_none=True))."""
+    views of the engine's flat gradient buffer (no copies when .grad is None, i.e. zero_grad(set_to_none=True)).
+
+    A second backward without zero_grad in between (gradient accumulation: Lightning's accumulate_grad_batches, the plain
+    `loss.backward()` idiom) finds those views as the parameters' `.grad`.  Returning them again would make autograd run
+    `p.grad += <the same memory>` after the kernels overwrote it -- twice the last micro-batch's gradient.  So when every
+    trainable parameter still holds its view, the kernels ADD into the buffer (ViTEngine.backward(accumulate=True)) and
+    autograd gets None for them."""
 
     @staticmethod
     def forward(ctx, model, x, labels, training, keep_hidden, *params):
@@ -89,13 +95,19 @@ class _ViTFunction(torch.autograd.Function):
     def backward(ctx, dloss, _dlogits):
         model = ctx.model
         eng = model.engine
-        dx = eng.backward(dloss, need_dx=ctx.need_dx, gen=ctx.gen)
-        grads = []
-        for name, p in zip(model._param_names, model._param_list):
-            if not p.requires_grad or name.startswith("vit.pooler."):
-                grads.append(None)  # the pooler output is never used (specvit.py:78): no gradient, as in the reference
-            else:
-                grads.append(eng.g(name))
+        # frozen parameters and the pooler (its output is never used, specvit.py:78: no gradient, as in the reference) get None
+        live = [p.requires_grad and not name.startswith("vit.pooler.") for name, p in zip(model._param_names, model._param_list)]
+        held = [ok and eng.grads is not None and p.grad is not None and p.grad.data_ptr() == eng.g(name).data_ptr()
+                for ok, name, p in zip(live, model._param_names, model._param_list)]
+        accumulate = any(held)
+        if accumulate and held != live:
+            # the fused kernels write q / k / v and the LayerNorm / bias groups together: one mode for the whole buffer
+            bad = next(n for n, ok, h in zip(model._param_names, live, held) if ok and not h)
+            raise VitError(f"backward: {bad}.grad is not the flat gradient buffer's view while other parameters still hold "
+                           f"theirs from an earlier backward; gradients accumulate in place for all trainable parameters or "
+                           f"for none -- call zero_grad() on the whole model (set_to_none=True or False), not on single parameters")
+        dx = eng.backward(dloss, need_dx=ctx.need_dx, gen=ctx.gen, accumulate=accumulate)
+        grads = [eng.g(name) if ok and not accumulate else None for ok, name in zip(live, model._param_names)]
         return (None, dx, None, None, None, *grads)
 
 

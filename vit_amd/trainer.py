@@ -5,6 +5,9 @@
            for batch: zero_grad -> training_step (forward) -> backward (when devices > 1 the flat gradient buffer is
                       mean-all-reduced bucket by bucket while backward runs: hardware_utils.py:95 'ddp')
                       -> clip the global gradient norm to `train.grad_clip` or 0.5 (basemodule.py:244) -> optimizer step
+                      (`train.accumulate_grad_batches: K` = Lightning's: zero_grad at the start of a group of K batches,
+                      each backward on loss / K adding into the flat gradient buffer in place, exchange + clip + step +
+                      per-step scheduler on every K-th batch and on the epoch's last one)
            validate every epoch (basemodule.py:249)
            scheduler: ReduceLROnPlateau on `val_{monitor}` / per-epoch / per-step (opt/optimizer.py:150-172)
            ModelCheckpoint(save_top_k=1, monitor=val_{mae|acc}, save_last=True) when `train.save` (vit.py:386-414)
@@ -70,6 +73,26 @@ def _bind(loader, device):
     if loader is not None and hasattr(loader, "bind"):
         loader.bind(device)
     return loader
+
+
+def _accumulate_grad_batches(config) -> int:
+    """train.accumulate_grad_batches: an integer >= 1 (default 1); anything else is a ValueError."""
+    k = config.get("accumulate_grad_batches", 1)
+    if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+        raise ValueError(f"train.accumulate_grad_batches must be an integer >= 1, got {k!r}")
+    return k
+
+
+def _flag_last(iterable):
+    """(item, is_last) pairs: one item of look-ahead, so that the last batch of an epoch is known when it is trained on."""
+    it = iter(iterable)
+    prev = next(it, _flag_last)
+    if prev is _flag_last:
+        return
+    for cur in it:
+        yield prev, False
+        prev = cur
+    yield prev, True
 
 
 def _batch_size(batch) -> int:
@@ -189,6 +212,9 @@ class Trainer:
         # train.hip_graph: replay the optimisation step as one captured hipGraph (vit_amd/graph.py; single GPU only)
         self.use_graph = bool(config.get("hip_graph", False))
         self._graphed = None
+        # train.accumulate_grad_batches (Lightning's semantics): micro-batches per optimizer step
+        self.accumulate_grad_batches = _accumulate_grad_batches(config)
+        self._micro = 0  # micro-batches of the current group already accumulated
         self.verbose = verbose and self.rank == 0
         self.logged: Dict[str, float] = {}
         self.metric_totals: Dict[str, float] = {}
@@ -321,6 +347,7 @@ class Trainer:
         for g, saved in zip(opt.param_groups, snap["groups"]):
             g.update(saved)
         opt.zero_grad(set_to_none=True)
+        self._micro = 0
 
     def set_reserve_cus(self, module, n: int):
         """Launch geometry of THIS module's engine (its own vit_handle): nothing process-wide changes."""
@@ -340,39 +367,51 @@ class Trainer:
             return {}
         dist = torch.distributed
         snap = self._snapshot(module) if restore else None
+        accum, self.accumulate_grad_batches = self.accumulate_grad_batches, 1  # the probes are single optimisation steps
         # a per-step scheduler (one-cycle) has a fixed number of steps to give: the probe steps do not take from it
         sched_cfg, self.sched_cfg = self.sched_cfg, (None if restore else self.sched_cfg)
         out = {}
-        for c in candidates:
-            self.set_reserve_cus(module, int(c))
-            self.training_step(module, batch, 0)  # the grids' first launch at this size
-            ev = [torch.cuda.Event(enable_timing=True) for _ in range(steps + 1)]
-            torch.cuda.synchronize()
-            dist.barrier()
-            ev[0].record()
-            for i in range(steps):
-                self.training_step(module, batch, i)
-                ev[i + 1].record()
-            torch.cuda.synchronize()
-            t = torch.tensor([ev[i].elapsed_time(ev[i + 1]) for i in range(steps)], dtype=torch.float64, device=self.device)
-            dist.all_reduce(t, op=dist.ReduceOp.MAX)
-            out[int(c)] = float(t.median())
+        try:
+            for c in candidates:
+                self.set_reserve_cus(module, int(c))
+                self.training_step(module, batch, 0)  # the grids' first launch at this size
+                ev = [torch.cuda.Event(enable_timing=True) for _ in range(steps + 1)]
+                torch.cuda.synchronize()
+                dist.barrier()
+                ev[0].record()
+                for i in range(steps):
+                    self.training_step(module, batch, i)
+                    ev[i + 1].record()
+                torch.cuda.synchronize()
+                t = torch.tensor([ev[i].elapsed_time(ev[i + 1]) for i in range(steps)], dtype=torch.float64, device=self.device)
+                dist.all_reduce(t, op=dist.ReduceOp.MAX)
+                out[int(c)] = float(t.median())
+        finally:  # also when a probe raises: the trainer keeps its scheduler and its K
+            self.sched_cfg = sched_cfg
+            self.accumulate_grad_batches = accum
         best = min(out, key=lambda k: (out[k], k))
         self.set_reserve_cus(module, best)
-        self.sched_cfg = sched_cfg
         if snap is not None:
             self._restore(module, snap)
         return out
 
     # ------------------------------------------------------------------ one optimisation step
-    def training_step(self, module, batch, batch_idx):
-        """zero_grad -> forward -> backward (+ overlapped gradient exchange) -> clip -> optimizer step."""
+    def training_step(self, module, batch, batch_idx, is_last: bool = False):
+        """zero_grad -> forward -> backward (+ overlapped gradient exchange) -> clip -> optimizer step.
+        `is_last`: the epoch's last batch (closes a short accumulation group; unused without accumulation)."""
         self._cur_bs = _batch_size(batch)
+        if self.accumulate_grad_batches > 1:
+            return self._accumulating_step(module, batch, batch_idx, is_last)
         if self.use_graph and not self.exchanging:
             return self._graph_step(module, batch)
         self.optimizer.zero_grad(set_to_none=True)
         loss = module.training_step(batch, batch_idx)
         loss.backward()
+        self._optimizer_step(module)
+        return loss
+
+    def _optimizer_step(self, module):
+        """Join the gradient exchange, clip, step the optimizer and a per-step scheduler: the end of an optimisation step."""
         if self.reducer is not None:
             self.reducer.finish()
             for p in getattr(self.optimizer, "_extras", []):  # a trainable preprocessor lives outside the flat buffer
@@ -385,6 +424,36 @@ class Trainer:
         if self.sched_cfg and self.sched_cfg.get("interval") == "step":
             self.sched_cfg["scheduler"].step()
         self.global_step += 1
+
+    def _accumulating_step(self, module, batch, batch_idx, is_last: bool):
+        """One micro-batch of a group of K = train.accumulate_grad_batches (Lightning's semantics).  The backward runs on
+        loss / K -- a short trailing group still uses 1 / K -- and the model's autograd node adds into the flat gradient buffer
+        in place from the group's second micro-batch on (vit_amd/specvit.py).  The logged loss is the undivided one.  Exchange,
+        clip, optimizer step, per-step scheduler and global_step belong to the group's last micro-batch; on the others the
+        reducer is disarmed (Lightning's no_sync), so the one exchange carries the locally accumulated sum."""
+        K = self.accumulate_grad_batches
+        if self.use_graph:
+            import warnings
+
+            warnings.warn("train.hip_graph: a group of accumulated micro-batches is not captured as a graph "
+                          "(train.accumulate_grad_batches > 1); continuing with eager launches")
+            self.use_graph = False
+        if self._micro == 0:
+            self.optimizer.zero_grad(set_to_none=True)
+        stepping = self._micro + 1 >= K or is_last or self.fast_dev_run
+        if self.reducer is not None:
+            self.reducer.armed = stepping
+        try:
+            loss = module.training_step(batch, batch_idx)
+            (loss / K).backward()
+        finally:
+            if self.reducer is not None:
+                self.reducer.armed = True
+        self._micro += 1
+        if not stepping:
+            return loss
+        self._micro = 0
+        self._optimizer_step(module)
         return loss
 
     def _graph_step(self, module, batch):
@@ -552,6 +621,14 @@ class Trainer:
                 if peeked is not None:
                     batches = itertools.chain([] if peeked[0] is None else [peeked[0]], peeked[1])
                     peeked = None
+                self._micro = 0
+                if self.accumulate_grad_batches > 1:
+                    # the epoch's last batch closes a short group, so the batches are read with one batch of look-ahead
+                    for i, (batch, last) in enumerate(_flag_last(batches)):
+                        self.training_step(module, _to_device(batch, self.device), i, is_last=last)
+                        if self.fast_dev_run:
+                            break
+                    batches = ()
                 for i, batch in enumerate(batches):
                     self.training_step(module, _to_device(batch, self.device), i)
                     if self.fast_dev_run:
