@@ -44,10 +44,16 @@ typedef enum { VIT_LOSS_MSE = 0, VIT_LOSS_L1 = 1, VIT_LOSS_CE = 2 } vit_loss;
 int vit_version(void);
 const char* vit_last_error(void);
 
-/* Handle: device id + a caller-owned workspace (split-K slabs, reduction partials). */
+/* Handle: device id + a workspace (split-K slabs, reduction partials).  The workspace is caller-owned device memory of any
+ * size (256-byte aligned; none until vit_set_workspace).  Each call states what it needs: one that needs more than the handle
+ * holds returns VIT_ERR_WORKSPACE BEFORE launching anything -- nothing was written, and the call may simply be repeated with a
+ * larger workspace, also under "grad_accumulate" -- and vit_workspace_needed() then returns the bytes that whole call needs
+ * (thread-local, like vit_last_error).  The need depends on the call's arguments and the handle's options alone, and no call
+ * chooses its kernels or its summation order by the size of the workspace. */
 int vit_create(vit_handle* out, int device);
 int vit_destroy(vit_handle h);
 int vit_set_workspace(vit_handle h, void* ws, size_t bytes);
+size_t vit_workspace_needed(void);
 /* Process-wide options (none changes results beyond rounding order):
  *   "gemm_core": 0 = generic 128x128 core only, 1 = automatic (default): tile-aligned problems (M, N multiples of 256, K of
  *                64) run the 256x256x64 ping-pong core (wave halves one barrier out of phase: LOAD segment beside MFMA
@@ -81,7 +87,7 @@ int vit_set_option(const char* name, int value);
  * + old C); single-slice products -- the epilogue's residual port reads old C; vit_linear_bwd_dw_rows -- the final store of
  * the slice total; every vector output -- the last stage of the partial-row reducer.  A vit_gemm whose C accumulates AND that
  * carries colsum_out (two parameter gradients from one descriptor; no training step issues it) runs the product into a
- * scratch matrix taken from the end of the workspace (M * N * 4 more bytes), sums its columns and adds it into C. */
+ * scratch matrix at the end of the workspace (part of what the call needs of it), sums its columns and adds it into C. */
 int vit_handle_set_option(vit_handle h, const char* name, int value);
 
 /* Per-step state in device memory, for a training step captured as a hipGraph (HIP streams and graphs instead of a tracing
@@ -136,7 +142,8 @@ typedef struct vit_gemm_desc {
                             * order, scaled by alpha, old C added last), else through the epilogue's residual port (no residual
                             * then); OR-ed with the handle's "grad_accumulate" for products of the weight-gradient form */
   float* colsum_out;       /* optional f32 [N]: column sums of C as stored (a Linear's bias gradient when C is the gradient
-                            * of its output); summed inside the epilogue where the kernel can, else by a vit_colsum pass */
+                            * of its output); summed inside the epilogue by the kernels that have such an epilogue, else by a
+                            * vit_colsum pass behind the product: the shape and the options decide, never the workspace */
   /* Rotary position embedding of the fused QKV projection's output (src/models/vit_with_rope.py:58-60, rope.py:116-131):
    * columns [0, rope_cols) of C are heads of rope_dh columns whose element i pairs with element i + rope_dh / 2, row m is token
    * m % rope_T; cos / sin: f32 [rope_T, rope_dh / 2] (vit_rope_qk's tables).  NULL = off.  The ping-pong core rotates in its
@@ -255,7 +262,8 @@ int vit_attention_fwd(vit_handle h, const void* qkv, void* ctx, void* ctx_lo, fl
  * scratch (rowsum(dctx * (ctx + ctx_lo)); ctx_lo may be NULL: rowsum(dctx * ctx)), written by this call.
  * dqkv_colsum (f32 [3*H*dh], may be NULL) = the column sums of dqkv as stored: the bias gradient of the fused QKV projection
  * (without RoPE; with it the sums must be taken after the inverse rotation).  The resident and pipelined bf16 kernels sum
- * their own rows on the way out (one partial row per wave through the workspace); other paths run vit_colsum afterwards. */
+ * their own rows on the way out (one partial row per wave through the workspace); the tiled and f32 forms run vit_colsum
+ * afterwards.  Which of the two is a function of the shape and the options alone. */
 int vit_attention_bwd(vit_handle h, const void* qkv, const void* ctx, const void* ctx_lo, const void* dctx, const float* lse,
                       float* delta, void* dqkv, int io_dtype, int B, int H, int T, int dh, float scale, float dropout_p,
                       uint64_t seed, uint64_t site, float* dqkv_colsum, vit_stream stream);

@@ -302,7 +302,8 @@ _EXPORTS = {
     'vit_cast_f32_bf16': 5, 'vit_cast_bf16_f32': 6, 'vit_head_loss_fwd': 13, 'vit_head_loss_bwd': 16, 'vit_grad_sqnorm': 5,
     'vit_grad_sqnorm_acc': 5, 'vit_adamw_step': 16,
 }
-_NEW = {'vit_layernorm_fwd_residual_rows': 16, 'vit_layernorm_bwd_rows': 22, 'vit_linear_bwd_dw_rows': 13, 'vit_colsum_rows': 10}
+_NEW = {'vit_layernorm_fwd_residual_rows': 16, 'vit_layernorm_bwd_rows': 22, 'vit_linear_bwd_dw_rows': 13, 'vit_colsum_rows': 10,
+        'vit_workspace_needed': 0}
 _DESC_FIELDS = ["M", "N", "K", "a_trans", "b_trans", "ab_dtype", "A", "lda", "B", "ldb", "C", "ldc", "c_dtype", "alpha", "bias",
                 "act", "aux_out", "aux_in", "ldaux", "dropout_p", "seed", "site", "residual", "ldres", "rows_per_batch",
                 "out_batch_rows", "out_row_offset", "split_k", "accumulate", "colsum_out", "rope_cos", "rope_sin", "rope_T",

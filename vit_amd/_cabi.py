@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VIT_AMD_LIB") or os.path.join(_HERE, "lib", "libvit_amd.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "vit_amd.h")
 
-VIT_OK = 0
+VIT_OK, VIT_ERR_WORKSPACE = 0, -4
 VIT_F32, VIT_BF16 = 0, 1
 ACT_NONE, ACT_GELU, ACT_DGELU, ACT_GELU_GRAD, ACT_MUL_AUX = 0, 1, 2, 3, 4
 LOSS_MSE, LOSS_L1, LOSS_CE = 0, 1, 2
@@ -57,6 +57,7 @@ _PROTOS = {
     "vit_create": [C.POINTER(_P), _I],
     "vit_destroy": [_P],
     "vit_set_workspace": [_P, _P, _SZ],
+    "vit_workspace_needed": [],
     "vit_set_option": [C.c_char_p, _I],
     "vit_handle_set_option": [_P, C.c_char_p, _I],
     "vit_step_state_bind": [_P, _P],
@@ -97,7 +98,7 @@ _PROTOS = {
     "vit_grad_sqnorm_acc": [_P, _P, _I64, _P, _P],
     "vit_adamw_step": [_P, _P, _P, _P, _P, _P, _I64, _F, _F, _F, _F, _F, _I, _P, _F, _P],
 }
-_RESTYPES = {"vit_last_error": C.c_char_p, "vit_last_gemm_kernel": C.c_char_p}
+_RESTYPES = {"vit_last_error": C.c_char_p, "vit_last_gemm_kernel": C.c_char_p, "vit_workspace_needed": C.c_size_t}
 
 _lib = None
 _lock = threading.Lock()
@@ -171,7 +172,6 @@ class Handle:
         h = C.c_void_p()
         check(self.lib.vit_create(C.byref(h), device_index), "vit_create")
         self.h = h
-        self.options = {}  # name -> last value given to set_option (what the wrappers size workspaces by)
         self._ws = None
         self.set_workspace(workspace_bytes)
 
@@ -186,11 +186,20 @@ class Handle:
         """Per-handle options (vit_handle_set_option): 'reserve_cus' (launch geometry of the calls made through THIS handle),
         'grad_accumulate' (parameter-gradient outputs store old + new)."""
         check(self.lib.vit_handle_set_option(self.h, name.encode(), int(value)), f"vit_handle_set_option({name})")
-        self.options[name] = int(value)
 
     def ensure_workspace(self, nbytes: int):
         if nbytes > self.workspace_bytes:
             self.set_workspace(int(nbytes * 1.25))
+
+    def call(self, name: str, *args):
+        """lib.<name>(handle, *args).  The library states what a call needs of the workspace: one that needs more has launched
+        nothing (VIT_ERR_WORKSPACE), so the workspace grows to vit_workspace_needed() and the call is made once more."""
+        fn = getattr(self.lib, name)
+        rc = fn(self.h, *args)
+        if rc == VIT_ERR_WORKSPACE:
+            self.ensure_workspace(self.lib.vit_workspace_needed())
+            rc = fn(self.h, *args)
+        check(rc, name)
 
     def __del__(self):
         try:

@@ -58,7 +58,7 @@ int ctx_num_cus(vit_handle h) {
 int ctx_grad_accumulate(vit_handle h) { return h ? h->grad_accumulate : 0; }
 
 // Take at least `bytes` off the END of the handle's workspace for the caller (256-byte aligned start) and hide them from
-// ctx_workspace until ctx_release_tail gives them back: a scratch region that the kernels launched in between (which size
+// ctx_claim until ctx_release_tail gives them back: a scratch region that the kernels launched in between (which size
 // their own partials from the front of the workspace) cannot overlap.  Host-side bookkeeping only; NULL when the workspace
 // is too small.  One reservation at a time.
 void* ctx_reserve_tail(vit_handle h, size_t bytes) {
@@ -73,13 +73,13 @@ void ctx_release_tail(vit_handle h) {
   h->ws_hidden = 0;
 }
 
-void* ctx_workspace(vit_handle h, size_t* bytes) {
-  if (!h) {
-    *bytes = 0;
-    return nullptr;
-  }
-  *bytes = h->ws_bytes;
-  return h->ws;
+static thread_local size_t g_ws_needed = 0;  // vit_workspace_needed()
+void* ctx_claim(vit_handle h, size_t need_bytes, const char* who) {
+  const size_t have = h ? h->ws_bytes : 0;
+  if (h && h->ws && have >= need_bytes) return h->ws;
+  g_ws_needed = need_bytes;
+  set_error("%s: needs %zu workspace bytes, have %zu", who, need_bytes, have);
+  return nullptr;
 }
 
 }  // namespace vit
@@ -89,6 +89,8 @@ extern "C" {
 int vit_version(void) { return VIT_AMD_VERSION; }
 
 const char* vit_last_error(void) { return vit::g_err; }
+
+size_t vit_workspace_needed(void) { return vit::g_ws_needed; }
 
 int vit_create(vit_handle* out, int device) {
   VIT_CHECK(out, VIT_ERR_ARG, "vit_create: null out pointer");

@@ -4,8 +4,6 @@
 
 namespace vit {
 
-void* ctx_workspace(vit_handle h, size_t* bytes);
-
 // vit_set_option("attn_bwd_fused"): 0 = two-kernel backward everywhere; non-zero (default 4; 1 .. 3 named forms that no longer
 // exist and mean the same) = the pair-pipelined single kernel where it fits (dh 64, 64 <= T <= 208), the two-kernel path elsewhere
 int g_attn_bwd_fused = 4;
@@ -91,6 +89,14 @@ int vit_attention_bwd(vit_handle h, const void* qkv, const void* ctx, const void
   const AttnPlan pl = attn_plan(h, io_dtype, true, B, H, T, dh, ctx_lo != nullptr, false);
   hipStream_t st = (hipStream_t)stream;
   const int D3 = 3 * H * dh;
+  // column sums: the resident and pipelined kernels leave one partial row per wave (the sums as stored), the f32 and tiled
+  // forms run vit_colsum over the stored dqkv -- either way through the workspace, claimed before anything is launched
+  float* part = nullptr;
+  if (dqkv_colsum) {
+    part = (float*)ctx_claim(h, pl.csum_rows ? (size_t)pl.csum_rows * D3 * sizeof(float) : colsum_ws_bytes(B * T, D3),
+                             "vit_attention_bwd");
+    if (!part) return VIT_ERR_WORKSPACE;
+  }
   if (io_dtype == VIT_F32) {
     Attn32Args a32 = {};
     a32.qkv = (const float*)qkv; a32.ctx = (float*)const_cast<void*>(ctx); a32.lse = const_cast<float*>(lse);
@@ -105,18 +111,13 @@ int vit_attention_bwd(vit_handle h, const void* qkv, const void* ctx, const void
     a.dctx = (const short*)dctx; a.delta = delta; a.dqkv = (short*)dqkv;
     a.B = B; a.H = H; a.T = T; a.dh = dh; a.scale = scale;
     a.drop = make_drop_h(h, dropout_p, seed, site);
-    if (dqkv_colsum && pl.csum_rows) {
-      // the resident and pipelined kernels leave one partial row per wave (column sums as stored) if the workspace holds them
-      size_t wsb = 0;
-      float* part = (float*)ctx_workspace(h, &wsb);
-      if (part && wsb >= (size_t)pl.csum_rows * D3 * sizeof(float)) a.csum_part = part;
-    }
+    if (pl.csum_rows) a.csum_part = part;
     rc = pl.form == ATTN_PIPE ? launch_attn_pipe(a, pl, st)
          : pl.form == ATTN_RESIDENT ? launch_attn_resident(a, pl, st) : launch_attn_tiled(a, pl, st);
     if (rc == VIT_OK && a.csum_part)
       return launch_reduce_partials(a.csum_part, pl.csum_rows, D3, dqkv_colsum, D3, dqkv_colsum, ctx_grad_accumulate(h), st);
   }
-  // no kernel partials (f32, tiled form, workspace too small): column sums over the stored dqkv
+  // no kernel partials (f32, tiled form): column sums over the stored dqkv
   if (rc != VIT_OK || !dqkv_colsum) return rc;
   return vit_colsum(h, dqkv, io_dtype, D3, dqkv_colsum, B * T, D3, ctx_grad_accumulate(h), stream);
 }

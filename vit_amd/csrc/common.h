@@ -295,6 +295,13 @@ int ctx_num_cus(vit_handle h);  // compute units of the handle's device (api.hip
 // vit_handle_set_option("grad_accumulate"): non-zero = every parameter-gradient output of a call through this handle stores
 // old + new (new = what overwrite mode stores, bit for bit; one f32 add in the producer's final write or reduce stage)
 int ctx_grad_accumulate(vit_handle h);
+// The handle's workspace, for a caller that needs `need_bytes` (> 0) from its front -- or NULL when it does not hold them (a
+// NULL handle holds none): the need is then recorded for vit_workspace_needed(), the error text is "`who`: needs N workspace
+// bytes, have M", and the caller returns VIT_ERR_WORKSPACE.  An entry point claims its WHOLE need (the maximum over its stages,
+// which use the workspace one after another on one stream) before its first launch; a stage's own claim then cannot fail.
+void* ctx_claim(vit_handle h, size_t need_bytes, const char* who);
+// what colsum_strided / vit_colsum claim for a [rows, cols] tensor (elementwise.hip)
+size_t colsum_ws_bytes(int rows, int cols);
 static inline DropCfg make_drop_h(vit_handle h, float p, uint64_t seed, uint64_t site) {
   DropCfg d = make_drop(p, seed, site);
   const StepState* s = h ? ctx_step_state(h) : nullptr;

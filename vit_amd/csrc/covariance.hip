@@ -24,8 +24,6 @@
 
 namespace vit {
 
-void* ctx_workspace(vit_handle h, size_t* bytes);
-
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 constexpr int COV_T = 128;         // tile edge
@@ -232,10 +230,8 @@ int vit_cov_accumulate(vit_handle h, const float* x, int64_t ldx, const float* m
   const bool vec = (ldx % 4) == 0 && (L % 4) == 0 && ((uintptr_t)x & 15) == 0;
   float* slab = nullptr;
   if (slices > 1) {
-    size_t wsb = 0;
-    slab = (float*)ctx_workspace(h, &wsb);
-    const size_t need = (size_t)slices * tiles * COV_T * COV_T * sizeof(float);
-    VIT_CHECK(slab && wsb >= need, VIT_ERR_WORKSPACE, "vit_cov_accumulate: needs %zu workspace bytes, have %zu", need, wsb);
+    slab = (float*)ctx_claim(h, (size_t)slices * tiles * COV_T * COV_T * sizeof(float), "vit_cov_accumulate");
+    if (!slab) return VIT_ERR_WORKSPACE;
   }
   if (vec)
     hipLaunchKernelGGL(cov_accumulate_kernel<true>, dim3((unsigned)tiles, slices), dim3(256), 0, st, x, (long)ldx, mean, acc, slab,

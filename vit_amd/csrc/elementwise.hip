@@ -7,7 +7,6 @@
 
 namespace vit {
 
-void* ctx_workspace(vit_handle h, size_t* bytes);
 int colsum_strided(vit_handle h, const void* a, int a_dtype, int64_t lda, float* out, int rows, int cols, int64_t row_stride,
                    int held, int accumulate, hipStream_t st);
 
@@ -625,10 +624,8 @@ int vit_embed_finish_bwd(vit_handle h, const float* dtokens, void* dpatch_out, i
   VIT_CHECK(dtokens && dpatch_out && dcls, VIT_ERR_ARG, "vit_embed_finish_bwd: null pointer");
   VIT_CHECK(B > 0 && T > 1 && D > 0 && (D % 4) == 0, VIT_ERR_ARG, "vit_embed_finish_bwd: B=%d T=%d D=%d", B, T, D);
   const int nchunk = std::min(B, 16), bchunk = cdiv(B, nchunk), ny = cdiv(B, bchunk);
-  size_t wsb = 0;
-  float* part = (float*)ctx_workspace(h, &wsb);
-  const size_t need = (size_t)ny * T * D * sizeof(float);
-  VIT_CHECK(part && wsb >= need, VIT_ERR_WORKSPACE, "vit_embed_finish_bwd: needs %zu workspace bytes, have %zu", need, wsb);
+  float* part = (float*)ctx_claim(h, (size_t)ny * T * D * sizeof(float), "vit_embed_finish_bwd");
+  if (!part) return VIT_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   accumulate = accumulate || ctx_grad_accumulate(h);
   const dim3 grid(cdiv((long)T * (D / 4), 256), ny);
@@ -669,6 +666,9 @@ int vit_colsum(vit_handle h, const void* a, int a_dtype, int64_t lda, float* out
 }  // extern "C"
 
 namespace vit {
+static int colsum_blocks_y(int rows, int cols) { return std::max(1, std::min(cdiv(rows, 64), 2048 / cdiv(cols, 256))); }
+size_t colsum_ws_bytes(int rows, int cols) { return (size_t)colsum_blocks_y(rows, cols) * cols * sizeof(float); }
+
 // vit_colsum over `rows` rows of which, with row_stride s > 1, only the rows r = j * s, j < held, exist (compactly, at row j of a)
 int colsum_strided(vit_handle h, const void* a, int a_dtype, int64_t lda, float* out, int rows, int cols, int64_t row_stride,
                    int held, int accumulate, hipStream_t st) {
@@ -676,12 +676,9 @@ int colsum_strided(vit_handle h, const void* a, int a_dtype, int64_t lda, float*
   VIT_CHECK(a && out, VIT_ERR_ARG, "vit_colsum: null pointer");
   VIT_CHECK(rows > 0 && cols > 0 && (cols % 4) == 0 && (lda % 4) == 0 && lda >= cols, VIT_ERR_ARG,
             "vit_colsum: rows=%d cols=%d lda=%ld", rows, cols, (long)lda);
-  const int gx = cdiv(cols, 256);
-  const int gy = std::max(1, std::min(cdiv(rows, 64), 2048 / gx));
-  size_t wsb = 0;
-  float* part = (float*)ctx_workspace(h, &wsb);
-  const size_t need = (size_t)gy * cols * sizeof(float);
-  VIT_CHECK(part && wsb >= need, VIT_ERR_WORKSPACE, "vit_colsum: needs %zu workspace bytes, have %zu", need, wsb);
+  const int gx = cdiv(cols, 256), gy = colsum_blocks_y(rows, cols);
+  float* part = (float*)ctx_claim(h, colsum_ws_bytes(rows, cols), "vit_colsum");
+  if (!part) return VIT_ERR_WORKSPACE;
   if (a_dtype == VIT_BF16)
     hipLaunchKernelGGL(colsum_stage1_kernel<1>, dim3(gx, gy), dim3(256), 0, st, a, (long)lda, part, rows, cols, rs, held);
   else
@@ -735,9 +732,8 @@ int vit_head_loss_bwd(vit_handle h, const float* last_hidden, const float* W, co
   VIT_CHECK(last_hidden && W && logits && labels && dloss && dlast_hidden && dW && db, VIT_ERR_ARG,
             "vit_head_loss_bwd: null pointer");
   VIT_CHECK(B > 0 && T > 0 && D > 0 && C > 0, VIT_ERR_ARG, "vit_head_loss_bwd: B=%d T=%d D=%d C=%d", B, T, D, C);
-  size_t wsb = 0;
-  float* dlog = (float*)ctx_workspace(h, &wsb);
-  VIT_CHECK(dlog && wsb >= (size_t)B * C * 4, VIT_ERR_WORKSPACE, "vit_head_loss_bwd: workspace too small");
+  float* dlog = (float*)ctx_claim(h, (size_t)B * C * 4, "vit_head_loss_bwd");
+  if (!dlog) return VIT_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   // a kernel, not hipMemsetAsync: inside a captured hipGraph the memset node did not reliably run before the kernels that
   // follow it (replays kept stale rows), and a fill kernel is ordered like every other node
@@ -755,9 +751,8 @@ int vit_head_loss_bwd(vit_handle h, const float* last_hidden, const float* W, co
 static int grad_sqnorm_impl(vit_handle h, const float* g, int64_t n, float* out, int accumulate, vit_stream stream) {
   VIT_CHECK(g && out && n > 0, VIT_ERR_ARG, "vit_grad_sqnorm: bad arguments");
   const int blocks = grid_for(n / 4 + 1, 256, 1024);
-  size_t wsb = 0;
-  float* part = (float*)ctx_workspace(h, &wsb);
-  VIT_CHECK(part && wsb >= (size_t)blocks * 4, VIT_ERR_WORKSPACE, "vit_grad_sqnorm: workspace too small");
+  float* part = (float*)ctx_claim(h, (size_t)blocks * 4, "vit_grad_sqnorm");
+  if (!part) return VIT_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(sqnorm_stage1_kernel, dim3(blocks), dim3(256), 0, st, g, (long)n, part);
   VIT_LAUNCH_CHECK();

@@ -496,10 +496,10 @@ __global__ void add_into_kernel(float* __restrict__ C, long ldc, const float* __
   }
 }
 
-void* ctx_workspace(vit_handle h, size_t* bytes);
 void* ctx_reserve_tail(vit_handle h, size_t bytes);   // api.hip
 void ctx_release_tail(vit_handle h);
 int gemm2_try_launch(vit_handle h, const vit_gemm_desc* d, hipStream_t st, int* rc);  // gemm2.hip
+bool gemm2_ws_bytes(vit_handle h, const vit_gemm_desc* d, size_t* bytes);
 
 int launch_splitk_reduce(const float* slab, float* C, long ldc, int M, int N, int splits, float alpha, int accumulate,
                          hipStream_t st) {
@@ -519,17 +519,18 @@ struct KRows { int stride, rows; };
 int gemm_launch(vit_handle h, const vit_gemm_desc* d, hipStream_t st, int k_row_stride = 0, int k_rows = 0);
 static int gemm_launch_core(vit_handle h, const vit_gemm_desc* d, hipStream_t st, KRows kr = {0, 0});
 
+static size_t round256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+
 // grad_accumulate with BOTH outputs of one descriptor being parameter gradients (an f32 C that accumulates and colsum_out):
 // the column sums are those of the NEW product, which an accumulated C no longer holds.  The product goes to a scratch matrix
 // at the end of the workspace in overwrite mode (the same kernels as a plain call: `new` bit for bit), its column sums are
 // added into colsum_out, and one pass adds it into C.  The engine never issues this combination (its weight-gradient products
-// carry no column sums), so no weight matrix of a training step takes the extra pass.
+// carry no column sums), so no weight matrix of a training step takes the extra pass.  The scratch matrix is what such a call
+// needs on top of its stages' workspace (gemm_launch claims both).
+static size_t accum_scratch_bytes(const vit_gemm_desc* d) { return round256((size_t)d->M * d->N * sizeof(float)); }
 static int gemm_accumulate_with_colsum(vit_handle h, const vit_gemm_desc* d, hipStream_t st) {
-  VIT_CHECK(d->c_dtype == VIT_F32 && d->rows_per_batch == 0 && !d->rope_cos && !d->residual, VIT_ERR_ARG,
-            "vit_gemm: accumulate with colsum_out needs an f32 C and no row map, rope or residual");
-  const size_t bytes = (((size_t)d->M * d->N * sizeof(float)) + 255) & ~(size_t)255;
-  float* scr = (float*)ctx_reserve_tail(h, bytes);
-  VIT_CHECK(scr, VIT_ERR_WORKSPACE, "vit_gemm: accumulate with colsum_out needs %zu more workspace bytes", bytes);
+  float* scr = (float*)ctx_reserve_tail(h, accum_scratch_bytes(d));  // gemm_launch claimed it on top of the stages' need
+  VIT_CHECK(scr, VIT_ERR_WORKSPACE, "vit_gemm: the workspace's tail is already lent out");
   vit_gemm_desc t = *d;
   t.C = scr; t.ldc = d->N; t.accumulate = 0; t.colsum_out = nullptr;
   int rc = gemm_launch_core(h, &t, st);
@@ -543,38 +544,37 @@ static int gemm_accumulate_with_colsum(vit_handle h, const vit_gemm_desc* d, hip
   return VIT_OK;
 }
 
-int gemm_launch(vit_handle h, const vit_gemm_desc* d, hipStream_t st, int k_row_stride, int k_rows) {
-  g_colsum_fused = 0;
-  g_rope_fused = 0;
-  // vit_handle_set_option("grad_accumulate"): colsum_out is always a parameter gradient (a bias gradient); C is one iff the
-  // product has the weight-gradient form dW = dY^T X (a_trans, f32 C) -- a forward product or a dX of the fp32 path also has
-  // an f32 C, and activation gradients never accumulate.  OR-ed with the descriptor's own `accumulate`.
-  const int accum = d ? ctx_grad_accumulate(h) : 0;
-  vit_gemm_desc dd;
-  if (accum && d->a_trans && d->c_dtype == VIT_F32 && !d->accumulate) {
-    dd = *d;
-    dd.accumulate = 1;
-    d = &dd;
+// K slices of a product on the generic core (bk: rows of a K tile): how many, and rows per slice
+static void split_plan(const vit_gemm_desc* d, int bk, int* splits_out, int* kps_out) {
+  const int ktiles = cdiv(d->K, bk);
+  int splits = d->split_k;
+  if (splits < 0) {
+    const int tiles = cdiv(d->M, BM) * cdiv(d->N, BN);
+    splits = 1;
+    if (tiles < 256) splits = std::min(std::max(1, 512 / tiles), std::max(1, ktiles / 4));
   }
-  if (accum && d->accumulate && d->colsum_out) return gemm_accumulate_with_colsum(h, d, st);
-  if (d && d->rope_cos) {
-    VIT_CHECK(d->rope_sin && d->rope_T > 0 && d->rope_dh >= 8 && (d->rope_dh % 8) == 0 && d->rope_cols > 0 &&
-                  (d->rope_cols % (2 * d->rope_dh)) == 0 && d->rope_cols <= d->N && d->rows_per_batch == 0 && !d->colsum_out &&
-                  d->act == VIT_ACT_NONE && !d->residual && d->split_k <= 1 && d->dropout_p == 0.f,
-              VIT_ERR_ARG, "vit_gemm: rope needs sin, T > 0, head_dim %% 8 == 0, rope_cols = 2 x heads x head_dim <= N, and a "
-                           "projection (a bias is fine) without dropout, row map, column sums, residual or split-K: the pass "
-                           "behind a dropped-out product would rotate AFTER the dropout, which is not the reference's order");
-  }
-  int rc = gemm_launch_core(h, d, st, KRows{k_row_stride, k_rows});
-  if (rc == VIT_OK && d->rope_cos && !g_rope_fused)  // the core had no rotating epilogue for this shape: the separate pass
-    rc = vit_rope_qk(h, d->C, d->c_dtype, d->rope_cos, d->rope_sin, d->M, d->rope_T, d->rope_cols / (2 * d->rope_dh), d->rope_dh,
-                     d->ldc, 0, (vit_stream)st);
-  if (rc != VIT_OK || !d->colsum_out || g_colsum_fused) return rc;
-  VIT_CHECK(d->rows_per_batch == 0, VIT_ERR_ARG, "vit_gemm: colsum_out with a row map is not supported");
-  return vit_colsum(h, d->C, d->c_dtype, d->ldc, d->colsum_out, d->M, d->N, accum, (vit_stream)st);
+  if (splits < 1) splits = 1;
+  if (splits > ktiles) splits = ktiles;
+  const int kps = cdiv(ktiles, splits) * bk;
+  *splits_out = cdiv(d->K, kps);
+  *kps_out = kps;
 }
 
-static int gemm_launch_core(vit_handle h, const vit_gemm_desc* d, hipStream_t st, KRows kr) {
+// Workspace bytes of one (checked) product, the maximum over its stages: the split-K slabs of the core that runs it, by the plan
+// that core launches by, and for colsum_out the fused partials or the vit_colsum pass (both: the choice is the core's).
+static size_t gemm_ws_bytes(vit_handle h, const vit_gemm_desc* d) {
+  size_t need = 0;
+  const bool f32in = d->ab_dtype == VIT_F32;
+  if (f32in || !gemm2_ws_bytes(h, d, &need)) {
+    int splits, kps;
+    split_plan(d, f32in ? XBK : BK, &splits, &kps);
+    if (splits > 1) need = (size_t)splits * d->M * d->N * sizeof(float);
+  }
+  if (d->colsum_out) need = std::max(need, colsum_ws_bytes(d->M, d->N));
+  return need;
+}
+
+static int gemm_check_args(const vit_gemm_desc* d, KRows kr) {
   VIT_CHECK(d && d->A && d->B && d->C, VIT_ERR_ARG, "vit_gemm: null operand");
   VIT_CHECK(d->M > 0 && d->N > 0 && d->K > 0, VIT_ERR_ARG, "vit_gemm: empty problem M=%d N=%d K=%d", d->M, d->N, d->K);
   VIT_CHECK(d->ab_dtype == VIT_BF16 || d->ab_dtype == VIT_F32, VIT_ERR_ARG, "vit_gemm: bad ab_dtype");
@@ -607,6 +607,53 @@ static int gemm_launch_core(vit_handle h, const vit_gemm_desc* d, hipStream_t st
     VIT_CHECK(f32in && d->a_trans && d->b_trans && kr.rows > 0 &&
                   (unsigned long long)kr.rows * (unsigned long long)std::max(d->lda, d->ldb) * 4 < 0x7FFFFFF0ull,
               VIT_ERR_ARG, "vit_gemm: compact K rows need f32 operands, both transposed, below 2 GiB");
+  return VIT_OK;
+}
+
+int gemm_launch(vit_handle h, const vit_gemm_desc* d, hipStream_t st, int k_row_stride, int k_rows) {
+  g_colsum_fused = 0;
+  g_rope_fused = 0;
+  const KRows kr = {k_row_stride, k_rows};
+  int rc = gemm_check_args(d, kr);
+  if (rc != VIT_OK) return rc;
+  // vit_handle_set_option("grad_accumulate"): colsum_out is always a parameter gradient (a bias gradient); C is one iff the
+  // product has the weight-gradient form dW = dY^T X (a_trans, f32 C) -- a forward product or a dX of the fp32 path also has
+  // an f32 C, and activation gradients never accumulate.  OR-ed with the descriptor's own `accumulate`.
+  const int accum = ctx_grad_accumulate(h);
+  vit_gemm_desc dd;
+  if (accum && d->a_trans && d->c_dtype == VIT_F32 && !d->accumulate) {
+    dd = *d;
+    dd.accumulate = 1;
+    d = &dd;
+  }
+  const bool scratch = accum && d->accumulate && d->colsum_out;
+  if (scratch)
+    VIT_CHECK(d->c_dtype == VIT_F32 && d->rows_per_batch == 0 && !d->rope_cos && !d->residual, VIT_ERR_ARG,
+              "vit_gemm: accumulate with colsum_out needs an f32 C and no row map, rope or residual");
+  if (d->colsum_out) VIT_CHECK(d->rows_per_batch == 0, VIT_ERR_ARG, "vit_gemm: colsum_out with a row map is not supported");
+  if (d->rope_cos) {
+    VIT_CHECK(d->rope_sin && d->rope_T > 0 && d->rope_dh >= 8 && (d->rope_dh % 8) == 0 && d->rope_cols > 0 &&
+                  (d->rope_cols % (2 * d->rope_dh)) == 0 && d->rope_cols <= d->N && d->rows_per_batch == 0 && !d->colsum_out &&
+                  d->act == VIT_ACT_NONE && !d->residual && d->split_k <= 1 && d->dropout_p == 0.f,
+              VIT_ERR_ARG, "vit_gemm: rope needs sin, T > 0, head_dim %% 8 == 0, rope_cols = 2 x heads x head_dim <= N, and a "
+                           "projection (a bias is fine) without dropout, row map, column sums, residual or split-K: the pass "
+                           "behind a dropped-out product would rotate AFTER the dropout, which is not the reference's order");
+  }
+  // the whole call's workspace before its first launch: a call that returns VIT_ERR_WORKSPACE has written nothing
+  size_t need = gemm_ws_bytes(h, d);
+  if (scratch) need = round256(need) + accum_scratch_bytes(d);
+  if (need && !ctx_claim(h, need, "vit_gemm")) return VIT_ERR_WORKSPACE;
+  if (scratch) return gemm_accumulate_with_colsum(h, d, st);
+  rc = gemm_launch_core(h, d, st, kr);
+  if (rc == VIT_OK && d->rope_cos && !g_rope_fused)  // the core had no rotating epilogue for this shape: the separate pass
+    rc = vit_rope_qk(h, d->C, d->c_dtype, d->rope_cos, d->rope_sin, d->M, d->rope_T, d->rope_cols / (2 * d->rope_dh), d->rope_dh,
+                     d->ldc, 0, (vit_stream)st);
+  if (rc != VIT_OK || !d->colsum_out || g_colsum_fused) return rc;
+  return vit_colsum(h, d->C, d->c_dtype, d->ldc, d->colsum_out, d->M, d->N, accum, (vit_stream)st);
+}
+
+static int gemm_launch_core(vit_handle h, const vit_gemm_desc* d, hipStream_t st, KRows kr) {
+  const bool f32in = d->ab_dtype == VIT_F32;
   if (!f32in) {
     int rc2 = VIT_OK;  // tile-aligned problems go to the LDS-DMA / persistent core
     if (gemm2_try_launch(h, d, st, &rc2)) return rc2;
@@ -618,29 +665,15 @@ static int gemm_launch_core(vit_handle h, const vit_gemm_desc* d, hipStream_t st
   a.a_bs = a.b_bs = a.c_bs = 0;
   a.M = d->M; a.N = d->N; a.K = d->K;
   a.tiles_m = cdiv(d->M, BM); a.tiles_n = cdiv(d->N, BN);
-  const int bk = f32in ? XBK : BK;
-  const int ktiles = cdiv(d->K, bk);
-  int splits = d->split_k;
-  if (splits < 0) {
-    const int tiles = a.tiles_m * a.tiles_n;
-    splits = 1;
-    if (tiles < 256) splits = std::min(std::max(1, 512 / tiles), std::max(1, ktiles / 4));
-  }
-  if (splits < 1) splits = 1;
-  if (splits > ktiles) splits = ktiles;
-  int kps = cdiv(ktiles, splits) * bk;
-  splits = cdiv(d->K, kps);
+  int splits, kps;
+  split_plan(d, f32in ? XBK : BK, &splits, &kps);
   a.splits = splits; a.k_per_split = kps;
   a.slab = nullptr;
   if (splits > 1) {
     VIT_CHECK(d->c_dtype == VIT_F32 && !d->bias && d->act == VIT_ACT_NONE && d->dropout_p == 0.f && !d->residual &&
                   d->rows_per_batch == 0,
               VIT_ERR_ARG, "vit_gemm: split_k supports only alpha and an f32 C");
-    size_t wsb = 0;
-    void* ws = ctx_workspace(h, &wsb);
-    size_t need = (size_t)splits * d->M * d->N * 4;
-    VIT_CHECK(ws && wsb >= need, VIT_ERR_WORKSPACE, "vit_gemm: split-K needs %zu workspace bytes, have %zu", need, wsb);
-    a.slab = (float*)ws;
+    if (!(a.slab = (float*)ctx_claim(h, (size_t)splits * d->M * d->N * sizeof(float), "vit_gemm: split-K"))) return VIT_ERR_WORKSPACE;
   }
   a.bias = d->bias;
   a.aux_in = (const short*)d->aux_in; a.aux_out = (short*)d->aux_out; a.ldaux = d->ldaux;
@@ -653,7 +686,6 @@ static int gemm_launch_core(vit_handle h, const vit_gemm_desc* d, hipStream_t st
   a.alpha = d->alpha;
   a.act = d->act; a.c_dtype = d->c_dtype;
   a.drop = make_drop_h(h, d->dropout_p, d->seed, d->site);
-  if (a.drop.thr) VIT_CHECK((d->N % 2) == 0, VIT_ERR_ARG, "vit_gemm: dropout needs an even N");
   a.rpb = d->rows_per_batch; a.orb = d->out_batch_rows; a.roff = d->out_row_offset;
   a.drs = (a.drop.thr && d->drop_row_stride > 1) ? d->drop_row_stride : 1;
   a.krs = a.krs_rows = 0;

@@ -139,10 +139,9 @@ __device__ __forceinline__ void tile_epilogue(f32x4 (&acc)[WM][WN], char* scr, c
   }
 }
 
-// defined in gemm.hip / api.hip
+// defined in gemm.hip
 int launch_splitk_reduce(const float* slab, float* C, long ldc, int M, int N, int splits, float alpha, int accumulate,
                          hipStream_t st);
-void* ctx_workspace(vit_handle h, size_t* bytes);
 
 // Specialised epilogues of the ping-pong kernel (FAST): what the five hot GEMM kinds of a ViT layer need, with every
 // decision at compile time so that no load sits behind a runtime branch (hipcc waits vmcnt(0) after each such load,
@@ -762,17 +761,43 @@ static bool pp_shape_ok(long M, long N, long K, long lda, long ldb) {
   return true;
 }
 
-// returns 1 if handled (rc in *rc), 0 if the shape is not eligible
-int gemm2_try_launch(vit_handle h, const vit_gemm_desc* d, hipStream_t st, int* rc) {
-  if (!pp_shape_ok(d->M, d->N, d->K, d->lda, d->ldb)) return 0;
+// Does the ping-pong core run this (checked, bf16) product -- the generic core does otherwise -- and if so with which generic
+// epilogue and which K slices?  gemm2_try_launch launches by the answer; gemm2_ws_bytes sizes the workspace by it beforehand.
+static bool pp_plan(vit_handle h, const vit_gemm_desc* d, int* epi_out, int* splits_out, int* kps_out) {
+  if (!pp_shape_ok(d->M, d->N, d->K, d->lda, d->ldb)) return false;
   int epi = 0;
   if (d->act == VIT_ACT_GELU || d->act == VIT_ACT_GELU_GRAD) {
-    if (d->a_trans || d->b_trans) return 0;
+    if (d->a_trans || d->b_trans) return false;
     epi = 1;
   } else if (d->act == VIT_ACT_DGELU || d->act == VIT_ACT_MUL_AUX) {
-    if (d->a_trans || !d->b_trans) return 0;
+    if (d->a_trans || !d->b_trans) return false;
     epi = 2;
   }
+  int splits, kps;
+  pp_split_plan(ctx_num_cus(h), (d->M / 256) * (d->N / 256), d->K, d->split_k, &splits, &kps);
+  if (splits > 1 && !(d->c_dtype == VIT_F32 && !d->bias && d->act == VIT_ACT_NONE && d->dropout_p == 0.f && !d->residual &&
+                      d->rows_per_batch == 0)) return false;
+  if (d->accumulate && splits == 1 && !(d->c_dtype == VIT_F32 && !d->residual && d->rows_per_batch == 0)) return false;
+  *epi_out = epi; *splits_out = splits; *kps_out = kps;
+  return true;
+}
+// the column-sum partials of the epilogues that sum their own rows: two rows per tile row (one per 128-row wave block)
+static size_t pp_colsum_bytes(const vit_gemm_desc* d) { return (size_t)(d->M / 256) * 2 * d->N * sizeof(float); }
+
+// false: the generic core runs d.  Else the workspace bytes of the product here: its split-K slabs and, given colsum_out, the
+// partials above (claimed whichever epilogue is then chosen).
+bool gemm2_ws_bytes(vit_handle h, const vit_gemm_desc* d, size_t* bytes) {
+  int epi, splits, kps;
+  if (!pp_plan(h, d, &epi, &splits, &kps)) return false;
+  *bytes = splits > 1 ? (size_t)splits * d->M * d->N * sizeof(float) : 0;
+  if (d->colsum_out) *bytes = std::max(*bytes, pp_colsum_bytes(d));
+  return true;
+}
+
+// returns 1 if handled (rc in *rc), 0 if the shape is not eligible
+int gemm2_try_launch(vit_handle h, const vit_gemm_desc* d, hipStream_t st, int* rc) {
+  int epi, splits, kps;
+  if (!pp_plan(h, d, &epi, &splits, &kps)) return 0;
   const int slots = ctx_num_cus(h);  // one workgroup per CU
 
   Gemm2Args a;
@@ -781,32 +806,15 @@ int gemm2_try_launch(vit_handle h, const vit_gemm_desc* d, hipStream_t st, int* 
   a.M = d->M; a.N = d->N; a.K = d->K;
   a.tiles_m = d->M / 256; a.tiles_n = d->N / 256;
   const int ntile = a.tiles_m * a.tiles_n;
-  const int ktiles = d->K / 64;
-  int splits, kps;
-  pp_split_plan(slots, ntile, d->K, d->split_k, &splits, &kps);
   a.splits = splits; a.k_per_split = kps;
   a.slab = nullptr;
-  if (splits > 1) {
-    if (!(d->c_dtype == VIT_F32 && !d->bias && d->act == VIT_ACT_NONE && d->dropout_p == 0.f && !d->residual &&
-          d->rows_per_batch == 0)) return 0;
-    size_t wsb = 0;
-    void* ws = ctx_workspace(h, &wsb);
-    const size_t need = (size_t)splits * d->M * d->N * 4;
-    if (!ws || wsb < need) {
-      set_error("vit_gemm: split-K needs %zu workspace bytes, have %zu", need, wsb);
-      *rc = VIT_ERR_WORKSPACE;
-      return 1;
-    }
-    a.slab = (float*)ws;
-  }
+  *rc = VIT_ERR_WORKSPACE;  // what a refused claim below returns (gemm_launch has claimed the whole call's need already)
+  if (splits > 1 && !(a.slab = (float*)ctx_claim(h, (size_t)splits * d->M * d->N * sizeof(float), "vit_gemm: split-K"))) return 1;
   a.nblk = std::min(ntile, slots);
   a.bias = d->bias;
   a.aux_in = (const short*)d->aux_in; a.aux_out = (short*)d->aux_out; a.ldaux = d->ldaux;
   a.residual = d->residual; a.ldres = d->ldres;
-  if (d->accumulate && splits == 1) {
-    if (!(d->c_dtype == VIT_F32 && !d->residual && d->rows_per_batch == 0)) return 0;
-    a.residual = (const float*)d->C; a.ldres = d->ldc;
-  }
+  if (d->accumulate && splits == 1) { a.residual = (const float*)d->C; a.ldres = d->ldc; }
   a.alpha = d->alpha;
   a.rope_cos = d->rope_cos; a.rope_sin = d->rope_sin; a.rope_T = d->rope_T; a.rope_dh = d->rope_dh; a.rope_cols = d->rope_cols;
   a.act = d->act; a.c_dtype = d->c_dtype;
@@ -861,11 +869,8 @@ int gemm2_try_launch(vit_handle h, const vit_gemm_desc* d, hipStream_t st, int* 
       grid = dim3(a.nblk, splits);
     }
   }
-  if (d->colsum_out && (epi5 == 3 || epi5 == 5 || epi5 == 6)) {
-    size_t wsb = 0;
-    void* ws = ctx_workspace(h, &wsb);
-    if (ws && wsb >= (size_t)a.tiles_m * 2 * d->N * sizeof(float)) a.colsum_part = (float*)ws;
-  }
+  if (d->colsum_out && (epi5 == 3 || epi5 == 5 || epi5 == 6) &&
+      !(a.colsum_part = (float*)ctx_claim(h, pp_colsum_bytes(d), "vit_gemm: column sums"))) return 1;
   {
     const int at = epi ? 0 : d->a_trans, bt = epi == 1 ? 0 : (epi == 2 ? 1 : d->b_trans);
     snprintf(g_last_gemm, sizeof(g_last_gemm), "gemm3_kernel<%d, %d, %d, %d>", at, bt, epi5, 8);
@@ -1006,7 +1011,7 @@ extern "C" {
 int vit_linear_bwd_dw_rows(vit_handle h, const void* dy, int64_t ldy, const void* x, int64_t ldx, int dtype, float* dW,
                            int rows, int N, int K, int64_t row_stride, int64_t full_rows, vit_stream stream) {
   using namespace vit;
-  VIT_CHECK(h && dy && x && dW, VIT_ERR_ARG, "vit_linear_bwd_dw_rows: null pointer");
+  VIT_CHECK(dy && x && dW, VIT_ERR_ARG, "vit_linear_bwd_dw_rows: null pointer");
   VIT_CHECK(rows > 0 && N > 0 && K > 0 && row_stride >= 1 && full_rows >= (int64_t)(rows - 1) * row_stride + 1 &&
                 full_rows <= 0x7FFFFFFF && ldy >= N && ldx >= K,
             VIT_ERR_ARG, "vit_linear_bwd_dw_rows: rows=%d N=%d K=%d row_stride=%lld full_rows=%lld", rows, N, K,
@@ -1042,7 +1047,7 @@ int vit_linear_bwd_dw_rows(vit_handle h, const void* dy, int64_t ldy, const void
 int vit_colsum_rows(vit_handle h, const void* a, int a_dtype, int64_t lda, float* out, int rows, int cols, int64_t row_stride,
                     int64_t full_rows, vit_stream stream) {
   using namespace vit;
-  VIT_CHECK(h && a && out, VIT_ERR_ARG, "vit_colsum_rows: null pointer");
+  VIT_CHECK(a && out, VIT_ERR_ARG, "vit_colsum_rows: null pointer");
   VIT_CHECK(rows > 0 && cols > 0 && lda >= cols && row_stride >= 1 && full_rows >= (int64_t)(rows - 1) * row_stride + 1 &&
                 full_rows <= 0x7FFFFFFF,
             VIT_ERR_ARG, "vit_colsum_rows: rows=%d cols=%d row_stride=%lld full_rows=%lld", rows, cols, (long long)row_stride,
@@ -1051,14 +1056,12 @@ int vit_colsum_rows(vit_handle h, const void* a, int a_dtype, int64_t lda, float
   // the full tensor's column sums ride in the ping-pong epilogue iff the product that writes it is tile-aligned
   if (a_dtype == VIT_BF16 && pp_shape_ok(full_rows, cols, 64, 64, 64)) {  // K of that product: a multiple of 64 at these widths
     const int nblk = (int)(full_rows / 128);
-    size_t wsb = 0;
-    float* part = (float*)ctx_workspace(h, &wsb);
-    if (part && wsb >= (size_t)nblk * cols * sizeof(float)) {
-      hipLaunchKernelGGL(colsum_rows_part_kernel, dim3((unsigned)cdiv((long)nblk * cols, 256)), dim3(256), 0, st,
-                         (const short*)a, (long)lda, part, nblk, cols, rows, (int)row_stride);
-      VIT_LAUNCH_CHECK();
-      return launch_reduce_partials(part, nblk, cols, out, cols, out, ctx_grad_accumulate(h), st);
-    }
+    float* part = (float*)ctx_claim(h, (size_t)nblk * cols * sizeof(float), "vit_colsum_rows");
+    if (!part) return VIT_ERR_WORKSPACE;
+    hipLaunchKernelGGL(colsum_rows_part_kernel, dim3((unsigned)cdiv((long)nblk * cols, 256)), dim3(256), 0, st,
+                       (const short*)a, (long)lda, part, nblk, cols, rows, (int)row_stride);
+    VIT_LAUNCH_CHECK();
+    return launch_reduce_partials(part, nblk, cols, out, cols, out, ctx_grad_accumulate(h), st);
   }
   if (a_dtype == VIT_F32 && row_stride > 1)  // precision '32': vit_colsum's order over the full tensor (absent rows add nothing)
     return colsum_strided(h, a, a_dtype, lda, out, (int)full_rows, cols, row_stride, rows, ctx_grad_accumulate(h), st);

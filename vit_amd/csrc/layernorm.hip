@@ -8,7 +8,6 @@
 
 namespace vit {
 
-void* ctx_workspace(vit_handle h, size_t* bytes);
 
 // NV = float4 chunks per lane held in registers; supports D <= 256*NV
 // RES: 0 = plain; 1 / 2 = the row normalised is x + delta (delta bf16 / f32: the projection underneath a
@@ -287,10 +286,8 @@ static int ln_bwd_common(vit_handle h, const void* dy, int dy_dtype, const float
   const bool big = rows >= 256 * 16;
   const int threads = big ? 512 : 256;
   const int blocks = big ? 512 : std::min(cdiv(rows, 16), 1024);
-  size_t wsb = 0;
-  float* part = (float*)ctx_workspace(h, &wsb);
-  const size_t need = (size_t)blocks * np * D * sizeof(float);
-  VIT_CHECK(part && wsb >= need, VIT_ERR_WORKSPACE, "vit_layernorm_bwd: needs %zu workspace bytes, have %zu", need, wsb);
+  float* part = (float*)ctx_claim(h, (size_t)blocks * np * D * sizeof(float), "vit_layernorm_bwd");
+  if (!part) return VIT_ERR_WORKSPACE;
   int rc;
   if (dyn && dyn_dtype == VIT_BF16)
     rc = dy_dtype == VIT_BF16 ? ln_bwd_dispatch<1, 1>(dy, x, gamma, mean, rstd, dres, dx, part, rows, D, blocks, threads, dyn, drop, rm, st)

@@ -8,7 +8,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import _cabi
-from ._cabi import ACT_DGELU, ACT_GELU, ACT_GELU_GRAD, ACT_MUL_AUX, ACT_NONE, LOSS_CE, LOSS_L1, LOSS_MSE, VIT_BF16, VIT_F32, GemmDesc, check
+from ._cabi import ACT_DGELU, ACT_GELU, ACT_GELU_GRAD, ACT_MUL_AUX, ACT_NONE, LOSS_CE, LOSS_L1, LOSS_MSE, VIT_BF16, VIT_F32, GemmDesc
 
 _DT = {torch.float32: VIT_F32, torch.bfloat16: VIT_BF16}
 
@@ -60,18 +60,6 @@ NO_DROP: Dropout = (0.0, 0, 0)
 
 
 # ------------------------------------------------------------------------------------------------ GEMM
-def _splitk_slabs(M: int, N: int, K: int, split_k: int, dtype) -> int:
-    """Slabs a split-K product may write: `split_k` itself, or for -1 an upper bound over the automatic choices of both GEMM
-    cores (gemm.hip: K tiles of 64, of 32 for f32 operands; gemm2.hip).  The one place the wrappers size that workspace from."""
-    if split_k >= 0:
-        return max(1, split_k)
-    tiles = -(-M // 128) * -(-N // 128)
-    ktiles = -(-K // (32 if dtype == torch.float32 else 64))
-    n = min(max(1, 512 // tiles), max(1, ktiles // 4)) if tiles < 256 else 1
-    t2 = max(1, (M // 256) * max(1, N // 256))
-    return max(n, min(max(1, 256 // t2), max(1, -(-K // 64) // 8)) + 1)
-
-
 def gemm(a: torch.Tensor, b: torch.Tensor, *, M: int, N: int, K: int, a_trans: bool = False, b_trans: bool = False,
          lda: Optional[int] = None, ldb: Optional[int] = None, out: Optional[torch.Tensor] = None,
          out_dtype=torch.bfloat16, ldc: Optional[int] = None, alpha: float = 1.0, bias: Optional[torch.Tensor] = None,
@@ -108,15 +96,11 @@ def gemm(a: torch.Tensor, b: torch.Tensor, *, M: int, N: int, K: int, a_trans: b
     d.rows_per_batch, d.out_batch_rows, d.out_row_offset = row_map
     d.split_k = split_k
     d.accumulate = int(accumulate)
-    extra = 0  # bytes behind the kernels' own partials
     if colsum_out is not None:  # column sums of C (a bias gradient): fused into the epilogue or a vit_colsum pass
         _chk(colsum_out, torch.float32, "gemm colsum_out")
         if colsum_out.numel() != N:
             raise _cabi.VitError(f"gemm: colsum_out must have N={N} elements")
         d.colsum_out = colsum_out.data_ptr()
-        if h.options.get("grad_accumulate") and a_trans and out.dtype == torch.float32:
-            extra = M * N * 4 + 256  # an accumulating C beside column sums: the product's scratch matrix (vit_amd.h)
-        h.ensure_workspace(max(2 * (-(-M // 256)), 2048) * N * 4 + extra)
     if rope is not None:
         cos, sin, rT, rdh, rcols = rope
         _chk(cos, torch.float32, "gemm rope cos")
@@ -124,9 +108,7 @@ def gemm(a: torch.Tensor, b: torch.Tensor, *, M: int, N: int, K: int, a_trans: b
         if cos.numel() != rT * (rdh // 2) or sin.numel() != cos.numel():
             raise _cabi.VitError(f"gemm: rope tables must be [T={rT}, head_dim/2={rdh // 2}]")
         d.rope_cos, d.rope_sin, d.rope_T, d.rope_dh, d.rope_cols = cos.data_ptr(), sin.data_ptr(), int(rT), int(rdh), int(rcols)
-    if split_k != 0 and split_k != 1:
-        h.ensure_workspace(_splitk_slabs(M, N, K, split_k, a.dtype) * M * N * 4 + extra)
-    check(h.lib.vit_gemm(h.h, C.byref(d), _stream(a)), "vit_gemm")
+    h.call("vit_gemm", C.byref(d), _stream(a))
     return out
 
 
@@ -161,8 +143,8 @@ def layernorm_fwd(x, gamma, beta, eps: float, out_dtype=torch.bfloat16, out=None
     y = out if out is not None else torch.empty(x.shape, dtype=out_dtype, device=x.device)
     mean = mean if mean is not None else torch.empty(rows, dtype=torch.float32, device=x.device)
     rstd = rstd if rstd is not None else torch.empty(rows, dtype=torch.float32, device=x.device)
-    check(h.lib.vit_layernorm_fwd(h.h, x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), y.data_ptr(), _DT[y.dtype],
-                                  _ptr(mean), _ptr(rstd), rows, D, eps, _stream(x)), "vit_layernorm_fwd")
+    h.call("vit_layernorm_fwd", x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), y.data_ptr(), _DT[y.dtype], _ptr(mean),
+           _ptr(rstd), rows, D, eps, _stream(x))
     return y, mean, rstd
 
 
@@ -185,14 +167,12 @@ def layernorm_fwd_residual(x, delta, xsum, gamma, beta, eps: float, out_dtype=to
     if y.numel() != xsum.numel() or mean.numel() < rows or rstd.numel() < rows:
         raise _cabi.VitError("layernorm_fwd_residual: out / mean / rstd do not hold xsum's rows")
     if x_row_stride != 1:
-        check(h.lib.vit_layernorm_fwd_residual_rows(h.h, x.data_ptr(), x_row_stride, delta.data_ptr(), _DT[delta.dtype],
-                                                    xsum.data_ptr(), gamma.data_ptr(), beta.data_ptr(), y.data_ptr(),
-                                                    _DT[y.dtype], _ptr(mean), _ptr(rstd), rows, D, eps, _stream(x)),
-              "vit_layernorm_fwd_residual_rows")
+        h.call("vit_layernorm_fwd_residual_rows", x.data_ptr(), x_row_stride, delta.data_ptr(), _DT[delta.dtype],
+               xsum.data_ptr(), gamma.data_ptr(), beta.data_ptr(), y.data_ptr(), _DT[y.dtype], _ptr(mean), _ptr(rstd), rows,
+               D, eps, _stream(x))
         return y, mean, rstd
-    check(h.lib.vit_layernorm_fwd_residual(h.h, x.data_ptr(), delta.data_ptr(), _DT[delta.dtype], xsum.data_ptr(),
-                                           gamma.data_ptr(), beta.data_ptr(), y.data_ptr(), _DT[y.dtype], _ptr(mean),
-                                           _ptr(rstd), rows, D, eps, _stream(x)), "vit_layernorm_fwd_residual")
+    h.call("vit_layernorm_fwd_residual", x.data_ptr(), delta.data_ptr(), _DT[delta.dtype], xsum.data_ptr(),
+           gamma.data_ptr(), beta.data_ptr(), y.data_ptr(), _DT[y.dtype], _ptr(mean), _ptr(rstd), rows, D, eps, _stream(x))
     return y, mean, rstd
 
 
@@ -204,9 +184,8 @@ def layernorm_bwd(dy, x, gamma, mean, rstd, dres=None, dx=None, dgamma=None, dbe
     dx = dx if dx is not None else torch.empty_like(x)
     dgamma = dgamma if dgamma is not None else torch.empty(D, dtype=torch.float32, device=x.device)
     dbeta = dbeta if dbeta is not None else torch.empty(D, dtype=torch.float32, device=x.device)
-    check(h.lib.vit_layernorm_bwd(h.h, dy.data_ptr(), _DT[dy.dtype], x.data_ptr(), gamma.data_ptr(), mean.data_ptr(),
-                                  rstd.data_ptr(), _ptr(dres), dx.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(),
-                                  rows, D, _stream(x)), "vit_layernorm_bwd")
+    h.call("vit_layernorm_bwd", dy.data_ptr(), _DT[dy.dtype], x.data_ptr(), gamma.data_ptr(), mean.data_ptr(),
+           rstd.data_ptr(), _ptr(dres), dx.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), rows, D, _stream(x))
     return dx, dgamma, dbeta
 
 
@@ -217,10 +196,9 @@ def layernorm_bwd_fused(dy, x, gamma, mean, rstd, dres, dx, dgamma, dbeta, dyn, 
     D = x.shape[-1]
     rows = x.numel() // D
     p, seed, site = dropout
-    check(h.lib.vit_layernorm_bwd_fused(h.h, dy.data_ptr(), _DT[dy.dtype], x.data_ptr(), gamma.data_ptr(),
-                                        mean.data_ptr(), rstd.data_ptr(), _ptr(dres), dx.data_ptr(), dgamma.data_ptr(),
-                                        dbeta.data_ptr(), rows, D, dyn.data_ptr(), _DT[dyn.dtype], dbias.data_ptr(), p, seed,
-                                        site, _stream(x)), "vit_layernorm_bwd_fused")
+    h.call("vit_layernorm_bwd_fused", dy.data_ptr(), _DT[dy.dtype], x.data_ptr(), gamma.data_ptr(), mean.data_ptr(),
+           rstd.data_ptr(), _ptr(dres), dx.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), rows, D, dyn.data_ptr(),
+           _DT[dyn.dtype], dbias.data_ptr(), p, seed, site, _stream(x))
     return dx, dgamma, dbeta, dyn, dbias
 
 
@@ -248,12 +226,10 @@ def layernorm_bwd_rows(dy, x, gamma, mean, rstd, dres, dx, dgamma, dbeta, dyn=No
         full_rows = (rows - 1) * row_stride + 1 if full_rows is None else full_rows
         if dres_row_stride or -(-full_rows // row_stride) != rows:
             raise _cabi.VitError("layernorm_bwd_rows: row_stride needs full_rows = the full tensor's rows and a dres like dx")
-        h.ensure_workspace(1024 * 3 * D * 4)
         rows = full_rows
-    check(h.lib.vit_layernorm_bwd_rows(h.h, dy.data_ptr(), _DT[dy.dtype], x.data_ptr(), gamma.data_ptr(), mean.data_ptr(),
-                                       rstd.data_ptr(), _ptr(dres), dres_row_stride, dx.data_ptr(), dgamma.data_ptr(),
-                                       dbeta.data_ptr(), rows, D, _ptr(dyn), _DT[dyn.dtype] if dyn is not None else VIT_BF16,
-                                       _ptr(dbias), p, seed, site, row_stride, _stream(x)), "vit_layernorm_bwd_rows")
+    h.call("vit_layernorm_bwd_rows", dy.data_ptr(), _DT[dy.dtype], x.data_ptr(), gamma.data_ptr(), mean.data_ptr(),
+           rstd.data_ptr(), _ptr(dres), dres_row_stride, dx.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), rows, D,
+           _ptr(dyn), _DT[dyn.dtype] if dyn is not None else VIT_BF16, _ptr(dbias), p, seed, site, row_stride, _stream(x))
     return dx
 
 
@@ -268,11 +244,8 @@ def linear_bwd_dw_rows(dy, x, out, *, row_stride: int, full_rows: int, ldx: Opti
     K = out.shape[1]
     if out.shape[0] != N or not out.is_contiguous() or not dy.is_contiguous():
         raise _cabi.VitError("linear_bwd_dw_rows: out must be a contiguous [N, K] tensor, dy contiguous")
-    if dy.dtype == torch.float32 and row_stride > 1:  # the full product's split-K slabs
-        h.ensure_workspace(_splitk_slabs(N, K, full_rows, -1, dy.dtype) * N * K * 4)
-    check(h.lib.vit_linear_bwd_dw_rows(h.h, dy.data_ptr(), N, x.data_ptr(), ldx if ldx is not None else K, _DT[dy.dtype],
-                                       out.data_ptr(), rows, N, K, row_stride, full_rows, _stream(dy)),
-          "vit_linear_bwd_dw_rows")
+    h.call("vit_linear_bwd_dw_rows", dy.data_ptr(), N, x.data_ptr(), ldx if ldx is not None else K, _DT[dy.dtype],
+           out.data_ptr(), rows, N, K, row_stride, full_rows, _stream(dy))
     return out
 
 
@@ -281,9 +254,8 @@ def colsum_rows(a, out, *, row_stride: int, full_rows: int):
     _chk(out, torch.float32, "colsum_rows out")
     h = _h(a)
     rows, cols = a.shape
-    h.ensure_workspace(max((full_rows // 128 + 1) * cols * 4, 2048 * cols * 4))
-    check(h.lib.vit_colsum_rows(h.h, a.data_ptr(), _DT[a.dtype], a.stride(0), out.data_ptr(), rows, cols, row_stride, full_rows,
-                                _stream(a)), "vit_colsum_rows")
+    h.call("vit_colsum_rows", a.data_ptr(), _DT[a.dtype], a.stride(0), out.data_ptr(), rows, cols, row_stride, full_rows,
+           _stream(a))
     return out
 
 
@@ -297,8 +269,8 @@ def attention_fwd(qkv, B: int, H: int, T: int, dh: int, scale: float, dropout: D
     p, seed, site = dropout
     if ctx_lo is not None:
         _chk(ctx_lo, ctx.dtype, "attention_fwd ctx_lo")
-    check(h.lib.vit_attention_fwd(h.h, qkv.data_ptr(), ctx.data_ptr(), _ptr(ctx_lo), lse.data_ptr(), _DT[qkv.dtype], B, H,
-                                  T, dh, scale, p, seed, site, _stream(qkv)), "vit_attention_fwd")
+    h.call("vit_attention_fwd", qkv.data_ptr(), ctx.data_ptr(), _ptr(ctx_lo), lse.data_ptr(), _DT[qkv.dtype], B, H, T, dh,
+           scale, p, seed, site, _stream(qkv))
     return ctx, lse
 
 
@@ -313,18 +285,16 @@ def attention_bwd(qkv, ctx, dctx, lse, B: int, H: int, T: int, dh: int, scale: f
     p, seed, site = dropout
     if colsum_out is not None:
         _chk(colsum_out, torch.float32, "attention_bwd colsum_out")
-        h.ensure_workspace(B * 16 * 3 * H * dh * 4)  # the library's true row count is AttnPlan::csum_rows (B * 21 at T = 577)
-    check(h.lib.vit_attention_bwd(h.h, qkv.data_ptr(), ctx.data_ptr(), _ptr(ctx_lo), dctx.data_ptr(), lse.data_ptr(),
-                                  delta.data_ptr(), dqkv.data_ptr(), _DT[qkv.dtype], B, H, T, dh, scale, p, seed, site,
-                                  _ptr(colsum_out), _stream(qkv)), "vit_attention_bwd")
+    h.call("vit_attention_bwd", qkv.data_ptr(), ctx.data_ptr(), _ptr(ctx_lo), dctx.data_ptr(), lse.data_ptr(),
+           delta.data_ptr(), dqkv.data_ptr(), _DT[qkv.dtype], B, H, T, dh, scale, p, seed, site, _ptr(colsum_out),
+           _stream(qkv))
     return dqkv
 
 
 def attention_probs(qkv, B: int, H: int, T: int, dh: int, scale: float):
     h = _h(qkv)
     probs = torch.empty((B, H, T, T), dtype=torch.float32, device=qkv.device)
-    check(h.lib.vit_attention_probs(h.h, qkv.data_ptr(), probs.data_ptr(), _DT[qkv.dtype], B, H, T, dh, scale,
-                                    _stream(qkv)), "vit_attention_probs")
+    h.call("vit_attention_probs", qkv.data_ptr(), probs.data_ptr(), _DT[qkv.dtype], B, H, T, dh, scale, _stream(qkv))
     return probs
 
 
@@ -336,7 +306,7 @@ def fold_add(dpatches, B: int, L: int, P: int, S: int, N: int, out=None):
         raise _cabi.VitError("fold_add: dpatches must hold B*N*P elements")
     out = out if out is not None else torch.empty((B, L), dtype=torch.float32, device=dpatches.device)
     h = _h(dpatches)
-    check(h.lib.vit_fold_add(h.h, dpatches.data_ptr(), out.data_ptr(), B, L, P, S, N, _stream(dpatches)), "vit_fold_add")
+    h.call("vit_fold_add", dpatches.data_ptr(), out.data_ptr(), B, L, P, S, N, _stream(dpatches))
     return out
 
 
@@ -348,8 +318,8 @@ def add_noise(flux, error, noise_level: float, seed: int, out=None):
         raise _cabi.VitError("add_noise: flux/error must have the same shape and a multiple of 4 elements")
     out = out if out is not None else torch.empty_like(flux)
     h = _h(flux)
-    check(h.lib.vit_add_noise(h.h, flux.data_ptr(), error.data_ptr(), out.data_ptr(), flux.numel(), float(noise_level),
-                              int(seed) & 0xFFFFFFFFFFFFFFFF, _stream(flux)), "vit_add_noise")
+    h.call("vit_add_noise", flux.data_ptr(), error.data_ptr(), out.data_ptr(), flux.numel(), float(noise_level),
+           int(seed) & 0xFFFFFFFFFFFFFFFF, _stream(flux))
     return out
 
 
@@ -362,8 +332,8 @@ def rope_qk(qkv, cos_half, sin_half, T: int, H: int, dh: int, inverse: bool = Fa
     if cos_half.shape[-1] != dh // 2 or cos_half.shape[0] < T or sin_half.shape != cos_half.shape:
         raise _cabi.VitError("rope_qk: tables must be [>= T, dh/2]")
     h = _h(qkv)
-    check(h.lib.vit_rope_qk(h.h, qkv.data_ptr(), _DT[qkv.dtype], cos_half.data_ptr(), sin_half.data_ptr(), qkv.shape[0], T,
-                            H, dh, qkv.shape[1], 1 if inverse else 0, _stream(qkv)), "vit_rope_qk")
+    h.call("vit_rope_qk", qkv.data_ptr(), _DT[qkv.dtype], cos_half.data_ptr(), sin_half.data_ptr(), qkv.shape[0], T, H, dh,
+           qkv.shape[1], 1 if inverse else 0, _stream(qkv))
     return qkv
 
 
@@ -372,8 +342,7 @@ def unfold_cast(x, P: int, S: int, N: int, out=None, out_dtype=torch.bfloat16):
     h = _h(x)
     B, L = x.shape
     out = out if out is not None else torch.empty((B * N, P), dtype=out_dtype, device=x.device)
-    check(h.lib.vit_unfold_cast(h.h, x.data_ptr(), out.data_ptr(), _DT[out.dtype], B, L, P, S, N, _stream(x)),
-          "vit_unfold_cast")
+    h.call("vit_unfold_cast", x.data_ptr(), out.data_ptr(), _DT[out.dtype], B, L, P, S, N, _stream(x))
     return out
 
 
@@ -382,8 +351,7 @@ def embed_finish(tokens, cls, pos=None, dropout: Dropout = NO_DROP):
     h = _h(tokens)
     B, T, D = tokens.shape
     p, seed, site = dropout
-    check(h.lib.vit_embed_finish(h.h, tokens.data_ptr(), cls.data_ptr(), _ptr(pos), B, T, D, p, seed, site,
-                                 _stream(tokens)), "vit_embed_finish")
+    h.call("vit_embed_finish", tokens.data_ptr(), cls.data_ptr(), _ptr(pos), B, T, D, p, seed, site, _stream(tokens))
     return tokens
 
 
@@ -393,8 +361,8 @@ def embed_finish_bwd(dtokens, dcls, dpos=None, dropout: Dropout = NO_DROP, dpatc
     B, T, D = dtokens.shape
     dpatch = dpatch if dpatch is not None else torch.empty((B * (T - 1), D), dtype=out_dtype, device=dtokens.device)
     p, seed, site = dropout
-    check(h.lib.vit_embed_finish_bwd(h.h, dtokens.data_ptr(), dpatch.data_ptr(), _DT[dpatch.dtype], dcls.data_ptr(),
-                                     _ptr(dpos), B, T, D, p, seed, site, 0, _stream(dtokens)), "vit_embed_finish_bwd")
+    h.call("vit_embed_finish_bwd", dtokens.data_ptr(), dpatch.data_ptr(), _DT[dpatch.dtype], dcls.data_ptr(), _ptr(dpos), B,
+           T, D, p, seed, site, 0, _stream(dtokens))
     return dpatch
 
 
@@ -406,8 +374,7 @@ def dropout_bwd_cast(dx, dropout: Dropout = NO_DROP, out=None, out_dtype=torch.b
     rows = dx.numel() // cols
     out = out if out is not None else torch.empty(dx.shape, dtype=out_dtype, device=dx.device)
     p, seed, site = dropout
-    check(h.lib.vit_dropout_bwd_cast(h.h, dx.data_ptr(), out.data_ptr(), _DT[out.dtype], rows, cols, p, seed, site,
-                                     _stream(dx)), "vit_dropout_bwd_cast")
+    h.call("vit_dropout_bwd_cast", dx.data_ptr(), out.data_ptr(), _DT[out.dtype], rows, cols, p, seed, site, _stream(dx))
     return out
 
 
@@ -415,15 +382,11 @@ def colsum(a, out=None, accumulate: bool = False):
     h = _h(a)
     rows, cols = a.shape
     out = out if out is not None else torch.empty(cols, dtype=torch.float32, device=a.device)
-    check(h.lib.vit_colsum(h.h, a.data_ptr(), _DT[a.dtype], a.stride(0), out.data_ptr(), rows, cols, int(accumulate),
-                           _stream(a)), "vit_colsum")
+    h.call("vit_colsum", a.data_ptr(), _DT[a.dtype], a.stride(0), out.data_ptr(), rows, cols, int(accumulate), _stream(a))
     return out
 
 
 # ------------------------------------------------------------------------------------------------ covariance statistics
-COV_WORKSPACE_BYTES = 4096 * 128 * 128 * 4  # upper bound of vit_cov_accumulate's slabs: slices x tiles < 2048 + 2048 tiles
-
-
 def cov_accumulate(x, mean, acc, *, rows: Optional[int] = None, cols: Optional[int] = None):
     """acc[L, L] += (x - mean)^T (x - mean) over x's rows, upper 128 x 128 tiles only (vit_cov_accumulate).  x: f32 [n, >= L]
     with unit column stride, used in place through its row stride; mean: f32 with at least L elements."""
@@ -436,9 +399,8 @@ def cov_accumulate(x, mean, acc, *, rows: Optional[int] = None, cols: Optional[i
     L = x.shape[1] if cols is None else cols
     if n > x.shape[0] or L > x.shape[1] or mean.numel() < L or tuple(acc.shape) != (L, L):
         raise _cabi.VitError(f"cov_accumulate: x {tuple(x.shape)}, mean {mean.numel()}, acc {tuple(acc.shape)} do not fit n={n} L={L}")
-    h.ensure_workspace(COV_WORKSPACE_BYTES)
-    check(h.lib.vit_cov_accumulate(h.h, x.data_ptr(), x.stride(0) if n > 1 else max(L, x.stride(0)), mean.data_ptr(),
-                                   acc.data_ptr(), n, L, _stream(x)), "vit_cov_accumulate")
+    h.call("vit_cov_accumulate", x.data_ptr(), x.stride(0) if n > 1 else max(L, x.stride(0)), mean.data_ptr(),
+           acc.data_ptr(), n, L, _stream(x))
     return acc
 
 
@@ -446,8 +408,8 @@ def cov_mean_finish(colsum, n_total: int, cols: Optional[int] = None):
     """colsum[:L] /= n_total in place (vit_cov_mean_finish): column sums -> the mean."""
     _chk(colsum, torch.float32, "cov_mean_finish colsum")
     h = _h(colsum)
-    check(h.lib.vit_cov_mean_finish(h.h, colsum.data_ptr(), colsum.numel() if cols is None else cols, int(n_total),
-                                    _stream(colsum)), "vit_cov_mean_finish")
+    h.call("vit_cov_mean_finish", colsum.data_ptr(), colsum.numel() if cols is None else cols, int(n_total),
+           _stream(colsum))
     return colsum
 
 
@@ -458,7 +420,7 @@ def cov_finish(acc, n_total: int, out=None):
     L = acc.shape[0]
     out = out if out is not None else torch.empty((L, L), dtype=torch.float32, device=acc.device)
     _chk(out, torch.float32, "cov_finish out")
-    check(h.lib.vit_cov_finish(h.h, acc.data_ptr(), out.data_ptr(), L, int(n_total), _stream(acc)), "vit_cov_finish")
+    h.call("vit_cov_finish", acc.data_ptr(), out.data_ptr(), L, int(n_total), _stream(acc))
     return out
 
 
@@ -466,7 +428,7 @@ def cast_f32_bf16(src, out=None):
     _chk(src, torch.float32, "cast_f32_bf16 src")
     h = _h(src)
     out = out if out is not None else torch.empty(src.shape, dtype=torch.bfloat16, device=src.device)
-    check(h.lib.vit_cast_f32_bf16(h.h, src.data_ptr(), out.data_ptr(), src.numel(), _stream(src)), "vit_cast_f32_bf16")
+    h.call("vit_cast_f32_bf16", src.data_ptr(), out.data_ptr(), src.numel(), _stream(src))
     return out
 
 
@@ -475,7 +437,7 @@ def cast_bf16_f32(src, out, scale: float = 1.0):
     _chk(src, torch.bfloat16, "cast_bf16_f32 src")
     _chk(out, torch.float32, "cast_bf16_f32 out")
     h = _h(src)
-    check(h.lib.vit_cast_bf16_f32(h.h, src.data_ptr(), out.data_ptr(), src.numel(), float(scale), _stream(src)), "vit_cast_bf16_f32")
+    h.call("vit_cast_bf16_f32", src.data_ptr(), out.data_ptr(), src.numel(), float(scale), _stream(src))
     return out
 
 
@@ -487,9 +449,8 @@ def head_loss_fwd(last_hidden, W, b, labels, loss_kind: int):
     Cn = W.shape[0]
     logits = torch.empty((B, Cn), dtype=torch.float32, device=last_hidden.device)
     loss = torch.zeros((), dtype=torch.float32, device=last_hidden.device) if labels is not None else None
-    check(h.lib.vit_head_loss_fwd(h.h, last_hidden.data_ptr(), W.data_ptr(), b.data_ptr(), _ptr(labels),
-                                  logits.data_ptr(), _ptr(loss), B, T, D, Cn, loss_kind, _stream(last_hidden)),
-          "vit_head_loss_fwd")
+    h.call("vit_head_loss_fwd", last_hidden.data_ptr(), W.data_ptr(), b.data_ptr(), _ptr(labels), logits.data_ptr(),
+           _ptr(loss), B, T, D, Cn, loss_kind, _stream(last_hidden))
     return logits, loss
 
 
@@ -500,9 +461,9 @@ def head_loss_bwd(last_hidden, W, logits, labels, dloss, loss_kind: int, dlast=N
     dlast = dlast if dlast is not None else torch.empty_like(last_hidden)
     dW = dW if dW is not None else torch.empty_like(W)
     db = db if db is not None else torch.empty(Cn, dtype=torch.float32, device=W.device)
-    check(h.lib.vit_head_loss_bwd(h.h, last_hidden.data_ptr(), W.data_ptr(), logits.data_ptr(), labels.data_ptr(),
-                                  dloss.data_ptr(), dlast.data_ptr(), dW.data_ptr(), db.data_ptr(), B, T, D, Cn,
-                                  loss_kind, 0, _stream(last_hidden)), "vit_head_loss_bwd")
+    h.call("vit_head_loss_bwd", last_hidden.data_ptr(), W.data_ptr(), logits.data_ptr(), labels.data_ptr(),
+           dloss.data_ptr(), dlast.data_ptr(), dW.data_ptr(), db.data_ptr(), B, T, D, Cn, loss_kind, 0,
+           _stream(last_hidden))
     return dlast, dW, db
 
 
@@ -512,8 +473,7 @@ def grad_sqnorm(g, out=None, accumulate: bool = False):
     _chk(g, torch.float32, "grad_sqnorm g")
     h = _h(g)
     out = out if out is not None else torch.empty(1, dtype=torch.float32, device=g.device)
-    fn = h.lib.vit_grad_sqnorm_acc if accumulate else h.lib.vit_grad_sqnorm
-    check(fn(h.h, g.data_ptr(), g.numel(), out.data_ptr(), _stream(g)), "vit_grad_sqnorm")
+    h.call("vit_grad_sqnorm_acc" if accumulate else "vit_grad_sqnorm", g.data_ptr(), g.numel(), out.data_ptr(), _stream(g))
     return out
 
 
@@ -521,5 +481,5 @@ def adamw_step(p, g, m, v, p_bf16, *, lr, beta1=0.9, beta2=0.999, eps=1e-8, weig
                max_norm=0.0, n: Optional[int] = None):
     h = _h(p)
     n = p.numel() if n is None else n
-    check(h.lib.vit_adamw_step(h.h, p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), _ptr(p_bf16), n, lr, beta1,
-                               beta2, eps, weight_decay, step, _ptr(sqnorm), max_norm, _stream(p)), "vit_adamw_step")
+    h.call("vit_adamw_step", p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), _ptr(p_bf16), n, lr, beta1, beta2, eps,
+           weight_decay, step, _ptr(sqnorm), max_norm, _stream(p))
