@@ -92,12 +92,15 @@ int vit_handle_set_option(vit_handle h, const char* name, int value);
 
 /* Per-step state in device memory, for a training step captured as a hipGraph (HIP streams and graphs instead of a tracing
  * compiler: kernel arguments are frozen at capture, so what changes from step to step must be read from memory).
- * `state`: 32 bytes, 16-byte aligned: { u32 key0, key1; f32 lr, bc1, rsqrt_bc2; u32 step; u32 pad[2] }, caller-owned.
+ * `state`: 32 bytes, 16-byte aligned: { u32 key0, key1; f32 lr, bc1, rsqrt_bc2; u32 step; f32 momentum; u32 pad },
+ * caller-owned.
  * While bound (NULL unbinds), every call through this handle that takes (dropout_p, seed, site) XORs the state's keys
  * into its dropout keys at kernel entry: the masks of a replay are those of (seed, site, step).  vit_step_advance (one
  * tiny kernel, first node of the captured step) does step += 1, derives the keys from (base_seed, step) and AdamW's
- * bias corrections from step; `lr` is the host's to write (a scheduler changes it between replays).
- * vit_adamw_step_dyn = vit_adamw_step with lr / bias corrections read from the state.
+ * bias corrections from step; `lr` and `momentum` are the host's to write (a scheduler changes them between replays: one-cycle
+ * cycles both on every step).
+ * vit_adamw_step_dyn = vit_adamw_step with lr / bias corrections read from the state; vit_adam_l2_step_dyn and
+ * vit_sgd_step_dyn (vit_amd_optim.h) read lr / bias corrections and lr / momentum from it in the same way.
  * Replaces what Lightning's loop hands torch per step: the generator advance behind nn.Dropout and optimizer.step()'s
  * step count (basemodule.py:230-251). */
 int vit_step_state_bind(vit_handle h, void* state);
@@ -351,5 +354,8 @@ int vit_adamw_step(vit_handle h, float* p, const float* g, float* m, float* v, v
 /* Covariance statistics of the training spectra (the file behind `warmup.cov_path`): vit_cov_accumulate, vit_cov_mean_finish,
  * vit_cov_finish.  Set-up time entry points, outside the training step: declared in their own header, part of this ABI. */
 #include "vit_amd_cov.h"
+/* The optimizer steps beside vit_adamw_step -- Adam with L2 decay and SGD, eager and captured (opt/optimizer.py:14-26,108;
+ * `opt.type` in configs/config.yaml) -- are declared in their own header, part of this ABI. */
+#include "vit_amd_optim.h"
 
 #endif /* VIT_AMD_H_ */

@@ -1,0 +1,174 @@
+"""What the fused SGD / Adam-L2 steps buy over the torch.optim fall-through they replace, and what the bare kernels reach.
+
+    python tools/optim_bench.py --parent DIR [--rounds 3] [--steps 30] [--warmup 10] [--out FILE.json]
+
+`DIR` is a built checkout of the parent commit (its own vit_amd/lib/libvit_amd.so).  This process never touches the GPU: it
+starts one fresh worker process per (tree, round), alternating parent / this tree, so both see the same box in the same
+minutes.  A worker imports `vit_amd` from ITS tree and times, with hipEvents around blocks of eager `Trainer.training_step`
+calls (ms per step, host launches included), bf16-mixed:
+
+    C1 at B = 64 and C3 at B = 256, for  opt: {type: SGD} | {type: SGD, lr_sch: onecycle} | {type: Adam, weight_decay: 0.01}
+    C1 at B = 64 with train.hip_graph: true for the same three (the parent warns and falls back to eager launches there)
+
+Per configuration the figure is the median over the rounds; min / max over the rounds is the spread to read it against.
+The last worker (this tree only) times the bare kernels at n = 85.8 M against the bytes the algorithm moves per parameter
+(shadow included): SGD 14 B, SGD with momentum 22 B, Adam-L2 30 B -- beside vit_adamw_step (30 B) in the same process."""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import statistics
+import subprocess
+import sys
+
+HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+OPTS = {"sgd": {"type": "SGD", "lr": 1e-2}, "sgd_onecycle": {"type": "SGD", "lr": 1e-2, "lr_sch": "onecycle"},
+        "adam_l2": {"type": "Adam", "lr": 1e-3, "weight_decay": 0.01}}
+CASES = [("C1", 64, False), ("C3", 256, False), ("C1", 64, True)]
+KERNEL_N = 85_800_000
+
+
+def _train_case(name, batch, graph, opt_name, steps, warmup, dev):
+    import warnings
+
+    import torch
+    from oracle import refvit  # seeded inputs only
+    from vit_amd.module import ViTLModule
+    from vit_amd.trainer import Trainer, seed_everything
+
+    seed_everything(42)
+    rc = refvit.named_config(name)
+    cfg = {"model": dict(name="vit", task_type="reg", image_size=rc.image_size, patch_size=rc.patch_size,
+                         hidden_size=rc.hidden_size, num_hidden_layers=rc.num_hidden_layers,
+                         num_attention_heads=rc.num_attention_heads, stride_size=rc.stride_size, proj_fn="SW"),
+           "train": dict(batch_size=batch, ep=1, precision="bf16-mixed", hip_graph=graph),
+           "loss": {"name": "mae"}, "opt": dict(OPTS[opt_name]), "data": {"param": "log_g", "num_samples": batch * 1000},
+           "noise": {"noise_level": 0}}
+    module = ViTLModule(config=cfg)
+    trainer = Trainer(cfg["train"], device=dev, verbose=False)
+    trainer._setup(module)
+    module.train()
+    b = tuple(t.to(dev) for t in refvit.make_inputs(rc, batch, 2))
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")  # the parent's "continuing with eager launches"
+        for i in range(warmup):
+            trainer.training_step(module, b, i)
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for i in range(steps):
+            trainer.training_step(module, b, i)
+        e1.record()
+        torch.cuda.synchronize()
+    return {"config": name, "batch": batch, "hip_graph": graph, "opt": opt_name, "optimizer": type(trainer.optimizer).__name__,
+            "graph_in_use": bool(trainer.use_graph), "ms_per_step": round(e0.elapsed_time(e1) / steps, 4)}
+
+
+def _kernels(dev):
+    import torch
+    import vit_amd.functional as vf
+
+    n = KERNEL_N
+    p = torch.randn(n, device=dev)
+    g = torch.randn(n, device=dev) * 1e-3
+    a, b = torch.zeros(n, device=dev), torch.zeros(n, device=dev)
+    pb = torch.empty(n, device=dev, dtype=torch.bfloat16)
+    sq = torch.ones(1, device=dev)
+    clip = dict(sqnorm=sq, max_norm=0.5)
+    calls = {
+        "sgd (14 B)": (14, lambda: vf.sgd_step(p, g, None, pb, lr=1e-2, **clip)),
+        "sgd momentum (22 B)": (22, lambda: vf.sgd_step(p, g, a, pb, lr=1e-2, momentum=0.9, weight_decay=0.01, **clip)),
+        "sgd nesterov (22 B)": (22, lambda: vf.sgd_step(p, g, a, pb, lr=1e-2, momentum=0.9, weight_decay=0.01, nesterov=True, **clip)),
+        "adam_l2 (30 B)": (30, lambda: vf.adam_l2_step(p, g, a, b, pb, lr=1e-3, weight_decay=0.01, step=3, **clip)),
+        "adamw (30 B)": (30, lambda: vf.adamw_step(p, g, a, b, pb, lr=1e-3, weight_decay=0.01, step=3, **clip)),
+    }
+    out = []
+    for name, (nbytes, f) in calls.items():
+        f(); f()
+        torch.cuda.synchronize()
+        ts = []
+        for _ in range(7):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(); f(); f(); f(); e1.record()
+            torch.cuda.synchronize()
+            ts.append(e0.elapsed_time(e1) / 3 * 1e3)
+        t = statistics.median(ts)
+        out.append({"kernel": name, "n": n, "us": round(t, 1), "us_min": round(min(ts), 1), "us_max": round(max(ts), 1),
+                    "gb_per_s": round(n * nbytes / t / 1e3, 1)})
+    return out
+
+
+def worker(args):
+    root = os.path.abspath(args.root)
+    sys.path.insert(0, root)
+    os.chdir(root)
+    import torch
+
+    if not torch.cuda.is_available():
+        raise SystemExit("optim_bench.py times an MI355X; there is no GPU here and no fallback")
+    dev = torch.device("cuda", 0)
+    if args.worker == "kernels":
+        res = _kernels(dev)
+    else:
+        res = [_train_case(name, batch, graph, opt, args.steps, args.warmup, dev)
+               for name, batch, graph in CASES for opt in OPTS]
+    print("RESULT " + json.dumps(res), flush=True)
+
+
+def _spawn(root, what, args):
+    cmd = [sys.executable, os.path.abspath(__file__), "--worker", what, "--root", root, "--steps", str(args.steps),
+           "--warmup", str(args.warmup)]
+    env = {k: v for k, v in os.environ.items() if k != "VIT_AMD_LIB"}
+    r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=args.worker_timeout)
+    if r.returncode != 0:
+        raise SystemExit(f"worker {what} in {root} failed ({r.returncode}); nothing further is started:\n{r.stdout[-2000:]}\n{r.stderr[-3000:]}")
+    line = [l for l in r.stdout.splitlines() if l.startswith("RESULT ")][-1]
+    return json.loads(line[len("RESULT "):])
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--parent", default="", help="a built checkout of the parent commit")
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=30)
+    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--worker-timeout", type=int, default=240)
+    ap.add_argument("--out", default="")
+    ap.add_argument("--worker", default="", choices=["", "train", "kernels"])
+    ap.add_argument("--root", default=HERE)
+    args = ap.parse_args()
+    if args.worker:
+        return worker(args)
+    trees = ([("parent", os.path.abspath(args.parent))] if args.parent else []) + [("this", HERE)]
+    runs = {t: [] for t, _ in trees}
+    for rnd in range(args.rounds):
+        for tree, root in trees:
+            runs[tree].append(_spawn(root, "train", args))
+            print(f"[round {rnd}] {tree}: " + " ".join(f"{r['ms_per_step']:.2f}" for r in runs[tree][-1]), flush=True)
+    table = []
+    for i, (name, batch, graph) in enumerate((c, b, g) for c, b, g in CASES for _ in OPTS):
+        opt = list(OPTS)[i % len(OPTS)]
+        row = {"config": name, "batch": batch, "hip_graph": graph, "opt": opt}
+        for tree in runs:
+            ms = [r[i]["ms_per_step"] for r in runs[tree]]
+            row[tree] = {"optimizer": runs[tree][0][i]["optimizer"], "graph_in_use": runs[tree][0][i]["graph_in_use"],
+                         "ms_median": round(statistics.median(ms), 4), "ms_min": min(ms), "ms_max": max(ms), "ms_rounds": ms}
+        table.append(row)
+        print(f"{name} B={batch} graph={int(graph)} {opt:13s} " + "  ".join(
+            f"{t}: {row[t]['ms_median']:.3f} ms [{row[t]['ms_min']:.3f} .. {row[t]['ms_max']:.3f}] ({row[t]['optimizer']}"
+            f"{', graph' if row[t]['graph_in_use'] else ''})" for t in runs), flush=True)
+    kernels = _spawn(HERE, "kernels", args)
+    for k in kernels:
+        print(f"{k['kernel']:22s} n = {k['n'] / 1e6:.1f} M: {k['us']:8.1f} us [{k['us_min']:.1f} .. {k['us_max']:.1f}] = "
+              f"{k['gb_per_s']:.0f} GB/s", flush=True)
+    line = json.dumps({"optim_bench": {"steps": args.steps, "warmup": args.warmup, "rounds": args.rounds, "train": table,
+                                       "kernels": kernels}})
+    print(line)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()

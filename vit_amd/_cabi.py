@@ -97,6 +97,10 @@ _PROTOS = {
     "vit_grad_sqnorm": [_P, _P, _I64, _P, _P],
     "vit_grad_sqnorm_acc": [_P, _P, _I64, _P, _P],
     "vit_adamw_step": [_P, _P, _P, _P, _P, _P, _I64, _F, _F, _F, _F, _F, _I, _P, _F, _P],
+    "vit_sgd_step": [_P, _P, _P, _P, _P, _I64, _F, _F, _F, _I, _P, _F, _P],
+    "vit_sgd_step_dyn": [_P, _P, _P, _P, _P, _I64, _F, _I, _P, _F, _P],
+    "vit_adam_l2_step": [_P, _P, _P, _P, _P, _P, _I64, _F, _F, _F, _F, _F, _I, _P, _F, _P],
+    "vit_adam_l2_step_dyn": [_P, _P, _P, _P, _P, _P, _I64, _F, _F, _F, _F, _P, _F, _P],
 }
 _RESTYPES = {"vit_last_error": C.c_char_p, "vit_last_gemm_kernel": C.c_char_p, "vit_workspace_needed": C.c_size_t}
 
@@ -105,7 +109,7 @@ _lock = threading.Lock()
 
 
 def declared_symbols(header_path: str = HEADER_PATH):
-    """Every function the C header declares, the headers it includes from its own directory (vit_amd_cov.h) included (used by
+    """Every function the C header declares, the headers it includes from its own directory (vit_amd_cov.h, vit_amd_optim.h) included (used by
     the CPU test that checks the library exports them all)."""
     seen, names, todo = set(), set(), [os.path.abspath(header_path)]
     while todo:

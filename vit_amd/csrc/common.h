@@ -288,8 +288,8 @@ __device__ __forceinline__ void lds_dma4_s(const void* sbase /* wave-uniform */,
   asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %0, %1" ::"v"(voff), "s"(sbase), "s"(a) : "memory", "m0");
 }
 
-// the handle's bound per-step state (api.hip): [key0, key1, lr, bc1, rsqrt_bc2, step] in device memory, or NULL
-struct StepState { unsigned key0, key1; float lr, bc1, rsqrt_bc2; unsigned step; };
+// the handle's bound per-step state (api.hip): [key0, key1, lr, bc1, rsqrt_bc2, step, momentum, pad] in device memory, or NULL
+struct StepState { unsigned key0, key1; float lr, bc1, rsqrt_bc2; unsigned step; float momentum; unsigned pad; };
 const StepState* ctx_step_state(vit_handle h);
 int ctx_num_cus(vit_handle h);  // compute units of the handle's device (api.hip)
 // vit_handle_set_option("grad_accumulate"): non-zero = every parameter-gradient output of a call through this handle stores
@@ -310,6 +310,11 @@ static inline DropCfg make_drop_h(vit_handle h, float p, uint64_t seed, uint64_t
 }
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+// blocks of a grid-stride launch over n work items
+static inline int grid_for(long n, int block = 256, int cap = 4096) {
+  const long b = (n + block - 1) / block;
+  return (int)(b < 1 ? 1 : b > cap ? cap : b);
+}
 
 // out[c] (+)= sum_{k < nblk} part[k * stride + c]; columns [0, split) go to out0, [split, split2) to out1 (- split),
 // [split2, width) to out2 (- split2; split2 = 0: no third output).  64 columns x 16 row groups per block, fixed

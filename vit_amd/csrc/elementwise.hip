@@ -1,5 +1,6 @@
 // HBM-bound side kernels of the ViT step for gfx950: unfold+cast, embedding finish (CLS / pos-emb / dropout) and its
-// backward, dropout-backward cast, deterministic column sums (bias gradients), head + loss, global grad norm, AdamW.
+// backward, dropout-backward cast, deterministic column sums (bias gradients), head + loss, global grad norm (the optimizer
+// steps that consume it: optim.hip).
 // All are vectorised (8-16 B per lane), grid-stride, and free of float atomics (reference: deterministic=True).
 #include <algorithm>
 
@@ -9,10 +10,6 @@ namespace vit {
 
 int colsum_strided(vit_handle h, const void* a, int a_dtype, int64_t lda, float* out, int rows, int cols, int64_t row_stride,
                    int held, int accumulate, hipStream_t st);
-
-static inline int grid_for(long n, int block = 256, int cap = 4096) {
-  return (int)std::max<long>(1, std::min<long>((n + block - 1) / block, cap));
-}
 
 // ------------------------------------------------------------------------------------------ unfold + cast
 // patches[(b*N+n)*P + p] = bf16(x[b*L + n*S + p]); a window that does not fit entirely inside the signal is ALL zero:
@@ -387,7 +384,7 @@ __global__ void head_bwd_params_kernel(const float* __restrict__ last, const flo
   }
 }
 
-// ------------------------------------------------------------------------------------------ grad norm + AdamW
+// ------------------------------------------------------------------------------------------ grad norm
 __global__ __launch_bounds__(256) void sqnorm_stage1_kernel(const float* __restrict__ g, long n, float* __restrict__ part) {
   __shared__ float red[4];
   const long nv = n >> 2;
@@ -417,44 +414,6 @@ __global__ __launch_bounds__(256) void sqnorm_stage2_kernel(const float* __restr
     __syncthreads();
   }
   if (threadIdx.x == 0) out[0] = accumulate ? out[0] + red[0] : red[0];
-}
-
-// torch.optim.AdamW (single-tensor form): p *= 1 - lr*wd; m,v EMA; p -= (lr/bc1) * m / (sqrt(v)/sqrt(bc2) + eps)
-__global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                    float* __restrict__ m, float* __restrict__ v,
-                                                    short* __restrict__ pb, long n, float lr, float b1, float b2,
-                                                    float eps, float wd, float bc1, float rsqrt_bc2,
-                                                    const float* __restrict__ sqnorm, float max_norm) {
-  float clip = 1.f;
-  if (sqnorm) clip = fminf(1.f, max_norm / (sqrtf(sqnorm[0]) + 1e-6f));
-  const float step = lr / bc1, decay = 1.f - lr * wd;
-  const long nv = n >> 2;
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < nv; i += (long)gridDim.x * blockDim.x) {
-    f32x4 pp = *(const f32x4*)(p + 4 * i);
-    const f32x4 gg = *(const f32x4*)(g + 4 * i) * clip;
-    f32x4 mm = *(const f32x4*)(m + 4 * i);
-    f32x4 vv = *(const f32x4*)(v + 4 * i);
-    mm = mm * b1 + gg * (1.f - b1);
-    vv = vv * b2 + gg * gg * (1.f - b2);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) pp[k] = pp[k] * decay - step * mm[k] / (sqrtf(vv[k]) * rsqrt_bc2 + eps);
-    *(f32x4*)(p + 4 * i) = pp;
-    *(f32x4*)(m + 4 * i) = mm;
-    *(f32x4*)(v + 4 * i) = vv;
-    if (pb) {
-      u32x2 pk = {pack2bf(pp[0], pp[1]), pack2bf(pp[2], pp[3])};
-      *(u32x2*)(pb + 4 * i) = pk;
-    }
-  }
-  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
-    const long i = (nv << 2) + threadIdx.x;
-    const float gg = g[i] * clip;
-    const float mm = m[i] * b1 + gg * (1.f - b1);
-    const float vv = v[i] * b2 + gg * gg * (1.f - b2);
-    const float pp = p[i] * decay - step * mm / (sqrtf(vv) * rsqrt_bc2 + eps);
-    p[i] = pp; m[i] = mm; v[i] = vv;
-    if (pb) pb[i] = f2bf(pp);
-  }
 }
 
 // ---- backward of the tokenizer's unfold (tokenization.py:43-49 / the Conv1d windows of :66-69) for a TRAINABLE input
@@ -768,7 +727,7 @@ int vit_grad_sqnorm_acc(vit_handle h, const float* g, int64_t n, float* out, vit
 }
 
 // ---- per-step state in device memory (hipGraph replays): one thread advances the step counter and derives from it the
-// dropout keys of the step and AdamW's bias corrections; lr is whatever the host last wrote into the state
+// dropout keys of the step and Adam's bias corrections; lr and momentum are whatever the host last wrote into the state
 __global__ void step_advance_kernel(StepState* s, unsigned long long base_seed, float b1, float b2) {
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     const unsigned step = s->step + 1;
@@ -784,73 +743,12 @@ __global__ void step_advance_kernel(StepState* s, unsigned long long base_seed, 
     s->step = step;
   }
 }
-__global__ __launch_bounds__(256) void adamw_dyn_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                        float* __restrict__ m, float* __restrict__ v,
-                                                        short* __restrict__ pb, long n, const StepState* __restrict__ st,
-                                                        float b1, float b2, float eps, float wd,
-                                                        const float* __restrict__ sqnorm, float max_norm) {
-  float clip = 1.f;
-  if (sqnorm) clip = fminf(1.f, max_norm / (sqrtf(sqnorm[0]) + 1e-6f));
-  const float lr = st->lr, rsqrt_bc2 = st->rsqrt_bc2;
-  const float step = lr / st->bc1, decay = 1.f - lr * wd;
-  const long nv = n >> 2;
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < nv; i += (long)gridDim.x * blockDim.x) {
-    f32x4 pp = *(const f32x4*)(p + 4 * i);
-    const f32x4 gg = *(const f32x4*)(g + 4 * i) * clip;
-    f32x4 mm = *(const f32x4*)(m + 4 * i);
-    f32x4 vv = *(const f32x4*)(v + 4 * i);
-    mm = mm * b1 + gg * (1.f - b1);
-    vv = vv * b2 + gg * gg * (1.f - b2);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) pp[k] = pp[k] * decay - step * mm[k] / (sqrtf(vv[k]) * rsqrt_bc2 + eps);
-    *(f32x4*)(p + 4 * i) = pp;
-    *(f32x4*)(m + 4 * i) = mm;
-    *(f32x4*)(v + 4 * i) = vv;
-    if (pb) {
-      u32x2 pk = {pack2bf(pp[0], pp[1]), pack2bf(pp[2], pp[3])};
-      *(u32x2*)(pb + 4 * i) = pk;
-    }
-  }
-  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
-    const long i = (nv << 2) + threadIdx.x;
-    const float gg = g[i] * clip;
-    const float mm = m[i] * b1 + gg * (1.f - b1);
-    const float vv = v[i] * b2 + gg * gg * (1.f - b2);
-    const float pp = p[i] * decay - step * mm / (sqrtf(vv) * rsqrt_bc2 + eps);
-    p[i] = pp; m[i] = mm; v[i] = vv;
-    if (pb) pb[i] = f2bf(pp);
-  }
-}
 
 int vit_step_advance(vit_handle h, uint64_t base_seed, float beta1, float beta2, vit_stream stream) {
   const StepState* st = ctx_step_state(h);
   VIT_CHECK(st, VIT_ERR_ARG, "vit_step_advance: no step state bound (vit_step_state_bind)");
   hipLaunchKernelGGL(step_advance_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, const_cast<StepState*>(st),
                      (unsigned long long)base_seed, beta1, beta2);
-  VIT_LAUNCH_CHECK();
-  return VIT_OK;
-}
-
-int vit_adamw_step_dyn(vit_handle h, float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, float beta1,
-                       float beta2, float eps, float weight_decay, const float* sqnorm, float max_norm, vit_stream stream) {
-  const StepState* st = ctx_step_state(h);
-  VIT_CHECK(st, VIT_ERR_ARG, "vit_adamw_step_dyn: no step state bound (vit_step_state_bind)");
-  VIT_CHECK(p && g && m && v && n > 0, VIT_ERR_ARG, "vit_adamw_step_dyn: bad arguments");
-  hipLaunchKernelGGL(adamw_dyn_kernel, dim3(grid_for(n / 4 + 1)), dim3(256), 0, (hipStream_t)stream, p, g, m, v,
-                     (short*)p_bf16, (long)n, st, beta1, beta2, eps, weight_decay, sqnorm, max_norm);
-  VIT_LAUNCH_CHECK();
-  return VIT_OK;
-}
-
-int vit_adamw_step(vit_handle h, float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, float lr,
-                   float beta1, float beta2, float eps, float weight_decay, int step, const float* sqnorm,
-                   float max_norm, vit_stream stream) {
-  (void)h;
-  VIT_CHECK(p && g && m && v && n > 0 && step >= 1, VIT_ERR_ARG, "vit_adamw_step: bad arguments");
-  const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
-  hipLaunchKernelGGL(adamw_kernel, dim3(grid_for(n / 4 + 1)), dim3(256), 0, (hipStream_t)stream, p, g, m, v,
-                     (short*)p_bf16, (long)n, lr, beta1, beta2, eps, weight_decay, (float)bc1,
-                     (float)(1.0 / sqrt(bc2)), sqnorm, max_norm);
   VIT_LAUNCH_CHECK();
   return VIT_OK;
 }

@@ -483,3 +483,21 @@ def adamw_step(p, g, m, v, p_bf16, *, lr, beta1=0.9, beta2=0.999, eps=1e-8, weig
     n = p.numel() if n is None else n
     h.call("vit_adamw_step", p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), _ptr(p_bf16), n, lr, beta1, beta2, eps,
            weight_decay, step, _ptr(sqnorm), max_norm, _stream(p))
+
+
+def adam_l2_step(p, g, m, v, p_bf16, *, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, step=1, sqnorm=None,
+                 max_norm=0.0, n: Optional[int] = None):
+    """torch.optim.Adam with weight_decay as L2 in the (clipped) gradient; otherwise `adamw_step`."""
+    h = _h(p)
+    n = p.numel() if n is None else n
+    h.call("vit_adam_l2_step", p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), _ptr(p_bf16), n, lr, beta1, beta2, eps,
+           weight_decay, step, _ptr(sqnorm), max_norm, _stream(p))
+
+
+def sgd_step(p, g, buf, p_bf16, *, lr, momentum=0.0, weight_decay=0.0, nesterov=False, sqnorm=None, max_norm=0.0,
+             n: Optional[int] = None):
+    """torch.optim.SGD (dampening 0) over a flat buffer; `buf` (the momentum buffer) may be None when momentum == 0."""
+    h = _h(p)
+    n = p.numel() if n is None else n
+    h.call("vit_sgd_step", p.data_ptr(), g.data_ptr(), _ptr(buf), _ptr(p_bf16), n, lr, momentum, weight_decay, int(bool(nesterov)),
+           _ptr(sqnorm), max_norm, _stream(p))

@@ -1,10 +1,12 @@
 """Optimizer factory of the hot path: mirrors `OptModule` (reference src/opt/optimizer.py:1-173).
 
 Same config keys, same scheduler table, same Lightning-style return value ({optimizer, lr_scheduler{scheduler, monitor,
-...}}).  For a `MyViT` on an MI355X, 'adam'/'adamw' resolve to `FusedAdamW`: one HIP kernel over the flat parameter
-buffer that applies the global-norm clip coefficient, the AdamW update and the bf16 shadow refresh in a single pass
-(torch.optim.AdamW semantics, verified against it in tests/).  Any other optimizer type falls through to torch.optim
-exactly as in the reference (it then works on the `.grad` views the model's backward produces).
+...}}).  For a `MyViT` on an MI355X the three types the reference documents (`opt.type` in configs/config.yaml: 'Adam',
+'AdamW', 'SGD') resolve to a fused optimizer: one HIP kernel over the flat parameter buffer that applies the global-norm
+clip coefficient, the update and the bf16 shadow refresh in a single pass -- `FusedAdamW` (torch.optim.AdamW; with
+`adam_l2` torch.optim.Adam, whose weight decay is L2 in the gradient) and `FusedSGD` (torch.optim.SGD), each verified
+against its torch class in tests/.  Any other optimizer type falls through to torch.optim exactly as in the reference
+(src/opt/optimizer.py:14-26,108; it then works on the `.grad` views the model's backward produces).
 """
 from __future__ import annotations
 
@@ -14,15 +16,16 @@ import torch
 
 from . import functional as vf
 
-__all__ = ["OptModule", "FusedAdamW"]
+__all__ = ["OptModule", "FusedOptimizer", "FusedAdamW", "FusedSGD"]
 
 
-class FusedAdamW(torch.optim.Optimizer):
-    """AdamW over MyViT's flat buffers.  `step()` == torch.optim.AdamW.step(): parameters without a gradient (frozen ones,
-    the never-used pooler, everything when no backward ran) are left alone together with their moments, exactly as torch
-    skips them; `state_dict()` / `load_state_dict()` speak torch.optim.AdamW's format (per-parameter `step`, `exp_avg`,
-    `exp_avg_sq`, indexed in `model.parameters()` order), so optimizer state moves between this class and the reference's
-    torch optimizer through a Lightning checkpoint.
+class FusedOptimizer(torch.optim.Optimizer):
+    """What the fused optimizers over MyViT's flat buffers share; a subclass adds its state buffers and its kernel.
+
+    `step()` == the torch optimizer's: parameters without a gradient (frozen ones, the never-used pooler, everything when
+    no backward ran) are left alone together with their state, exactly as torch skips them.  Parameters that are not slices
+    of the engine's flat buffer (a trainable input preprocessor) are stepped by the same kernel on state buffers of their
+    own, and their gradients join the global clipping norm.
 
     Gradient clipping: either the caller clips `.grad` beforehand (Lightning's gradient_clip_val path; the grads are
     views of the flat buffer, so that is seen here), or `set_grad_clip(max_norm)` fuses clip_grad_norm_(max_norm) into the
@@ -31,20 +34,21 @@ class FusedAdamW(torch.optim.Optimizer):
     Under data parallelism (`attach_reducer`) the flat gradient buffer holds the rank-averaged gradient when `step()` runs;
     a `.grad` that is NOT the flat-buffer view (a hook or an accumulation replaced it) would silently overwrite that
     average with a local gradient, so it is an error there.  With a sharding reducer ('zero1') each rank updates only its
-    shard of every sharded bucket and the updated parameters are all-gathered."""
+    shard of every sharded bucket and the updated parameters are all-gathered.
 
-    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, adam_l2: bool = False):
+    A subclass provides: `_STATE` (attribute names of its flat state buffers, each None until allocated), `_ensure_state()`,
+    `_step_args(group, sqnorm)`, `_update(p, g, states, p_bf16, kw)`, `_extra_buffers(p)`; and for a captured step
+    (vit_amd/graph.py) `_graph_record()`, `_graph_update(...)`, optionally `_graph_betas()` / `_graph_signature()`."""
+
+    _STATE = ()
+
+    def __init__(self, model, defaults):
         self.model = model
         params = [p for p in model.parameters()]
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
-        # parameters that are not slices of the engine's flat buffer (a trainable input preprocessor): same AdamW kernel,
-        # own moment buffers, and their gradients join the global clipping norm
+        super().__init__(params, defaults)
         own = {id(p) for p in getattr(model, "_param_list", [])}
         self._extras = [p for p in params if id(p) not in own]
         self._extra_state = {}
-        self.adam_l2 = adam_l2
-        self._m = None
-        self._v = None
         self._step = 0
         self._clip: Optional[float] = None
         self._sq = None
@@ -57,16 +61,26 @@ class FusedAdamW(torch.optim.Optimizer):
     def attach_reducer(self, reducer):
         self._reducer = reducer
 
-    def _ensure_state(self):
+    def _flat_states(self):
+        """The allocated flat state buffers, in `_STATE` order (all of them or none)."""
+        bufs = [getattr(self, name) for name in self._STATE]
+        return [] if any(b is None for b in bufs) else bufs
+
+    def _ensure_flat(self, names):
+        """Zero-filled buffers like the engine's flat buffer for `names`; one that was loaded before the model moved to the
+        GPU is carried over."""
+        flat = self.model.engine.flat
+        for name in names:
+            cur = getattr(self, name)
+            if cur is None or cur.device != flat.device:
+                new = torch.zeros_like(flat)
+                if cur is not None:
+                    new.copy_(cur)
+                setattr(self, name, new)
+
+    def _ensure_sq(self):
         eng = self.model.engine
         eng._ensure_device_state()
-        if self._m is None or self._m.device != eng.flat.device:
-            m = torch.zeros_like(eng.flat)
-            v = torch.zeros_like(eng.flat)
-            if self._m is not None:  # state loaded before the model moved to the GPU
-                m.copy_(self._m)
-                v.copy_(self._v)
-            self._m, self._v = m, v
         if self._sq is None or self._sq.device != eng.flat.device:
             self._sq = torch.zeros(1, dtype=torch.float32, device=eng.flat.device)
 
@@ -131,21 +145,17 @@ class FusedAdamW(torch.optim.Optimizer):
                 vf.grad_sqnorm(p.grad.contiguous().view(-1), out=sq, accumulate=True)
             self.last_grad_norm = sq
         shadow = eng.shadow if eng.precision == "bf16" else None  # f32 mode has no bf16 copy to refresh
-        kw = dict(lr=float(g["lr"]), beta1=g["betas"][0], beta2=g["betas"][1], eps=g["eps"], weight_decay=g["weight_decay"],
-                  step=self._step, sqnorm=sq, max_norm=float(self._clip or 0.0))
+        kw = self._step_args(g, sq)
+        states = self._flat_states()
         for a, b in runs:
-            vf.adamw_step(eng.flat[a:b], eng.grads[a:b], self._m[a:b], self._v[a:b], None if shadow is None else shadow[a:b],
-                          **kw)
+            self._update(eng.flat[a:b], eng.grads[a:b], [s[a:b] for s in states], None if shadow is None else shadow[a:b], kw)
         if red is not None:
             red.all_gather_params(eng.flat)
             if shadow is not None:
                 vf.cast_f32_bf16(eng.flat, shadow)
         eng.mark_shadow_fresh()  # the kernel rewrote flat AND shadow through raw pointers
         for p in extras:
-            st = self._extra_state.get(id(p))
-            if st is None or st[0].device != p.device:
-                st = self._extra_state[id(p)] = (torch.zeros_like(p.data).view(-1), torch.zeros_like(p.data).view(-1))
-            vf.adamw_step(p.data.view(-1), p.grad.contiguous().view(-1), st[0], st[1], None, **kw)
+            self._update(p.data.view(-1), p.grad.contiguous().view(-1), self._extra_buffers(p), None, kw)
         return loss
 
     def _shard_runs(self, runs, red):
@@ -166,42 +176,141 @@ class FusedAdamW(torch.optim.Optimizer):
         super().zero_grad(set_to_none=True)
 
     def gather_sharded_state(self):
-        """Under the 'zero1' exchange a rank's moment buffers are current only inside its own shard of every sharded bucket.
+        """Under the 'zero1' exchange a rank's state buffers are current only inside its own shard of every sharded bucket.
         A checkpoint is written by rank 0 and read back by EVERY rank, so before `state_dict()` the shards are all-gathered
         into every rank's buffers (a collective: all ranks must call this; a no-op for the all-reduce exchange and for a
         single process).  Without it the other ranks resumed with zero moments (first update ~3x lr; ADVICE r2 #2)."""
         red = self._reducer
-        if red is None or getattr(red, "mode", "") != "zero1" or self._m is None or self._step == 0:
+        if red is None or getattr(red, "mode", "") != "zero1" or self._step == 0:
             return
-        red.all_gather_params(self._m)
-        red.all_gather_params(self._v)
+        for buf in self._flat_states():
+            red.all_gather_params(buf)
+
+    # ------------------------------------------------------------------ everything a step changes in here, for a caller that
+    # takes real steps and then undoes them (Trainer._snapshot / _restore, the warm-up steps of a graph capture)
+    def clone_state(self):
+        return {"step": self._step,
+                "flat": [None if getattr(self, n) is None else getattr(self, n).clone() for n in self._STATE],
+                "extra_state": {k: tuple(t.clone() for t in bufs) for k, bufs in self._extra_state.items()},
+                "extras": [p.detach().clone() for p in self._extras]}
+
+    def restore_state(self, saved):
+        """Buffers that existed at `clone_state()` are copied back IN PLACE (a captured graph holds their addresses); one
+        that did not exist then is dropped again."""
+        self._step = saved["step"]
+        for name, old in zip(self._STATE, saved["flat"]):
+            if old is None:
+                setattr(self, name, None)
+            else:
+                getattr(self, name).copy_(old)
+        self._extra_state = saved["extra_state"]
+        with torch.no_grad():
+            for p, q in zip(self._extras, saved["extras"]):
+                p.copy_(q)
+
+    # ------------------------------------------------------------------ the captured step (vit_amd/graph.py)
+    def _graph_betas(self):
+        """(beta1, beta2) for vit_step_advance's bias corrections."""
+        return 0.0, 0.0
+
+    def _graph_signature(self):
+        """What of this optimizer's set-up is frozen into a capture; `_graph_validate` raises ValueError when a replay would
+        no longer be the eager step."""
+        return None
+
+    def _graph_validate(self, signature):
+        pass
+
+    # ------------------------------------------------------------------ torch.optim-format state
+    def _param_slices(self):
+        """(index in param_groups[0]["params"], offset, numel, shape) of every trainable parameter in the flat buffer."""
+        lay = self.model.engine.layout
+        index = {id(p): i for i, p in enumerate(self.param_groups[0]["params"])}
+        for name, p in zip(self.model._param_names, self.model._param_list):
+            off, shape = lay.entries[name]
+            if off < lay.n_trainable:
+                yield index[id(p)], off, lay.numel(name), shape
+
+    def _groups_dict(self):
+        groups = []
+        for grp in self.param_groups:
+            d = {k: (list(v) if isinstance(v, tuple) else v) for k, v in grp.items() if k != "params"}
+            d["params"] = list(range(len(grp["params"])))
+            groups.append(d)
+        return groups
+
+    def _load_groups(self, sd):
+        for grp, src in zip(self.param_groups, sd.get("param_groups", [])):
+            for k, v in src.items():
+                if k != "params":
+                    grp[k] = tuple(v) if k == "betas" else v
+
+
+class FusedAdamW(FusedOptimizer):
+    """AdamW over MyViT's flat buffers (see FusedOptimizer).  `step()` == torch.optim.AdamW.step(); `adam_l2=True` makes it
+    torch.optim.Adam.step(): `weight_decay` is then L2 in the (clipped) gradient instead of a decoupled decay.
+    `state_dict()` / `load_state_dict()` speak torch.optim.AdamW's (= Adam's) format (per-parameter `step`, `exp_avg`,
+    `exp_avg_sq`, indexed in `model.parameters()` order), so optimizer state moves between this class and the reference's
+    torch optimizer through a Lightning checkpoint."""
+
+    _STATE = ("_m", "_v")
+
+    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, adam_l2: bool = False):
+        super().__init__(model, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+        self.adam_l2 = bool(adam_l2)
+        self._m = None
+        self._v = None
+
+    def _ensure_state(self):
+        self._ensure_sq()
+        self._ensure_flat(self._STATE)
+
+    def _step_args(self, g, sq):
+        return dict(lr=float(g["lr"]), beta1=g["betas"][0], beta2=g["betas"][1], eps=g["eps"], weight_decay=g["weight_decay"],
+                    step=self._step, sqnorm=sq, max_norm=float(self._clip or 0.0))
+
+    def _update(self, p, g, states, p_bf16, kw):
+        (vf.adam_l2_step if self.adam_l2 else vf.adamw_step)(p, g, states[0], states[1], p_bf16, **kw)
+
+    def _extra_buffers(self, p):
+        st = self._extra_state.get(id(p))
+        if st is None or st[0].device != p.device:
+            st = self._extra_state[id(p)] = (torch.zeros_like(p.data).view(-1), torch.zeros_like(p.data).view(-1))
+        return st
+
+    def _graph_betas(self):
+        return tuple(self.param_groups[0]["betas"])
+
+    def _graph_record(self):
+        return {2: float(self.param_groups[0]["lr"])}
+
+    def _graph_update(self, h, n, p_bf16, sqnorm, stream):
+        """The update of flat[:n] inside a capture: lr and the bias corrections come from the bound record, everything else
+        is frozen at capture."""
+        from . import _cabi
+
+        eng, g = self.model.engine, self.param_groups[0]
+        name = "vit_adam_l2_step_dyn" if self.adam_l2 else "vit_adamw_step_dyn"
+        _cabi.check(getattr(h.lib, name)(h.h, eng.flat.data_ptr(), eng.grads.data_ptr(), self._m.data_ptr(), self._v.data_ptr(),
+                                         p_bf16, n, g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"], sqnorm,
+                                         float(self._clip or 0.0), stream), name)
 
     # ------------------------------------------------------------------ torch.optim.AdamW-format state
     def state_dict(self):
-        lay = self.model.engine.layout
         index = {id(p): i for i, p in enumerate(self.param_groups[0]["params"])}
         state = {}
         if self._m is not None and self._step > 0:
-            for name, p in zip(self.model._param_names, self.model._param_list):
-                off, shape = lay.entries[name]
-                if off >= lay.n_trainable:
-                    continue
-                n = lay.numel(name)
-                state[index[id(p)]] = {"step": torch.tensor(float(self._step)),
-                                       "exp_avg": self._m[off:off + n].detach().cpu().clone().view(shape),
-                                       "exp_avg_sq": self._v[off:off + n].detach().cpu().clone().view(shape)}
+            for i, off, n, shape in self._param_slices():
+                state[i] = {"step": torch.tensor(float(self._step)),
+                            "exp_avg": self._m[off:off + n].detach().cpu().clone().view(shape),
+                            "exp_avg_sq": self._v[off:off + n].detach().cpu().clone().view(shape)}
             for p in self._extras:
                 st = self._extra_state.get(id(p))
                 if st is not None:
                     state[index[id(p)]] = {"step": torch.tensor(float(self._step)),
                                            "exp_avg": st[0].detach().cpu().clone().view(p.shape),
                                            "exp_avg_sq": st[1].detach().cpu().clone().view(p.shape)}
-        groups = []
-        for grp in self.param_groups:
-            d = {k: (list(v) if isinstance(v, tuple) else v) for k, v in grp.items() if k != "params"}
-            d["params"] = list(range(len(grp["params"])))
-            groups.append(d)
-        return {"state": state, "param_groups": groups}
+        return {"state": state, "param_groups": self._groups_dict()}
 
     def load_state_dict(self, sd):
         if "state" not in sd:  # round-1 layout: flat moment buffers
@@ -230,10 +339,111 @@ class FusedAdamW(torch.optim.Optimizer):
                 self._extra_state[id(p)] = (st["exp_avg"].detach().clone().to(p.device).float().view(-1),
                                             st["exp_avg_sq"].detach().clone().to(p.device).float().view(-1))
         self._step = step
-        for grp, src in zip(self.param_groups, sd.get("param_groups", [])):
-            for k, v in src.items():
-                if k != "params":
-                    grp[k] = tuple(v) if k == "betas" else v
+        self._load_groups(sd)
+
+
+class FusedSGD(FusedOptimizer):
+    """SGD over MyViT's flat buffers (see FusedOptimizer).  `step()` == torch.optim.SGD.step() with dampening 0.
+    `param_groups[0]` carries torch SGD's keys, and `lr` and `momentum` are read from it on every step: a one-cycle scheduler
+    cycles both (it raises SGD's momentum from the reference's 0 to 0.85 .. 0.95).  The flat momentum buffer (and one per
+    parameter outside the flat buffer) is allocated, as zeros, by the first step that sees momentum != 0: with dampening 0 a
+    zero buffer gives exactly torch's first step (buf = g'), also for a parameter that is unfrozen mid-run.
+    `state_dict()` / `load_state_dict()` speak torch.optim.SGD's format (per-parameter `momentum_buffer`, indexed in
+    `model.parameters()` order, absent while no buffer exists)."""
+
+    _STATE = ("_buf",)
+
+    def __init__(self, model, lr=1e-3, momentum=0, dampening=0, weight_decay=0, nesterov=False):
+        if dampening != 0:
+            raise ValueError("FusedSGD supports dampening = 0 only (a zero momentum buffer then reproduces torch's first step)")
+        if lr < 0 or momentum < 0 or weight_decay < 0:
+            raise ValueError(f"FusedSGD: lr = {lr}, momentum = {momentum}, weight_decay = {weight_decay} must not be negative")
+        if nesterov and momentum <= 0:
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        super().__init__(model, dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov,
+                                     maximize=False, foreach=None, differentiable=False, fused=None))
+        self._buf = None
+
+    def _ensure_state(self):
+        self._ensure_sq()
+        if self._buf is not None or self.param_groups[0]["momentum"] != 0:
+            self._ensure_flat(self._STATE)
+
+    def _step_args(self, g, sq):
+        if g["dampening"] != 0 or g.get("maximize"):
+            raise ValueError("FusedSGD supports neither dampening nor maximize")
+        return dict(lr=float(g["lr"]), momentum=float(g["momentum"]), weight_decay=float(g["weight_decay"]),
+                    nesterov=bool(g["nesterov"]), sqnorm=sq, max_norm=float(self._clip or 0.0))
+
+    def _update(self, p, g, states, p_bf16, kw):
+        vf.sgd_step(p, g, states[0] if states and kw["momentum"] != 0 else None, p_bf16, **kw)
+
+    def _extra_buffers(self, p):
+        if self.param_groups[0]["momentum"] == 0:
+            return ()
+        st = self._extra_state.get(id(p))
+        if st is None or st[0].device != p.device:
+            st = self._extra_state[id(p)] = (torch.zeros_like(p.data).view(-1),)
+        return st
+
+    def _graph_record(self):
+        g = self.param_groups[0]
+        return {2: float(g["lr"]), 6: float(g["momentum"])}
+
+    def _graph_signature(self):
+        return self._buf is not None
+
+    def _graph_validate(self, had_buffer):
+        mu = self.param_groups[0]["momentum"]
+        if mu != 0 and not had_buffer:
+            raise ValueError(f"SGD's momentum became {mu} after the step was captured without a momentum buffer")
+        if mu == 0 and had_buffer:
+            raise ValueError("SGD's momentum became 0 after the step was captured with a momentum buffer")
+
+    def _graph_update(self, h, n, p_bf16, sqnorm, stream):
+        """The update of flat[:n] inside a capture: lr and momentum come from the bound record; weight decay, nesterov and
+        whether there is a momentum buffer at all are frozen at capture."""
+        from . import _cabi
+
+        eng, g = self.model.engine, self.param_groups[0]
+        if g["dampening"] != 0 or g.get("maximize"):
+            raise ValueError("FusedSGD supports neither dampening nor maximize")
+        _cabi.check(h.lib.vit_sgd_step_dyn(h.h, eng.flat.data_ptr(), eng.grads.data_ptr(),
+                                           None if self._buf is None else self._buf.data_ptr(), p_bf16, n,
+                                           float(g["weight_decay"]), int(bool(g["nesterov"])), sqnorm,
+                                           float(self._clip or 0.0), stream), "vit_sgd_step_dyn")
+
+    # ------------------------------------------------------------------ torch.optim.SGD-format state
+    def state_dict(self):
+        index = {id(p): i for i, p in enumerate(self.param_groups[0]["params"])}
+        state = {}
+        if self._buf is not None:
+            for i, off, n, shape in self._param_slices():
+                state[i] = {"momentum_buffer": self._buf[off:off + n].detach().cpu().clone().view(shape)}
+        for p in self._extras:
+            st = self._extra_state.get(id(p))
+            if st is not None:
+                state[index[id(p)]] = {"momentum_buffer": st[0].detach().cpu().clone().view(p.shape)}
+        return {"state": state, "param_groups": self._groups_dict()}
+
+    def load_state_dict(self, sd):
+        lay = self.model.engine.layout
+        params = self.param_groups[0]["params"]
+        names = {id(p): n for n, p in zip(self.model._param_names, self.model._param_list)}
+        self._buf, self._extra_state = None, {}
+        for idx, st in sd["state"].items():
+            buf = st.get("momentum_buffer")
+            if buf is None:
+                continue
+            p = params[int(idx)]
+            if id(p) in names:
+                if self._buf is None:
+                    self._buf = torch.zeros_like(self.model.engine.flat)
+                off, _ = lay.entries[names[id(p)]]
+                self._buf[off:off + lay.numel(names[id(p)])].copy_(buf.reshape(-1))
+            else:
+                self._extra_state[id(p)] = (buf.detach().clone().to(p.device).float().view(-1),)
+        self._load_groups(sd)
 
 
 # ---------------------------------------------------------------------------------------------------------------- factory
@@ -312,11 +522,13 @@ class OptModule:
     def _make_optimizer(self, model):
         from .specvit import MyViT
 
-        fused_ok = self.opt_type == "adamw" or (self.opt_type == "adam" and not self.weight_decay)
-        if isinstance(model, MyViT) and fused_ok:
+        if isinstance(model, MyViT) and self.opt_type in ("adam", "adamw"):
             # torch.optim.Adam's weight_decay is L2-in-the-gradient; with the reference's default weight_decay=0
-            # (optimizer.py:51) Adam == AdamW, and only then does 'adam' take the fused kernel
-            return FusedAdamW(model, lr=self.lr, weight_decay=self.weight_decay)
+            # (optimizer.py:51) Adam == AdamW, and only with a decay does 'adam' need the L2 form of the kernel
+            return FusedAdamW(model, lr=self.lr, weight_decay=self.weight_decay,
+                              adam_l2=self.opt_type == "adam" and bool(self.weight_decay))
+        if isinstance(model, MyViT) and self.opt_type == "sgd":
+            return FusedSGD(model, lr=self.lr, weight_decay=self.weight_decay)
         return self.opt_fns[self.opt_type](model.parameters(), lr=self.lr, weight_decay=self.weight_decay)
 
     def _warmup_length(self) -> Optional[int]:

@@ -35,7 +35,7 @@ from typing import Any, Dict, Iterable, Optional
 import torch
 
 from . import ddp as ddp_mod
-from .optimizer import FusedAdamW
+from .optimizer import FusedOptimizer
 
 __all__ = ["Trainer", "Checkpointer", "FreezeSchedule", "select_accelerator_and_devices", "get_training_strategy", "seed_everything"]
 
@@ -276,7 +276,7 @@ class Trainer:
             self.reducer = ddp_mod.make_reducer(self.exchange, eng, grad_dtype=self.grad_dtype,
                                                 max_bucket_elems=self.max_bucket_elems)
             eng.grad_ready_cb = self.reducer.bucket_ready
-        if isinstance(self.optimizer, FusedAdamW):
+        if isinstance(self.optimizer, FusedOptimizer):
             self.optimizer.set_grad_clip(self.gradient_clip_val)
             self.optimizer.attach_reducer(self.reducer)
         # freeze schedule of the input preprocessor (src/prepca/callbacks.py): warmup.freeze_epochs > 0 freezes it for
@@ -308,10 +308,8 @@ class Trainer:
                 "sched": copy.deepcopy(self.sched_cfg["scheduler"].state_dict()) if self.sched_cfg else None,
                 # every hyper-parameter of every group: a one-cycle scheduler also cycles Adam's beta1 / SGD's momentum per step
                 "groups": [copy.deepcopy({k: v for k, v in g.items() if k != "params"}) for g in opt.param_groups]}
-        if isinstance(opt, FusedAdamW):
-            snap["fused"] = (opt._step, None if opt._m is None else opt._m.clone(), None if opt._v is None else opt._v.clone(),
-                             {k: (a.clone(), b.clone()) for k, (a, b) in opt._extra_state.items()},
-                             [p.detach().clone() for p in opt._extras])
+        if isinstance(opt, FusedOptimizer):
+            snap["fused"] = opt.clone_state()  # step count, state buffers (Adam's moments / SGD's momentum), extras
         else:
             snap["opt"] = copy.deepcopy(opt.state_dict())
             snap["extra_params"] = [p.detach().clone() for p in module.parameters()]
@@ -329,16 +327,7 @@ class Trainer:
         if self.sched_cfg:
             self.sched_cfg["scheduler"].load_state_dict(snap["sched"])
         if "fused" in snap:
-            step, m, v, extra_state, extras = snap["fused"]
-            opt._step = step
-            if m is None:
-                opt._m = opt._v = None
-            else:
-                opt._m.copy_(m); opt._v.copy_(v)
-            opt._extra_state = extra_state
-            with torch.no_grad():
-                for p, q in zip(opt._extras, extras):
-                    p.copy_(q)
+            opt.restore_state(snap["fused"])
         else:
             opt.load_state_dict(snap["opt"])
             with torch.no_grad():
@@ -418,7 +407,7 @@ class Trainer:
                 if p.grad is not None:
                     torch.distributed.all_reduce(p.grad, op=torch.distributed.ReduceOp.SUM)
                     p.grad.div_(self.world)
-        if not isinstance(self.optimizer, FusedAdamW) and self.gradient_clip_val:
+        if not isinstance(self.optimizer, FusedOptimizer) and self.gradient_clip_val:
             torch.nn.utils.clip_grad_norm_([p for p in module.parameters() if p.grad is not None], self.gradient_clip_val)
         self.optimizer.step()
         if self.sched_cfg and self.sched_cfg.get("interval") == "step":
@@ -459,26 +448,27 @@ class Trainer:
     def _graph_step(self, module, batch):
         """One captured graph per (batch shape, precision), at most two kept (the full batch and an epoch's partial last
         batch; each holds its own activation arena).  What the capture cannot take -- another optimizer, a trainable input
-        preprocessor, on-the-fly noise -- falls back to eager launches for the rest of the run, with one warning."""
+        preprocessor, on-the-fly noise, an SGD momentum that appears after a capture without a momentum buffer -- falls back
+        to eager launches for the rest of the run, with one warning."""
         from .graph import GraphedTrainStep
 
         key = (tuple(batch[0].shape), module.model.engine.precision)
         if self._graphed is None:
             self._graphed = {}
         g = self._graphed.get(key)
-        if g is None:
-            try:
+        try:
+            if g is None:
                 g = GraphedTrainStep(module, self.optimizer, batch)  # capture (runs warm-up steps on this batch)
-            except (TypeError, ValueError) as e:
-                import warnings
+                while len(self._graphed) >= 2:
+                    self._graphed.pop(next(iter(self._graphed)))
+                self._graphed[key] = g
+            loss = g.step(batch)  # refuses (before it touches anything) what its capture no longer covers
+        except (TypeError, ValueError) as e:
+            import warnings
 
-                warnings.warn(f"train.hip_graph: {e}; continuing with eager launches")
-                self.use_graph = False
-                return self.training_step(module, batch, 0)
-            while len(self._graphed) >= 2:
-                self._graphed.pop(next(iter(self._graphed)))
-            self._graphed[key] = g
-        loss = g.step(batch)
+            warnings.warn(f"train.hip_graph: {e}; continuing with eager launches")
+            self.use_graph = False
+            return self.training_step(module, batch, 0)
         module.log(f"{module.loss_name}_loss", loss, on_step=True, on_epoch=True, prog_bar=True)
         if self.sched_cfg and self.sched_cfg.get("interval") == "step":
             self.sched_cfg["scheduler"].step()
