@@ -290,6 +290,30 @@ def test_dctx_cls_rows_between_the_cls_rows_are_never_written(dev):
     buf[other] = 0.0
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("tail", [False, True])
+@pytest.mark.parametrize("tag", ["l3", "ms"])
+def test_one_stream_and_two_streams_give_the_same_bits(dev, tag, tail):
+    """engine.overlap_dw moves the weight-gradient products (and nothing else) to a second HIP stream with a workspace of its
+    own: the kernels and their arguments are the same and each is deterministic, so a train-mode step in bf16-mixed leaves the
+    same loss, logits and gradient bits with one stream and with two.  `l3` is off the 256-aligned GEMM core; at `ms` the
+    weight gradients are multi-slice split-K products in the second handle's workspace, and with two layers every scratch
+    buffer of the backward is rewritten while a reader of it on the second stream may still exist."""
+    rc, sd, flux, labels, _, _ = case(tag)
+    model = build(rc, sd, dev, "bf16-mixed")
+    x, y = flux.to(dev), labels.to(dev)
+    eng, runs = model.engine, []
+    for overlap in (False, True):
+        eng.overlap_dw = overlap
+        runs.append(hip_pass(model, x, y, True, tail=tail))
+        assert runs[-1]["tail"] is tail
+        assert (eng.side_stream is not None) is overlap
+    one, two = runs
+    assert one["loss"] == two["loss"] and torch.equal(one["logits"], two["logits"])
+    for n in one["grads"]:
+        assert torch.equal(one["grads"][n], two["grads"][n]), n
+
+
 # ------------------------------------------------------------------ no GPU needed
 # every export of the parent's header with its parameter count: the CLS tail ADDS entry points and one descriptor field
 _EXPORTS = {

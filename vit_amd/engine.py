@@ -15,20 +15,34 @@ Data layout in HBM (one MI355X, 288 GB: nothing is recomputed or re-materialised
   CLS tail c_* : compact [B, .] twins of y / x1 / h2 / u / g / x[L] / last and their statistics (and of the backward's
            scratch): what the last layer computes behind its attention when only the head consumes it (see `cls_tail`).
 Dropout masks are regenerated from (seed, site) in backward; no mask is stored.
+
+A layer's tail -- out-projection, LN-after, FC1 + GELU, FC2 behind its attention -- is stated once per direction
+(`_tail_fwd`, `_tail_bwd`) and runs over a `Rows`: every token row, or the last layer's B CLS rows.
 """
 from __future__ import annotations
 
+import collections
 import math
 import os
 from typing import Callable, Dict, List, Optional, Tuple
 
 import torch
 
+from . import _cabi
 from . import functional as vf
 from ._cabi import ACT_GELU, LOSS_CE, LOSS_L1, LOSS_MSE, VitError
 from .config import ViTConfig
 
 ALIGN = 8  # elements; keeps every view 32-byte (f32) / 16-byte (bf16) aligned
+
+EMBED = "vit.embeddings."
+PROJ = EMBED + "patch_embeddings.projection"
+# the name stems of one encoder layer's parameters (+ ".weight" / ".bias"): ViTEngine.names[i].fc1 etc.
+LayerNames = collections.namedtuple("LayerNames", "ln1 q wo ln2 fc1 fc2")
+_LAYER_STEMS = LayerNames("layernorm_before", "attention.attention.query", "attention.output.dense", "layernorm_after",
+                          "intermediate.dense", "output.dense")
+# one slot of ViTEngine._arenas; rows = (the token rows, the CLS rows)
+Arena = collections.namedtuple("Arena", "key act tmp Mp rows")
 
 
 def resolved_loss(task_type: str, loss_name: str) -> Tuple[str, int]:
@@ -47,15 +61,15 @@ class ParamLayout:
     def __init__(self, cfg: ViTConfig):
         D, P, Fd, T = cfg.hidden_size, cfg.patch_size, cfg.intermediate_size, cfg.seq_len
         self.entries: Dict[str, Tuple[int, Tuple[int, ...]]] = {}
+        self._span: Dict[str, Tuple[int, int, Tuple[int, ...]]] = {}  # name -> (offset, offset + numel, shape): what view() needs
         self.layer_ranges: List[Tuple[int, int]] = []
         off = 0
 
         def add(name, shape):
             nonlocal off
-            n = 1
-            for s in shape:
-                n *= s
+            n = math.prod(shape)
             self.entries[name] = (off, tuple(shape))
+            self._span[name] = (off, off + n, tuple(shape))
             off += (n + ALIGN - 1) // ALIGN * ALIGN
 
         e = "vit.embeddings."
@@ -112,22 +126,59 @@ class ParamLayout:
         self.state_order = order
 
     def view(self, flat: torch.Tensor, name: str) -> torch.Tensor:
-        off, shape = self.entries[name]
-        n = 1
-        for s in shape:
-            n *= s
-        return flat[off:off + n].view(shape)
+        off, end, shape = self._span[name]
+        return flat[off:end].view(shape)
 
     def numel(self, name: str) -> int:
-        n = 1
-        for s in self.entries[name][1]:
-            n *= s
-        return n
+        return self._span[name][1] - self._span[name][0]
 
     def buckets(self) -> List[Tuple[int, int]]:
         """Gradient buckets in the order backward completes them: tail (final LN + head), layers L-1..0, embeddings."""
         return [(self.tail_start, self.n_trainable)] + list(reversed(self.layer_ranges)) + \
                [(self.embed_start, self.embed_end)]
+
+
+class Rows:
+    """The rows a run of row-wise kernels covers, with their buffers in one arena: every token row (stride 1), or the B rows
+    b*T the head consumes (stride T: the last layer's CLS tail).  Strided rows are READ in place from the full tensors (ctx,
+    the residual stream) and everything written for them is compact; their dropout masks and the order of their sums are
+    those of the rows' ORIGINAL positions k * stride among the full tensor's M (Mp with the GEMMs' zero pad rows) rows."""
+
+    def __init__(self, n: int, stride: int, M: int, Mp: int, act: dict, tmp: dict, c: str, dctx):
+        self.n, self.stride, self.M, self.Mp = n, stride, M, Mp  # n: the GEMM row count (Mp for the token rows)
+        for k in ("y", "x1", "h2", "u", "g", "mean2", "rstd2", "xL", "last", "meanF", "rstdF"):  # x1 ... rstd2: per layer slot
+            setattr(self, k, act[c + k])
+        for k in ("dy", "dy2", "dU", "dh", "dlast"):  # training arenas only
+            setattr(self, k, tmp.get(c + k))
+        self.dx = (tmp.get(c + "dxa"), tmp.get(c + "dxb"))  # the residual gradient's ping-pong pair
+        self.dctx = dctx  # where the out-projection's dX goes (its rows k * stride)
+        self.last2 = self.last.view(-1, self.last.shape[-1])
+
+
+class _SideHop:
+    """`with engine._on_side as side:` -- the hop onto the engine's second HIP stream: that stream waits for the main stream's
+    position, and the block's launches go to it through its own vit_handle (= its own split-K workspace).  `side` is that
+    stream, or None with the second stream off: the block then runs where it stands.  One object per engine, not re-entrant."""
+
+    def __init__(self, eng: "ViTEngine"):
+        self.eng, self._inner = eng, None
+
+    def __enter__(self):
+        eng = self.eng
+        side = eng.side_stream
+        if side is not None:
+            side.wait_stream(torch.cuda.current_stream(eng.flat.device))
+            self._inner = inner = (torch.cuda.stream(side), vf.use_handle(eng._side_handle))
+            inner[0].__enter__()
+            inner[1].__enter__()
+        return side
+
+    def __exit__(self, *exc):
+        inner, self._inner = self._inner, None
+        if inner is not None:
+            inner[1].__exit__(*exc)
+            inner[0].__exit__(*exc)
+        return False
 
 
 class ViTEngine:
@@ -156,10 +207,14 @@ class ViTEngine:
         self.shadow: Optional[torch.Tensor] = None
         self.grads: Optional[torch.Tensor] = None
         self._shadow_version = -1
+        self.names = [LayerNames(*(f"vit.encoder.layer.{i}.{s}" for s in _LAYER_STEMS)) for i in range(cfg.num_hidden_layers)]
         self._arena_key = None
-        self._arenas: Dict[bool, tuple] = {}  # train? -> (key, act, tmp, Mp): one arena for training, one for evaluation
+        self._arenas: Dict[bool, Arena] = {}  # train? -> its slot: one arena for training, one for evaluation
         self.act: Dict[str, object] = {}
         self.tmp: Dict[str, torch.Tensor] = {}
+        self._Mp = 0  # the current arena's GEMM row count
+        self._rows: Optional[Tuple[Rows, Rows]] = None  # the current arena's (token rows, CLS rows)
+        self._rope, self._rope_key = None, None
         self.precision = "f32"       # 'f32' (reference default precision='32') | 'bf16' (precision='bf16-mixed')
         self.base_seed = int(torch.initial_seed()) & 0x7FFFFFFFFFFFFFFF
         self.step_counter = 0
@@ -169,7 +224,8 @@ class ViTEngine:
         self._side_handle = None
         self._main_handle = None  # this engine's own vit_handle (workspace + launch geometry): see handle()
         self.reserve_cus = -1     # -1 = the process-wide vit_set_option value
-        self._side_reads: Dict[str, object] = {}
+        self._side_reads: Dict[int, object] = {}  # data_ptr of a scratch buffer -> event behind its last reader on the side stream
+        self._on_side = _SideHop(self)
         # True / False / "auto": the second stream pays when the main stream's GEMMs leave a large part of the chip idle for
         # whole kernels (see _want_side)
         self.overlap_dw = "auto"
@@ -250,13 +306,20 @@ class ViTEngine:
         """This engine's own vit_handle.  Launch geometry (`reserve_cus`) and the split-K / reduction workspace belong to the
         handle, so two engines of one process -- a training and an evaluation model, a sweep's trials -- do not see each
         other's settings (include/vit_amd.h: vit_handle_set_option)."""
-        from . import _cabi
-
-        dev = self.flat.device
-        if self._main_handle is None or self._main_handle.device_index != (dev.index if dev.index is not None else torch.cuda.current_device()):
-            self._main_handle = _cabi.Handle(dev.index if dev.index is not None else torch.cuda.current_device())
-            self._main_handle.set_option("reserve_cus", self.reserve_cus)
+        if self._main_handle is None or self._main_handle.device_index != self._device_index():
+            self._main_handle = self._new_handle()
         return self._main_handle
+
+    def _device_index(self) -> int:
+        dev = self.flat.device
+        return dev.index if dev.index is not None else torch.cuda.current_device()
+
+    def _new_handle(self):
+        h = _cabi.Handle(self._device_index())
+        h.set_option("reserve_cus", self.reserve_cus)
+        if self._accum:  # created inside an accumulating backward
+            h.set_option("grad_accumulate", 1)
+        return h
 
     def set_reserve_cus(self, n: int):
         """CUs the one-workgroup-per-CU kernels of THIS engine leave to a collective that overlaps them (data-parallel runs);
@@ -276,21 +339,31 @@ class ViTEngine:
     def g(self, name: str) -> torch.Tensor:
         return self.layout.view(self.grads, name)
 
-    def _qkv16(self, i: int):
-        off, _ = self.layout.entries[f"vit.encoder.layer.{i}.attention.attention.query.weight"]
+    # by name stem (self.names[i].fc1, PROJ, ...): W the GEMM operand, b the f32 bias, dW / db their gradient slices
+    def W(self, stem: str) -> torch.Tensor:
+        return self.layout.view(self.shadow if self.precision == "bf16" else self.flat, stem + ".weight")
+
+    def b(self, stem: str) -> torch.Tensor:
+        return self.layout.view(self.flat, stem + ".bias")
+
+    def dW(self, stem: str) -> torch.Tensor:
+        return self.layout.view(self.grads, stem + ".weight")
+
+    def db(self, stem: str) -> torch.Tensor:
+        return self.layout.view(self.grads, stem + ".bias")
+
+    def _qkv_w(self, i: int, buf: torch.Tensor):
+        """Layer i's adjacent query / key / value weights in `buf` (a flat buffer) as one [3D, D] matrix."""
+        off, _ = self.layout.entries[self.names[i].q + ".weight"]
         D = self.cfg.hidden_size
-        src = self.shadow if self.precision == "bf16" else self.flat
-        return src[off:off + 3 * D * D].view(3 * D, D)
+        return buf[off:off + 3 * D * D].view(3 * D, D)
+
+    def _qkv16(self, i: int):
+        return self._qkv_w(i, self.shadow if self.precision == "bf16" else self.flat)
 
     def _qkv_bias(self, i: int, buf: torch.Tensor):
-        off, _ = self.layout.entries[f"vit.encoder.layer.{i}.attention.attention.query.bias"]
-        D = self.cfg.hidden_size
-        return buf[off:off + 3 * D]
-
-    def _qkv_wgrad(self, i: int):
-        off, _ = self.layout.entries[f"vit.encoder.layer.{i}.attention.attention.query.weight"]
-        D = self.cfg.hidden_size
-        return self.grads[off:off + 3 * D * D].view(3 * D, D)
+        off, _ = self.layout.entries[self.names[i].q + ".bias"]
+        return buf[off:off + 3 * self.cfg.hidden_size]
 
     # ------------------------------------------------------------------ arena
     def _ensure_arena(self, B: int, train: bool):
@@ -302,10 +375,10 @@ class ViTEngine:
         if self._arena_key == key:
             return
         slot = self._arenas.get(train)
-        if slot is not None and slot[0] == key:
-            self._arena_key, self.act, self.tmp, self._Mp = key, slot[1], slot[2], slot[3]
+        if slot is not None and slot.key == key:
+            self._arena_key, self.act, self.tmp, self._Mp, self._rows = slot
             return
-        self.act, self.tmp = {}, {}
+        self.act, self.tmp, self._rows = {}, {}, None
         self._arenas.pop(train, None)  # release the slot's old tensors before allocating their replacement
         c = self.cfg
         dev = self.flat.device
@@ -318,7 +391,6 @@ class ViTEngine:
         # bias-only values in the forward tensors and exact zeros in every gradient tensor: dW = dY^T X over Mp rows
         # equals the sum over the M real rows, and bias-gradient column sums likewise.
         Mp = -(-M // 256) * 256 if (D % 256 == 0 and Fd % 256 == 0) else M
-        self._Mp = Mp
         nl = L if train else 1
         f32, b16 = torch.float32, self.adt  # "b16" = the activation/operand dtype of the current precision mode
 
@@ -328,9 +400,12 @@ class ViTEngine:
         def G(cols, dt):  # a GEMM operand / result with M real rows (+ zeroed pad rows behind the view)
             return torch.zeros((Mp, cols), dtype=dt, device=dev)[:M]
 
-        self.act = dict(
+        def C(cols, dt):  # a CLS-tail buffer, listed per layer slot like its full twin: only the last layer has a tail, so
+            return [E((B, cols) if cols else (B,), dt)] * nl  # ONE buffer serves whichever slot that layer has
+
+        act = dict(
             patches=E((B * N, P), b16),
-            x=[E((B, T, D), f32) for _ in range(L + 1)],
+            x=(xs := [E((B, T, D), f32) for _ in range(L + 1)]), xL=xs[L].view(M, D),
             h1=[G(D, b16) for _ in range(nl)], qkv=[G(3 * D, b16) for _ in range(nl)],
             ctx=[G(D, b16) for _ in range(nl)], lse=[E((B * H, T), f32) for _ in range(nl)],
             # bf16 training: the rounding residual of ctx, so the backward's delta sees the context to ~16 bits (vit_amd.h)
@@ -342,13 +417,13 @@ class ViTEngine:
             last=E((B, T, D), f32), meanF=E((M,), f32), rstdF=E((M,), f32),
             y=G(D, b16),  # dropout(Linear(.)) of the attention-output / FC2 projection, until the next LayerNorm adds it
             # the last layer's CLS tail: one row per image
-            c_y=E((B, D), b16), c_x1=E((B, D), f32), c_h2=E((B, D), b16), c_u=E((B, Fd), b16), c_g=E((B, Fd), b16),
-            c_mean2=E((B,), f32), c_rstd2=E((B,), f32), c_xL=E((B, D), f32), c_last=E((B, 1, D), f32),
+            c_y=E((B, D), b16), c_x1=C(D, f32), c_h2=C(D, b16), c_u=C(Fd, b16), c_g=C(Fd, b16),
+            c_mean2=C(0, f32), c_rstd2=C(0, f32), c_xL=E((B, D), f32), c_last=E((B, 1, D), f32),
             c_meanF=E((B,), f32), c_rstdF=E((B,), f32),
         )
-        self.tmp = {}
+        tmp = {}
         if train:
-            self.tmp = dict(
+            tmp = dict(
                 dxa=E((M, D), f32), dxb=E((M, D), f32), dy=G(D, b16), dy2=G(D, b16), dU=G(Fd, b16), dh=G(D, b16),
                 dqkv=G(3 * D, b16), dctx=G(D, b16), delta=E((B * H, T), f32), dpatch=E((B * N, D), b16),
                 dlast=E((B, T, D), f32),
@@ -356,25 +431,26 @@ class ViTEngine:
                 c_dh=E((B, D), b16), c_dlast=E((B, 1, D), f32),
                 # the CLS tail's dctx: only its rows b*T are ever written, every other row keeps the zero it was allocated
                 # with -- the attention backward reads a full [M, D] gradient and no per-step fill is needed.  INVARIANT: the
-                # one writer is _backward_cls_tail's out-projection dX (B and T are fixed for the arena's life); anything
-                # else that writes this buffer breaks the tail's gradients silently (tests/test_cls_tail_gpu.py poisons the
-                # rows in between and checks that nothing rewrites them)
+                # one writer is the out-projection dX of _tail_bwd over the CLS rows, with ldc = T * D (B and T are fixed for
+                # the arena's life); anything else that writes this buffer breaks the tail's gradients silently
+                # (tests/test_cls_tail_gpu.py poisons the rows in between and checks that nothing rewrites them)
                 dctx_cls=G(D, b16),
             )
-        self._arena_key = key
-        self._arenas[train] = (key, self.act, self.tmp, Mp)
+        rows = (Rows(Mp, 1, M, Mp, act, tmp, "", tmp.get("dctx")), Rows(B, T, M, Mp, act, tmp, "c_", tmp.get("dctx_cls")))
+        self._arenas[train] = Arena(key, act, tmp, Mp, rows)
+        self._arena_key, self.act, self.tmp, self._Mp, self._rows = self._arenas[train]
 
     def _drop_arenas(self):
         self._arena_key = None
         self._arenas = {}
-        self.act, self.tmp = {}, {}
+        self.act, self.tmp, self._rows = {}, {}, None
 
     def _rope_tables(self, T: int):
         """Half-width cos / sin tables of RotaryPositionEmbedding (rope.py:36-56), computed on the host by the reference's
         own expression (so the table bits are the reference's) and kept on the device."""
         c = self.cfg
         key = (T, c.head_dim, float(c.rope_base), self.flat.device)
-        if getattr(self, "_rope_key", None) != key:
+        if self._rope_key != key:
             dim = c.head_dim
             inv_freq = 1.0 / (c.rope_base ** (torch.arange(0, dim, 2).float() / dim))
             freqs = torch.outer(torch.arange(T).type_as(inv_freq), inv_freq)
@@ -404,11 +480,10 @@ class ViTEngine:
         x = x.contiguous().to(torch.float32)
         B = x.shape[0]
         self._gen += 1
-        T, D, Fd, H, L, N, P, S = c.seq_len, c.hidden_size, c.intermediate_size, c.num_attention_heads, \
-            c.num_hidden_layers, c.num_patches, c.patch_size, c.stride
+        T, D, H, L, N, P, S = c.seq_len, c.hidden_size, c.num_attention_heads, c.num_hidden_layers, c.num_patches, \
+            c.patch_size, c.stride
         dh, M = c.head_dim, B * T
         self._ensure_arena(B, need_grad)
-        Mp = self._Mp
         a = self.act
         ph = c.hidden_dropout_prob if training else 0.0
         pa = c.attention_probs_dropout_prob if training else 0.0
@@ -416,36 +491,27 @@ class ViTEngine:
             self.step_counter += 1
         seed = (self.base_seed + 0x9E3779B97F4A7C15 * self.step_counter) & 0xFFFFFFFFFFFFFFFF
         scale = dh ** -0.5
-        eps = c.layer_norm_eps
-        e = "vit.embeddings."
-
+        full, cls = self._rows
         # --- embeddings: unfold -> projection (+bias) into token rows 1..N -> CLS / pos-emb / dropout
         vf.unfold_cast(x, P, S, N, out=a["patches"])  # bf16 or f32 patches, per the arena dtype
-        wp = self.w16(e + "patch_embeddings.projection.weight").view(D, P)
         x0 = a["x"][0]
-        vf.gemm(a["patches"], wp, M=B * N, N=D, K=P, out=x0.view(M, D), bias=self.p(e + "patch_embeddings.projection.bias"),
-                row_map=(N, T, 1))
-        pos = self.p(e + "position_embeddings").view(T, D) if c.pos_encoding_type == "learned" else None
-        vf.embed_finish(x0, self.p(e + "cls_token").view(D), pos, dropout=(ph, seed, 0))
+        vf.gemm(a["patches"], self.W(PROJ).view(D, P), M=B * N, N=D, K=P, out=x0.view(M, D), bias=self.b(PROJ), row_map=(N, T, 1))
+        pos = self.p(EMBED + "position_embeddings").view(T, D) if c.pos_encoding_type == "learned" else None
+        vf.embed_finish(x0, self.p(EMBED + "cls_token").view(D), pos, dropout=(ph, seed, 0))
 
         atts = [] if output_attentions else None
         rope = self._rope_tables(T) if c.pos_encoding_type == "rope" else None
-        # The two "dropout(Linear(.)) + residual" sums of a layer (HF ViTLayer / ViTOutput) are formed by the LayerNorm
-        # that consumes them: the projection GEMM writes y = dropout(acc + bias) in the activation dtype, the LayerNorm
-        # pass reads the f32 stream and y, writes the new stream and its normalised operand (vit_layernorm_fwd_residual).
-        y = a["y"]
         tail = bool(self.cls_tail) and L > 0 and not output_hidden_states
+        r = full
+        if L == 0:
+            self._ln(full.xL, "vit.layernorm", full.last2, full.meanF, full.rstdF)
+        else:
+            self._ln(x0.view(M, D), self.names[0].ln1, a["h1"][0], a["mean1"][0], a["rstd1"][0])
         for i in range(L):
             j = i if need_grad else 0
-            pre = f"vit.encoder.layer.{i}."
-            xin = a["x"][i].view(M, D)
-            if i == 0:
-                self._ln(xin, pre + "layernorm_before", a["h1"][j], a["mean1"][j], a["rstd1"][j])
-            else:
-                self._ln_res(a["x1"][jprev], y, xin, pre + "layernorm_before", a["h1"][j], a["mean1"][j], a["rstd1"][j])
             # vit_with_rope.py:58-60: q, k rotated per head before the scores -- inside the projection's epilogue where the
             # kernel has one (f32 values, one rounding), by a vit_rope_qk pass behind it otherwise (the library decides)
-            vf.gemm(a["h1"][j], self._qkv16(i), M=Mp, N=3 * D, K=D, out=a["qkv"][j], bias=self._qkv_bias(i, self.flat),
+            vf.gemm(a["h1"][j], self._qkv16(i), M=full.n, N=3 * D, K=D, out=a["qkv"][j], bias=self._qkv_bias(i, self.flat),
                     rope=None if rope is None else (rope[0], rope[1], T, dh, 2 * D))
             vf.attention_fwd(a["qkv"][j], B, H, T, dh, scale, dropout=(pa, seed, self._site(i, 0)), ctx=a["ctx"][j],
                              lse=a["lse"][j], ctx_lo=a["ctx_lo"][j])
@@ -453,40 +519,13 @@ class ViTEngine:
                 atts.append(vf.attention_probs(a["qkv"][j], B, H, T, dh, scale))
             if capture_ctx is not None:  # per-layer context for forward hooks on the attention modules
                 capture_ctx.append(a["ctx"][j].view(B, T, D).clone())
-            if tail and i == L - 1:
-                break
-            vf.gemm(a["ctx"][j], self.w16(pre + "attention.output.dense.weight"), M=Mp, N=D, K=D, out=y,
-                    bias=self.p(pre + "attention.output.dense.bias"), dropout=(ph, seed, self._site(i, 1)))
-            self._ln_res(xin, y, a["x1"][j], pre + "layernorm_after", a["h2"][j], a["mean2"][j], a["rstd2"][j])
-            vf.gemm(a["h2"][j], self.w16(pre + "intermediate.dense.weight"), M=Mp, N=Fd, K=D, out=a["g"][j],
-                    bias=self.p(pre + "intermediate.dense.bias"), act=vf.ACT_GELU_GRAD if need_grad else ACT_GELU,
-                    aux_out=a["u"][j] if need_grad else None)  # a["u"] holds gelu'(pre-activation) for the backward
-            vf.gemm(a["g"][j], self.w16(pre + "output.dense.weight"), M=Mp, N=D, K=Fd, out=y,
-                    bias=self.p(pre + "output.dense.bias"), dropout=(ph, seed, self._site(i, 2)))
-            jprev = j
-        last = a["last"]
-        if tail:
-            # the last layer behind its attention, over the rows b*T alone: ctx and the residual stream are read in place
-            # (row stride T), everything written is compact, and the dropout masks are keyed by the ORIGINAL row b*T so that
-            # they are the full path's (and oracle/dropmask.py's) bit for bit
-            i, pre = L - 1, f"vit.encoder.layer.{L - 1}."
-            j = i if need_grad else 0
-            cy, last = a["c_y"], a["c_last"]
-            vf.gemm(a["ctx"][j], self.w16(pre + "attention.output.dense.weight"), M=B, N=D, K=D, lda=T * D, out=cy,
-                    bias=self.p(pre + "attention.output.dense.bias"), dropout=(ph, seed, self._site(i, 1)), drop_row_stride=T)
-            self._ln_res(a["x"][i].view(M, D), cy, a["c_x1"], pre + "layernorm_after", a["c_h2"], a["c_mean2"], a["c_rstd2"],
-                         x_row_stride=T)
-            vf.gemm(a["c_h2"], self.w16(pre + "intermediate.dense.weight"), M=B, N=Fd, K=D, out=a["c_g"],
-                    bias=self.p(pre + "intermediate.dense.bias"), act=vf.ACT_GELU_GRAD if need_grad else ACT_GELU,
-                    aux_out=a["c_u"] if need_grad else None)
-            vf.gemm(a["c_g"], self.w16(pre + "output.dense.weight"), M=B, N=D, K=Fd, out=cy,
-                    bias=self.p(pre + "output.dense.bias"), dropout=(ph, seed, self._site(i, 2)), drop_row_stride=T)
-            self._ln_res(a["c_x1"], cy, a["c_xL"], "vit.layernorm", last.view(B, D), a["c_meanF"], a["c_rstdF"])
-        elif L > 0:
-            self._ln_res(a["x1"][jprev], y, a["x"][L].view(M, D), "vit.layernorm", a["last"].view(M, D), a["meanF"],
-                         a["rstdF"])
-        else:
-            self._ln(a["x"][L].view(M, D), "vit.layernorm", a["last"].view(M, D), a["meanF"], a["rstdF"])
+            if i + 1 < L:  # FC2's output is consumed by the next layer's LN-before
+                jn = i + 1 if need_grad else 0
+                then = (a["x"][i + 1].view(M, D), self.names[i + 1].ln1, a["h1"][jn], a["mean1"][jn], a["rstd1"][jn])
+            else:  # ... or by the final LayerNorm: over the CLS rows alone when only the head consumes it
+                r = cls if tail else full
+                then = (r.xL, "vit.layernorm", r.last2, r.meanF, r.rstdF)
+            self._tail_fwd(r, i, j, a["x"][i].view(M, D), then, ph, seed, need_grad)
         hn = self.layout.head
         if labels is not None:
             labels = labels.to(self.flat.device)
@@ -494,11 +533,33 @@ class ViTEngine:
             n_expected = B if self.loss_kind == LOSS_CE else B * c.num_labels
             if labels.numel() != n_expected:
                 raise ValueError(f"labels has {labels.numel()} elements, expected {n_expected}")
-        logits, loss = vf.head_loss_fwd(last, self.p(hn + ".weight"), self.p(hn + ".bias"), labels, self.loss_kind)
+        logits, loss = vf.head_loss_fwd(r.last, self.p(hn + ".weight"), self.p(hn + ".bias"), labels, self.loss_kind)
         self._last = dict(B=B, seed=seed, ph=ph, pa=pa, labels=labels, logits=logits, gen=self._gen, grad=need_grad,
                           tail=tail)
         hs = [t.clone() for t in a["x"]] if output_hidden_states else None
         return loss, logits, hs, atts
+
+    def _tail_fwd(self, r: Rows, i: int, j: int, xin, then, ph: float, seed: int, need_grad: bool):
+        """Layer i behind its attention, over the rows `r` (activations in layer slot j): out-projection -> LN-after -> FC1 + GELU
+        -> FC2 -> `then` = (xsum, name, out, mean, rstd), the LayerNorm that consumes FC2's output (the next layer's LN-before, or
+        the final one).
+        The two "dropout(Linear(.)) + residual" sums of a layer (HF ViTLayer / ViTOutput) are formed by the LayerNorm that
+        consumes them: the projection GEMM writes y = dropout(acc + bias) in the activation dtype, the LayerNorm pass reads the
+        f32 stream and y, writes the new stream and its normalised operand (vit_layernorm_fwd_residual).
+        Rows of stride T (the CLS rows b*T): ctx and the residual stream `xin` are read in place, everything written is compact,
+        and the dropout masks are keyed by the ORIGINAL row b*T so that they are the full path's (and oracle/dropmask.py's)
+        bit for bit."""
+        c, a, nm = self.cfg, self.act, self.names[i]
+        D, Fd, n = c.hidden_size, c.intermediate_size, r.n
+        drs = r.stride if r.stride > 1 else 0
+        vf.gemm(a["ctx"][j], self.W(nm.wo), M=n, N=D, K=D, lda=r.stride * D, out=r.y, bias=self.b(nm.wo),
+                dropout=(ph, seed, self._site(i, 1)), drop_row_stride=drs)
+        self._ln_res(xin, r.y, r.x1[j], nm.ln2, r.h2[j], r.mean2[j], r.rstd2[j], x_row_stride=r.stride)
+        vf.gemm(r.h2[j], self.W(nm.fc1), M=n, N=Fd, K=D, out=r.g[j], bias=self.b(nm.fc1), act=vf.ACT_GELU_GRAD if need_grad
+                else ACT_GELU, aux_out=r.u[j] if need_grad else None)  # u holds gelu'(pre-activation) for the backward
+        vf.gemm(r.g[j], self.W(nm.fc2), M=n, N=D, K=Fd, out=r.y, bias=self.b(nm.fc2), dropout=(ph, seed, self._site(i, 2)),
+                drop_row_stride=drs)
+        self._ln_res(r.x1[j], r.y, *then)
 
     def saved_attentions(self):
         """Attention probabilities (before dropout) of every layer of the LAST need_grad forward, from its saved qkv."""
@@ -518,46 +579,37 @@ class ViTEngine:
                                   self.cfg.layer_norm_eps, out=out, mean=mean, rstd=rstd, x_row_stride=x_row_stride)
 
     # ------------------------------------------------------------------ weight gradients beside the data path
-    def _dw(self, *args, reads=(), **kw):
-        """A weight-gradient GEMM (dW = dY^T X, deterministic split-K).  Its only consumer is the optimizer at the end of the
-        step, so it is enqueued on a second HIP stream (own vit_handle = own split-K workspace) right after its operands are
-        complete and runs beside whatever continues the chain on the main stream.  What that buys: the CUs a kernel of the main
-        stream leaves idle (partial rounds of the N = 768 GEMMs, the tail of a LayerNorm pass) get dW workgroups -- a GEMM
-        workgroup takes a whole CU (128 KiB of LDS, 2 x 232 of a SIMD's 512 VGPRs), so nothing shares a CU with it; measured
-        0.1-0.2 ms per step.
-        `reads` names the scratch buffers the GEMM reads; `_before_write(name)` makes the main stream wait for the last such
-        reader before a kernel overwrites the buffer (one layer later, so the wait is normally already satisfied)."""
-        if self.side_stream is None:
-            return vf.gemm(*args, **kw)
-        main = torch.cuda.current_stream(self.flat.device)
-        self.side_stream.wait_stream(main)
-        with torch.cuda.stream(self.side_stream), vf.use_handle(self._side_handle):
-            out = vf.gemm(*args, **kw)
-            if reads:
+    def _dw(self, r: Rows, dy, x, out, ldx: Optional[int] = None):
+        """A weight gradient out[N, K] = dy^T x over the rows `r`: a deterministic split-K GEMM over the token rows, the
+        compact product in the full product's summation order over the CLS rows (vf.linear_bwd_dw_rows).  Its only consumer is
+        the optimizer at the end of the step, so it is enqueued on a second HIP stream (own vit_handle = own split-K workspace)
+        right after its operands are complete and runs beside whatever continues the chain on the main stream.  What that buys:
+        the CUs a kernel of the main stream leaves idle (partial rounds of the N = 768 GEMMs, the tail of a LayerNorm pass) get
+        dW workgroups -- a GEMM workgroup takes a whole CU (128 KiB of LDS, 2 x 232 of a SIMD's 512 VGPRs), so nothing shares a
+        CU with it; measured 0.1-0.2 ms per step.
+        Token rows: `dy` is a scratch buffer that a later kernel of this backward overwrites, so an event is recorded behind
+        the GEMM and `_before_write(dy)` makes the main stream wait for it before that kernel (one layer later, so the wait is
+        normally already satisfied).  CLS rows: no read event is recorded -- c_dy, c_dU and c_dy2 have ONE writer per step
+        each, which runs before this call on the main stream, and the next step's writers run behind _join_side; a second
+        writer of one of them inside a step would need _before_write like the token rows'."""
+        N, K = out.shape
+        with self._on_side as side:
+            if r.stride > 1:
+                return vf.linear_bwd_dw_rows(dy, x, out, row_stride=r.stride, full_rows=r.Mp, ldx=ldx)
+            vf.gemm(dy, x, M=N, N=K, K=r.n, a_trans=True, b_trans=True, ldb=ldx, out=out, split_k=-1)
+            if side is not None:
                 ev = torch.cuda.Event()
-                ev.record(self.side_stream)
-                for name in reads:
-                    self._side_reads[name] = ev
+                ev.record(side)
+                self._side_reads[dy.data_ptr()] = ev
         return out
 
-    def _dw_rows(self, dy, x, out, **kw):
-        """_dw for the CLS tail's compact weight gradients (vf.linear_bwd_dw_rows).  No read events are recorded: c_dy, c_dU
-        and c_dy2 have ONE writer per step each, which runs before this call on the main stream, and the next step's writers
-        run behind _join_side; a second writer of one of them inside a step would need _before_write like the full path's."""
-        if self.side_stream is None:
-            return vf.linear_bwd_dw_rows(dy, x, out, **kw)
-        self.side_stream.wait_stream(torch.cuda.current_stream(self.flat.device))
-        with torch.cuda.stream(self.side_stream), vf.use_handle(self._side_handle):
-            return vf.linear_bwd_dw_rows(dy, x, out, **kw)
-
-    def _before_write(self, *names):
+    def _before_write(self, buf):
+        """The main stream waits for the second stream's last reader of `buf` (see _dw), if there is one."""
         if self.side_stream is None:
             return
-        main = torch.cuda.current_stream(self.flat.device)
-        for name in names:
-            ev = self._side_reads.pop(name, None)
-            if ev is not None:
-                main.wait_event(ev)
+        ev = self._side_reads.pop(buf.data_ptr(), None)
+        if ev is not None:
+            torch.cuda.current_stream(self.flat.device).wait_event(ev)
 
     def _join_side(self):
         if self.side_stream is not None:
@@ -569,13 +621,9 @@ class ViTEngine:
         (after it has caught up with the main stream's position): the exchange then waits for the weight-gradient GEMMs
         without the main stream having to join them, and the data path of the next layer keeps running."""
         cb = self.grad_ready_cb
-        if cb is None:
-            return
-        if self.side_stream is None:
-            return cb(lo, hi)
-        self.side_stream.wait_stream(torch.cuda.current_stream(self.flat.device))
-        with torch.cuda.stream(self.side_stream):
-            cb(lo, hi)
+        if cb is not None:
+            with self._on_side:
+                cb(lo, hi)
 
     def _want_side(self) -> bool:
         """`overlap_dw == "auto"`: second stream iff the balanced grid of this batch's [M, D] x [D, D] products leaves at least
@@ -587,7 +635,7 @@ class ViTEngine:
         if self.overlap_dw != "auto":
             return bool(self.overlap_dw)
         D = self.cfg.hidden_size
-        Mp = getattr(self, "_Mp", 0)
+        Mp = self._Mp
         if D % 256 or not Mp or Mp % 256:
             return True
         cus = max(1, torch.cuda.get_device_properties(self.flat.device).multi_processor_count - max(0, self.reserve_cus))
@@ -596,53 +644,63 @@ class ViTEngine:
         return -(-tiles // rounds) <= 0.7 * cus
 
     def _setup_side(self):
-        from . import _cabi
-
         on = self.precision == "bf16" and self._want_side()
         if on and self.side_stream is None:
-            import os
-
-            self.side_stream = torch.cuda.Stream(device=self.flat.device, priority=int(os.environ.get("VIT_SIDE_STREAM_PRIORITY", "0")))
+            self.side_stream = torch.cuda.Stream(device=self.flat.device,
+                                                 priority=int(os.environ.get("VIT_SIDE_STREAM_PRIORITY", "0")))
             if self._side_handle is None:
-                self._side_handle = _cabi.Handle(self.flat.device.index if self.flat.device.index is not None
-                                                 else torch.cuda.current_device())
-                self._side_handle.set_option("reserve_cus", self.reserve_cus)
+                self._side_handle = self._new_handle()
         elif not on:
             self.side_stream = None
-        if self._accum and self._side_handle is not None:  # a side handle created inside an accumulating backward
-            self._side_handle.set_option("grad_accumulate", 1)
 
     # ------------------------------------------------------------------ backward
-    def _backward_cls_tail(self, i: int, cdx: torch.Tensor, ph: float, seed: int) -> torch.Tensor:
-        """The last layer's backward from the final LayerNorm's input gradient down to dctx, over the B CLS rows: `cdx` is the
-        compact [B, D] gradient of the residual stream (t["c_dy"] = mask * cdx and the FC2 bias gradient came with it).  The
-        weight gradients and bias / LayerNorm parameter sums run over the B rows in the summation order of the full-size
-        passes (whose other rows are exact zeros), so they are the full path's bit for bit at T >= 64 (vit_amd.h:
+    def _ln_bwd(self, r: Rows, name: str, dy, x, mean, rstd, dres, dx, dyn=None, dbias=None, dropout=vf.NO_DROP,
+                dres_row_stride: int = 0):
+        """The backward of LayerNorm `name` over the rows `r`: dx = dres + its input gradient, and the gradients of its weight
+        and bias.  With `dyn` it also emits dyn = dropout_mask * dx (activation dtype) and dbias = its column sums: the gradient
+        of the Linear output underneath the next "dropout(.) + residual" going down, and that Linear's bias gradient.
+        `dres_row_stride = T`: dres alone is compact -- the CLS rows' residual gradient rejoining the token stream."""
+        vf.layernorm_bwd_rows(dy, x, self.p(name + ".weight"), mean, rstd, dres, dx, self.dW(name), self.db(name), dyn=dyn,
+                              dbias=dbias, dropout=dropout, dres_row_stride=dres_row_stride, row_stride=r.stride, full_rows=r.M)
+
+    def _fc2_dy(self, r: Rows, i: int, ph: float, seed: int) -> dict:
+        """What the LayerNorm backward that consumes layer i's output emits for that layer's FC2 (_ln_bwd's dyn / dbias):
+        r.dy and the FC2 bias gradient.  Nothing for i = -1: under layer 0's LN-before lie the embeddings."""
+        if i < 0:
+            return {}
+        return dict(dyn=r.dy, dbias=self.db(self.names[i].fc2), dropout=(ph, seed, self._site(i, 2)))
+
+    def _tail_bwd(self, r: Rows, i: int, dx, dx_out, ph: float, seed: int):
+        """Layer i's backward behind its attention, over the rows `r`: from `dx`, the gradient of the layer's output stream
+        (r.dy = mask * dx and the FC2 bias gradient came with the LayerNorm backward above), down to r.dctx; the residual
+        gradient at the layer's LN-after input goes to `dx_out`.
+        Over the CLS rows the weight gradients and bias / LayerNorm parameter sums run over the B rows in the summation order of
+        the full-size passes (whose other rows are exact zeros), so they are the full path's bit for bit at T >= 64 (vit_amd.h:
         vit_linear_bwd_dw_rows); the attention-output dX writes its B rows straight into the rows b*T of the otherwise zero
-        t["dctx_cls"].  Returns the compact residual gradient at the layer's LN-after
-        input.  Every c_* scratch buffer is written once per step, behind the join of the previous step, so the second
-        stream's readers need no _before_write."""
-        c, a, t = self.cfg, self.act, self.tmp
-        T, D, Fd = c.seq_len, c.hidden_size, c.intermediate_size
-        B = cdx.shape[0]
-        pre = f"vit.encoder.layer.{i}."
-        other = t["c_dxb"] if cdx is t["c_dxa"] else t["c_dxa"]
-        Mp = self._Mp
-        self._dw_rows(t["c_dy"], a["c_g"], self.g(pre + "output.dense.weight"), row_stride=T, full_rows=Mp)
-        vf.gemm(t["c_dy"], self.w16(pre + "output.dense.weight"), M=B, N=Fd, K=D, b_trans=True, out=t["c_dU"],
-                act=vf.ACT_MUL_AUX, aux_in=a["c_u"])
-        vf.colsum_rows(t["c_dU"], self.g(pre + "intermediate.dense.bias"), row_stride=T, full_rows=Mp)
-        self._dw_rows(t["c_dU"], a["c_h2"], self.g(pre + "intermediate.dense.weight"), row_stride=T, full_rows=Mp)
-        vf.gemm(t["c_dU"], self.w16(pre + "intermediate.dense.weight"), M=B, N=D, K=Fd, b_trans=True, out=t["c_dh"])
-        vf.layernorm_bwd_rows(t["c_dh"], a["c_x1"], self.p(pre + "layernorm_after.weight"), a["c_mean2"], a["c_rstd2"], cdx,
-                              other, self.g(pre + "layernorm_after.weight"), self.g(pre + "layernorm_after.bias"),
-                              dyn=t["c_dy2"], dbias=self.g(pre + "attention.output.dense.bias"),
-                              dropout=(ph, seed, self._site(i, 1)), row_stride=T, full_rows=B * T)
-        self._dw_rows(t["c_dy2"], a["ctx"][i], self.g(pre + "attention.output.dense.weight"), row_stride=T, full_rows=Mp,
-                      ldx=T * D)
-        vf.gemm(t["c_dy2"], self.w16(pre + "attention.output.dense.weight"), M=B, N=D, K=D, b_trans=True,
-                out=t["dctx_cls"], ldc=T * D)
-        return other
+        tmp["dctx_cls"].  Every c_* scratch buffer is written once per step, behind the join of the previous step, so the second
+        stream's readers of them record no event and the _before_write calls below find none to wait for.  The row set
+        decides two things, both a choice of kernel: the weight-gradient product (_dw) and where the FC1 bias gradient is summed."""
+        c, a, nm = self.cfg, self.act, self.names[i]
+        D, Fd, n = c.hidden_size, c.intermediate_size, r.n
+        strided = r.stride > 1
+        # x2 = dropout(g W2^T + b2) + x1
+        self._dw(r, r.dy, r.g[i], self.dW(nm.fc2))
+        self._before_write(r.dU)
+        # the FC1 bias gradient = column sums of dU: in the dX product's epilogue over the token rows, by the pass that sums
+        # compact rows in that order behind it over the CLS rows
+        vf.gemm(r.dy, self.W(nm.fc2), M=n, N=Fd, K=D, b_trans=True, out=r.dU, act=vf.ACT_MUL_AUX, aux_in=r.u[i],
+                colsum_out=None if strided else self.db(nm.fc1))
+        if strided:
+            vf.colsum_rows(r.dU, self.db(nm.fc1), row_stride=r.stride, full_rows=r.Mp)
+        self._dw(r, r.dU, r.h2[i], self.dW(nm.fc1))
+        vf.gemm(r.dU, self.W(nm.fc1), M=n, N=D, K=Fd, b_trans=True, out=r.dh)
+        # x1 = dropout(ctx Wo^T + bo) + x:  LN2 backward -> dx1, and dy2 = mask * dx1 with dbo
+        # this pass writes the OTHER dy buffer: the FC2 weight gradient still reading r.dy keeps running beside it
+        self._before_write(r.dy2)
+        self._ln_bwd(r, nm.ln2, r.dh, r.x1[i], r.mean2[i], r.rstd2[i], dx, dx_out, dyn=r.dy2, dbias=self.db(nm.wo),
+                     dropout=(ph, seed, self._site(i, 1)))
+        self._dw(r, r.dy2, a["ctx"][i], self.dW(nm.wo), ldx=r.stride * D)
+        vf.gemm(r.dy2, self.W(nm.wo), M=n, N=D, K=D, b_trans=True, out=r.dctx, ldc=r.stride * D)
 
     def _set_accumulate(self, on: bool):
         for h in (self._main_handle, self._side_handle):
@@ -679,118 +737,58 @@ class ViTEngine:
         c = self.cfg
         a, t = self.act, self.tmp
         B, seed, ph, pa = st["B"], st["seed"], st["ph"], st["pa"]
-        T, D, Fd, H, L, N, P = c.seq_len, c.hidden_size, c.intermediate_size, c.num_attention_heads, \
-            c.num_hidden_layers, c.num_patches, c.patch_size
+        T, D, H, L, N, P = c.seq_len, c.hidden_size, c.num_attention_heads, c.num_hidden_layers, c.num_patches, c.patch_size
         dh, M = c.head_dim, B * T
-        Mp = self._Mp
         scale = dh ** -0.5
         rope = self._rope_tables(T) if c.pos_encoding_type == "rope" else None
         hn = self.layout.head
         dloss = dloss.reshape(1).to(torch.float32).contiguous()
-
-        tail = st["tail"]
-        vf.head_loss_bwd(a["c_last"] if tail else a["last"], self.p(hn + ".weight"), st["logits"], st["labels"], dloss,
-                         self.loss_kind, dlast=t["c_dlast"] if tail else t["dlast"], dW=self.g(hn + ".weight"),
-                         db=self.g(hn + ".bias"))
+        full, cls = self._rows
+        r = cls if st["tail"] else full  # the rows the backward walks until the last layer's LN-before
+        vf.head_loss_bwd(r.last, self.p(hn + ".weight"), st["logits"], st["labels"], dloss, self.loss_kind, dlast=r.dlast,
+                         dW=self.dW(hn), db=self.db(hn))
         self._setup_side()
-        dx, dx_other = t["dxa"], t["dxb"]
-        cdx = None  # CLS tail: the compact [B, D] residual gradient that re-enters the token stream at the last layer's LN-before
-        # every LayerNorm backward below also emits dy = dropout_mask * dx (bf16) and its column sums: the gradient of
-        # the Linear output underneath the next "dropout(.) + residual" going down, and that Linear's bias gradient
-        if tail:
-            last_pre = f"vit.encoder.layer.{L - 1}."
-            cdx = t["c_dxa"]
-            vf.layernorm_bwd_rows(t["c_dlast"].view(B, D), a["c_xL"], self.p("vit.layernorm.weight"), a["c_meanF"],
-                                  a["c_rstdF"], None, cdx, self.g("vit.layernorm.weight"), self.g("vit.layernorm.bias"),
-                                  dyn=t["c_dy"], dbias=self.g(last_pre + "output.dense.bias"),
-                                  dropout=(ph, seed, self._site(L - 1, 2)), row_stride=T, full_rows=M)
-        elif L == 0:  # no encoder layer: the final LayerNorm sits directly on the embeddings
-            vf.layernorm_bwd(t["dlast"].view(M, D), a["x"][0].view(M, D), self.p("vit.layernorm.weight"), a["meanF"],
-                             a["rstdF"], dres=None, dx=dx, dgamma=self.g("vit.layernorm.weight"),
-                             dbeta=self.g("vit.layernorm.bias"))
-        else:
-            last_pre = f"vit.encoder.layer.{L - 1}."
-            vf.layernorm_bwd_fused(t["dlast"].view(M, D), a["x"][L].view(M, D), self.p("vit.layernorm.weight"), a["meanF"],
-                                   a["rstdF"], None, dx, self.g("vit.layernorm.weight"), self.g("vit.layernorm.bias"),
-                                   t["dy"], self.g(last_pre + "output.dense.bias"), (ph, seed, self._site(L - 1, 2)))
+        dx, spare = r.dx  # the residual gradient and the buffer the next LayerNorm backward writes it to
+        self._ln_bwd(r, "vit.layernorm", r.dlast.view(-1, D), r.xL, r.meanF, r.rstdF, None, dx,
+                     **self._fc2_dy(r, L - 1, ph, seed))
         self._notify(self.layout.tail_start, self.layout.n_trainable)
         for i in reversed(range(L)):
-            pre = f"vit.encoder.layer.{i}."
-            if cdx is not None:
-                cdx, dctx = self._backward_cls_tail(i, cdx, ph, seed), t["dctx_cls"]
-            else:
-                # x2 = dropout(g W2^T + b2) + x1      (t["dy"] = mask * dx and db2 were produced by the LN backward above)
-                self._dw(t["dy"], a["g"][i], M=D, N=Fd, K=Mp, a_trans=True, b_trans=True,
-                         out=self.g(pre + "output.dense.weight"), split_k=-1, reads=("dy",))
-                self._before_write("dU")
-                vf.gemm(t["dy"], self.w16(pre + "output.dense.weight"), M=Mp, N=Fd, K=D, b_trans=True, out=t["dU"],
-                        act=vf.ACT_MUL_AUX, aux_in=a["u"][i], colsum_out=self.g(pre + "intermediate.dense.bias"))
-                self._dw(t["dU"], a["h2"][i], M=Fd, N=D, K=Mp, a_trans=True, b_trans=True,
-                         out=self.g(pre + "intermediate.dense.weight"), split_k=-1, reads=("dU",))
-                vf.gemm(t["dU"], self.w16(pre + "intermediate.dense.weight"), M=Mp, N=D, K=Fd, b_trans=True, out=t["dh"])
-                # x1 = dropout(ctx Wo^T + bo) + x:  LN2 backward -> dx1, and dya = mask * dx1 with dbo
-                # this pass writes the OTHER dy buffer: the FC2 weight gradient still reading t["dy"] keeps running beside it
-                self._before_write("dy2")
-                vf.layernorm_bwd_fused(t["dh"], a["x1"][i], self.p(pre + "layernorm_after.weight"), a["mean2"][i],
-                                       a["rstd2"][i], dx, dx_other, self.g(pre + "layernorm_after.weight"),
-                                       self.g(pre + "layernorm_after.bias"), t["dy2"],
-                                       self.g(pre + "attention.output.dense.bias"), (ph, seed, self._site(i, 1)))
-                dx, dx_other = dx_other, dx
-                self._dw(t["dy2"], a["ctx"][i], M=D, N=D, K=Mp, a_trans=True, b_trans=True,
-                         out=self.g(pre + "attention.output.dense.weight"), split_k=-1, reads=("dy2",))
-                vf.gemm(t["dy2"], self.w16(pre + "attention.output.dense.weight"), M=Mp, N=D, K=D, b_trans=True,
-                        out=t["dctx"])
-                dctx = t["dctx"]
-            self._before_write("dqkv")
+            self._tail_bwd(r, i, dx, spare, ph, seed)
+            dx, spare = spare, dx
+            self._before_write(t["dqkv"])
             # the QKV bias gradient = column sums of dqkv: taken by the attention kernels on their way out, unless RoPE
             # sits in between (then after the inverse rotation, by the column-sum kernel)
-            vf.attention_bwd(a["qkv"][i], a["ctx"][i], dctx, a["lse"][i], B, H, T, dh, scale,
+            vf.attention_bwd(a["qkv"][i], a["ctx"][i], r.dctx, a["lse"][i], B, H, T, dh, scale,
                              dropout=(pa, seed, self._site(i, 0)), dqkv=t["dqkv"], delta=t["delta"],
                              colsum_out=None if rope is not None else self._qkv_bias(i, self.grads), ctx_lo=a["ctx_lo"][i])
             if rope is not None:  # gradient wrt the un-rotated q, k: the inverse rotation
                 vf.rope_qk(t["dqkv"], rope[0], rope[1], T, H, dh, inverse=True)
                 vf.colsum(t["dqkv"], out=self._qkv_bias(i, self.grads), accumulate=self._accum)
-            self._dw(t["dqkv"], a["h1"][i], M=3 * D, N=D, K=Mp, a_trans=True, b_trans=True, out=self._qkv_wgrad(i),
-                     split_k=-1, reads=("dqkv",))
-            vf.gemm(t["dqkv"], self._qkv16(i), M=Mp, N=D, K=3 * D, b_trans=True, out=t["dh"])
-            self._before_write("dy")  # the LayerNorm backward below rewrites t["dy"] (read by this layer's FC2 weight gradient)
-            if cdx is not None:
+            self._dw(full, t["dqkv"], a["h1"][i], self._qkv_w(i, self.grads))
+            vf.gemm(t["dqkv"], self._qkv16(i), M=full.n, N=D, K=3 * D, b_trans=True, out=t["dh"])
+            self._before_write(t["dy"])  # the LayerNorm backward below rewrites t["dy"] (read by this layer's FC2 weight gradient)
+            # LN1 backward -> dx (input of this layer = output of layer i-1), plus layer i-1's FC2 pieces
+            dres, rejoin = dx, 0
+            if r is not full:
                 # LN1 backward of the last layer: the compact residual gradient joins the token stream at the rows b*T (every
                 # other row has none); from here down the gradient is dense and the path is the full one
-                prev = f"vit.encoder.layer.{i - 1}."
-                vf.layernorm_bwd_rows(t["dh"], a["x"][i].view(M, D), self.p(pre + "layernorm_before.weight"), a["mean1"][i],
-                                      a["rstd1"][i], cdx, dx_other, self.g(pre + "layernorm_before.weight"),
-                                      self.g(pre + "layernorm_before.bias"), dyn=t["dy"] if i > 0 else None,
-                                      dbias=self.g(prev + "output.dense.bias") if i > 0 else None,
-                                      dropout=(ph, seed, self._site(i - 1, 2)) if i > 0 else vf.NO_DROP, dres_row_stride=T)
-                cdx = None
-            elif i > 0:
-                # LN1 backward -> dx (input of this layer = output of layer i-1), plus layer i-1's FC2 pieces
-                prev = f"vit.encoder.layer.{i - 1}."
-                vf.layernorm_bwd_fused(t["dh"], a["x"][i].view(M, D), self.p(pre + "layernorm_before.weight"),
-                                       a["mean1"][i], a["rstd1"][i], dx, dx_other,
-                                       self.g(pre + "layernorm_before.weight"), self.g(pre + "layernorm_before.bias"),
-                                       t["dy"], self.g(prev + "output.dense.bias"), (ph, seed, self._site(i - 1, 2)))
-            else:
-                vf.layernorm_bwd(t["dh"], a["x"][i].view(M, D), self.p(pre + "layernorm_before.weight"), a["mean1"][i],
-                                 a["rstd1"][i], dres=dx, dx=dx_other, dgamma=self.g(pre + "layernorm_before.weight"),
-                                 dbeta=self.g(pre + "layernorm_before.bias"))
-            dx, dx_other = dx_other, dx
+                rejoin, r = r.stride, full
+                dx, spare = full.dx
+            self._ln_bwd(full, self.names[i].ln1, t["dh"], a["x"][i].view(M, D), a["mean1"][i], a["rstd1"][i], dres, spare,
+                         dres_row_stride=rejoin, **self._fc2_dy(full, i - 1, ph, seed))
+            dx, spare = spare, dx
             self._notify(*self.layout.layer_ranges[i])
-        e = "vit.embeddings."
-        dpos = self.g(e + "position_embeddings").view(T, D) if c.pos_encoding_type == "learned" else None
-        vf.embed_finish_bwd(dx.view(B, T, D), self.g(e + "cls_token").view(D), dpos, dropout=(ph, seed, 0),
+        dpos = self.g(EMBED + "position_embeddings").view(T, D) if c.pos_encoding_type == "learned" else None
+        vf.embed_finish_bwd(dx.view(B, T, D), self.g(EMBED + "cls_token").view(D), dpos, dropout=(ph, seed, 0),
                             dpatch=t["dpatch"])  # dtype follows the buffer
-        vf.colsum(t["dpatch"], out=self.g(e + "patch_embeddings.projection.bias"), accumulate=self._accum)
-        vf.gemm(t["dpatch"], a["patches"], M=D, N=P, K=B * N, a_trans=True, b_trans=True,
-                out=self.g(e + "patch_embeddings.projection.weight").view(D, P), split_k=-1)
+        vf.colsum(t["dpatch"], out=self.db(PROJ), accumulate=self._accum)
+        vf.gemm(t["dpatch"], a["patches"], M=D, N=P, K=B * N, a_trans=True, b_trans=True, out=self.dW(PROJ).view(D, P),
+                split_k=-1)
         self._join_side()
         self._notify(self.layout.embed_start, self.layout.embed_end)
         if need_dx:
             # gradient wrt the signal itself (a trainable input preprocessor sits in front): dpatches = dpatch Wp, then the
             # overlap-add that undoes the tokenizer's unfold
-            S = c.stride
-            wp = self.w16(e + "patch_embeddings.projection.weight").view(D, P)
-            dpat = vf.gemm(t["dpatch"], wp, M=B * N, N=P, K=D, b_trans=True, out_dtype=torch.float32)
-            return vf.fold_add(dpat, B, c.image_size, P, S, N)
+            dpat = vf.gemm(t["dpatch"], self.W(PROJ).view(D, P), M=B * N, N=P, K=D, b_trans=True, out_dtype=torch.float32)
+            return vf.fold_add(dpat, B, c.image_size, P, c.stride, N)
         return None
