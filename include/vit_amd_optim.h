@@ -23,7 +23,36 @@
  *   which is the caller's own number for any beta of up to 7 significant digits.  vit_adamw_step keeps 1.f - beta.
  * vit_sgd_step_dyn / vit_adam_l2_step_dyn: the forms for a captured step (vit_step_state_bind): lr and momentum, or lr and the
  *   bias corrections, are read from the bound record at kernel entry.  vit_sgd_step_dyn with buf == NULL is the momentum-free
- *   update whatever the record holds.  VIT_ERR_ARG when no record is bound. */
+ *   update whatever the record holds.  VIT_ERR_ARG when no record is bound.
+ *
+ * Parameter groups (torch.optim's param_groups: no-decay sets, layer-wise learning rates) in ONE launch: vit_*_step_groups.
+ *   The flat buffer alternates decaying and non-decaying parameters (8 runs per encoder layer), so a launch per run would be
+ *   ~100 launches at ViT-B; instead one kernel walks the buffer once and looks up each element's lr / weight_decay / momentum.
+ *   Two caller-owned tables in device memory, only ever READ by the step kernels:
+ *     segment table: seg_end[n_segments], ascending end offsets in elements; segment s covers [seg_end[s-1], seg_end[s]) (from 0
+ *       for s = 0) and belongs to group seg_group[s].  Every end is a multiple of 4 except the last, which may equal the buffer's
+ *       length.  A segment may be as short as 8 elements; there is no cap on n_segments or n_groups.
+ *     group table: groups[n_groups][VIT_OPTIM_GROUP_STRIDE] f32 rows {lr, weight_decay, momentum, 0}, 16-byte aligned; momentum
+ *       is SGD's and is ignored by Adam.
+ *   `base` is the absolute element offset of p[0] in the segment table's coordinates (a multiple of 4, as the 16-byte accesses
+ *   need anyway): the call updates [base, base + n).  A sub-run of the buffer (the active runs when parameters are frozen, a
+ *   rank's shard) gives the bits the whole-buffer call gives there, wherever it starts and ends.
+ *   Arithmetic: the ungrouped entry point's, with the element's group's numbers in place of the scalar arguments -- on any
+ *   segment bit-identical to that entry point called on the slice.  beta1, beta2, eps, nesterov, `step` and the clip
+ *   coefficient stay call-wide.  vit_sgd_step_groups: a group whose momentum is 0 neither reads nor writes its part of buf
+ *   (vit_sgd_step with momentum 0); buf == NULL is the momentum-free update whatever the table holds.  No atomics,
+ *   deterministic.  Offsets past the last end count to the last segment and a group index past the table to the last group,
+ *   so a malformed table cannot make a kernel read outside the tables; beyond that the tables' contents are the caller's job
+ *   (vit_amd.functional.optim_group_tables checks them where they are built).
+ *   The `_dyn` forms (a captured step) take the bias corrections, and nothing else, from the bound record; learning rates and
+ *   momenta come from the group table in both forms (vit_sgd_step_groups_dyn only insists on the bound record).
+ *   VIT_ERR_ARG, before anything is launched: a NULL p, g, state buffer or table; n <= 0; n_segments <= 0; n_groups <= 0;
+ *   base < 0 or not a multiple of 4; step < 1; nesterov with buf == NULL; no record bound (`_dyn`).
+ * vit_optim_groups_write: writes groups[0 .. n_groups) from `values`, n_groups HOST rows of {lr, weight_decay, momentum}.  The
+ *   numbers travel by value in kernel arguments (64 rows per launch) and are stored with 16-byte vector stores, so there is no
+ *   staging buffer the host could overwrite under a running step.  The caller launches it only when a scheduler changed a
+ *   number, ahead of the step -- or ahead of the replay of a captured step -- on the same stream: per-step schedules stay
+ *   correct under a hipGraph although kernel arguments are frozen at capture. */
 #ifndef VIT_AMD_OPTIM_H_
 #define VIT_AMD_OPTIM_H_
 
@@ -43,6 +72,32 @@ int vit_adam_l2_step(vit_handle h, float* p, const float* g, float* m, float* v,
 int vit_adam_l2_step_dyn(vit_handle h, float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, float beta1,
                          float beta2, float eps, float weight_decay, const float* sqnorm, float max_norm,
                          vit_stream stream);
+
+#define VIT_OPTIM_GROUP_STRIDE 4 /* f32 per group-table row: lr, weight_decay, momentum, 0 */
+
+int vit_adamw_step_groups(vit_handle h, float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, int64_t base,
+                          const int64_t* seg_end, const int32_t* seg_group, int n_segments, const float* groups, int n_groups,
+                          float beta1, float beta2, float eps, int step, const float* sqnorm, float max_norm,
+                          vit_stream stream);
+int vit_adamw_step_groups_dyn(vit_handle h, float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n,
+                              int64_t base, const int64_t* seg_end, const int32_t* seg_group, int n_segments,
+                              const float* groups, int n_groups, float beta1, float beta2, float eps, const float* sqnorm,
+                              float max_norm, vit_stream stream);
+int vit_adam_l2_step_groups(vit_handle h, float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, int64_t base,
+                            const int64_t* seg_end, const int32_t* seg_group, int n_segments, const float* groups,
+                            int n_groups, float beta1, float beta2, float eps, int step, const float* sqnorm, float max_norm,
+                            vit_stream stream);
+int vit_adam_l2_step_groups_dyn(vit_handle h, float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n,
+                                int64_t base, const int64_t* seg_end, const int32_t* seg_group, int n_segments,
+                                const float* groups, int n_groups, float beta1, float beta2, float eps, const float* sqnorm,
+                                float max_norm, vit_stream stream);
+int vit_sgd_step_groups(vit_handle h, float* p, const float* g, float* buf, void* p_bf16, int64_t n, int64_t base,
+                        const int64_t* seg_end, const int32_t* seg_group, int n_segments, const float* groups, int n_groups,
+                        int nesterov, const float* sqnorm, float max_norm, vit_stream stream);
+int vit_sgd_step_groups_dyn(vit_handle h, float* p, const float* g, float* buf, void* p_bf16, int64_t n, int64_t base,
+                            const int64_t* seg_end, const int32_t* seg_group, int n_segments, const float* groups,
+                            int n_groups, int nesterov, const float* sqnorm, float max_norm, vit_stream stream);
+int vit_optim_groups_write(vit_handle h, float* groups, int n_groups, const float* values, vit_stream stream);
 
 #ifdef __cplusplus
 }

@@ -12,7 +12,15 @@ calls (ms per step, host launches included), bf16-mixed:
 
 Per configuration the figure is the median over the rounds; min / max over the rounds is the spread to read it against.
 The last worker (this tree only) times the bare kernels at n = 85.8 M against the bytes the algorithm moves per parameter
-(shadow included): SGD 14 B, SGD with momentum 22 B, Adam-L2 30 B -- beside vit_adamw_step (30 B) in the same process."""
+(shadow included): SGD 14 B, SGD with momentum 22 B, Adam-L2 30 B -- beside vit_adamw_step (30 B) in the same process.
+
+    python tools/optim_bench.py --groups [--parent DIR] [--rounds 3] [--out profiles/optim_groups_bench.json]
+
+The parameter-group study instead (vit_*_step_groups).  Kernel rows at n = 85.8 M, one fresh worker per round, all four in
+the same process: vit_adamw_step | the grouped kernel with one segment | with ViT-B's no-decay table | with ViT-L's
+layer-decay + no-decay table (its segments below n).  The yardstick is the plain kernel of the same session; the allowance
+is the spread that kernel shows across the session's rounds.  Step rows: C1 (eager and hip_graph) and C3 with AdamW,
+weight_decay 0.05, with and without `no_decay: true` + `layer_decay: 0.75` (`--parent`: its one-group step beside them)."""
 from __future__ import annotations
 
 import argparse
@@ -26,10 +34,12 @@ HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OPTS = {"sgd": {"type": "SGD", "lr": 1e-2}, "sgd_onecycle": {"type": "SGD", "lr": 1e-2, "lr_sch": "onecycle"},
         "adam_l2": {"type": "Adam", "lr": 1e-3, "weight_decay": 0.01}}
 CASES = [("C1", 64, False), ("C3", 256, False), ("C1", 64, True)]
+GROUP_OPTS = {"adamw": {"type": "AdamW", "lr": 1e-3, "weight_decay": 0.05},
+              "adamw_groups": {"type": "AdamW", "lr": 1e-3, "weight_decay": 0.05, "no_decay": True, "layer_decay": 0.75}}
 KERNEL_N = 85_800_000
 
 
-def _train_case(name, batch, graph, opt_name, steps, warmup, dev):
+def _train_case(name, batch, graph, opt_name, steps, warmup, dev, opts=OPTS):
     import warnings
 
     import torch
@@ -43,7 +53,7 @@ def _train_case(name, batch, graph, opt_name, steps, warmup, dev):
                          hidden_size=rc.hidden_size, num_hidden_layers=rc.num_hidden_layers,
                          num_attention_heads=rc.num_attention_heads, stride_size=rc.stride_size, proj_fn="SW"),
            "train": dict(batch_size=batch, ep=1, precision="bf16-mixed", hip_graph=graph),
-           "loss": {"name": "mae"}, "opt": dict(OPTS[opt_name]), "data": {"param": "log_g", "num_samples": batch * 1000},
+           "loss": {"name": "mae"}, "opt": dict(opts[opt_name]), "data": {"param": "log_g", "num_samples": batch * 1000},
            "noise": {"noise_level": 0}}
     module = ViTLModule(config=cfg)
     trainer = Trainer(cfg["train"], device=dev, verbose=False)
@@ -62,6 +72,7 @@ def _train_case(name, batch, graph, opt_name, steps, warmup, dev):
         e1.record()
         torch.cuda.synchronize()
     return {"config": name, "batch": batch, "hip_graph": graph, "opt": opt_name, "optimizer": type(trainer.optimizer).__name__,
+            "param_groups": len(trainer.optimizer.param_groups),
             "graph_in_use": bool(trainer.use_graph), "ms_per_step": round(e0.elapsed_time(e1) / steps, 4)}
 
 
@@ -99,6 +110,66 @@ def _kernels(dev):
     return out
 
 
+def _model_table(hidden, layers, heads, dev, layer_decay):
+    """The segment / group tables the fused optimizer would build for a ViT of this shape (no_decay: true, and layer_decay when
+    asked), from the parameter layout alone -- no model is allocated."""
+    import vit_amd.functional as vf
+    from vit_amd.config import ViTConfig
+    from vit_amd.engine import ParamLayout
+    from vit_amd.optimizer import _layer_id
+
+    lay = ParamLayout(ViTConfig(task_type="reg", image_size=50176, patch_size=256, hidden_size=hidden, num_hidden_layers=layers,
+                                num_attention_heads=heads, stride_size=256, num_labels=1))
+    keys, triples = {}, []
+    for name, (off, shape) in sorted(lay.entries.items(), key=lambda kv: kv[1][0]):
+        if off >= lay.n_trainable:
+            continue
+        skip = len(shape) <= 1 or name.endswith(("cls_token", "position_embeddings"))
+        key = (_layer_id(name, layers) if layer_decay else 0, skip)
+        triples.append((off, (lay.numel(name) + 7) // 8 * 8, keys.setdefault(key, len(keys))))
+    t = vf.optim_group_tables(triples, len(keys), dev)
+    vf.optim_groups_write(t, [(1e-3 * 0.75 ** (layers + 1 - d), 0.0 if skip else 0.05, 0.0) for d, skip in keys])
+    return t
+
+
+def _group_kernels(dev):
+    import torch
+    import vit_amd.functional as vf
+
+    n = KERNEL_N
+    p = torch.randn(n, device=dev)
+    g = torch.randn(n, device=dev) * 1e-3
+    a, b = torch.zeros(n, device=dev), torch.zeros(n, device=dev)
+    pb = torch.empty(n, device=dev, dtype=torch.bfloat16)
+    sq = torch.ones(1, device=dev)
+    clip = dict(sqnorm=sq, max_norm=0.5)
+    one = vf.optim_group_tables([(0, n, 0)], 1, dev, total=n)
+    vf.optim_groups_write(one, [(1e-3, 0.01, 0.0)])
+    tables = {"grouped, 1 segment": one, "grouped, ViT-B no_decay": _model_table(768, 12, 12, dev, False),
+              "grouped, ViT-L layer_decay + no_decay": _model_table(1024, 24, 16, dev, True)}
+    calls = {"adamw (plain)": (None, lambda: vf.adamw_step(p, g, a, b, pb, lr=1e-3, weight_decay=0.01, step=3, **clip))}
+    for name, t in tables.items():
+        calls[name] = (t, lambda t=t: vf.adamw_step_groups(p, g, a, b, pb, t, step=3, **clip))
+    out, ts = [], {name: [] for name in calls}
+    for f in (f for _, f in calls.values()):
+        f(); f()
+    torch.cuda.synchronize()
+    for _ in range(7):  # interleaved: every kernel sees the same minutes
+        for name, (_, f) in calls.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(); f(); f(); f(); e1.record()
+            torch.cuda.synchronize()
+            ts[name].append(e0.elapsed_time(e1) / 3 * 1e3)
+    for name, (t, _) in calls.items():
+        us = statistics.median(ts[name])
+        row = {"kernel": name, "n": n, "us": round(us, 1), "us_min": round(min(ts[name]), 1), "us_max": round(max(ts[name]), 1),
+               "gb_per_s": round(n * 30 / us / 1e3, 1)}
+        if t is not None:
+            row.update(n_groups=t.n_groups, n_segments=t.n_segments, segments_below_n=int((t.seg_end <= n).sum()) + 1)
+        out.append(row)
+    return out
+
+
 def worker(args):
     root = os.path.abspath(args.root)
     sys.path.insert(0, root)
@@ -110,6 +181,12 @@ def worker(args):
     dev = torch.device("cuda", 0)
     if args.worker == "kernels":
         res = _kernels(dev)
+    elif args.worker == "group_kernels":
+        res = _group_kernels(dev)
+    elif args.worker in ("group_train", "group_train_parent"):  # the parent knows no groups: its one-group step only
+        opts = {k: v for k, v in GROUP_OPTS.items() if args.worker == "group_train" or k == "adamw"}
+        res = [_train_case(name, batch, graph, opt, args.steps, args.warmup, dev, opts)
+               for name, batch, graph in CASES for opt in opts]
     else:
         res = [_train_case(name, batch, graph, opt, args.steps, args.warmup, dev)
                for name, batch, graph in CASES for opt in OPTS]
@@ -127,6 +204,44 @@ def _spawn(root, what, args):
     return json.loads(line[len("RESULT "):])
 
 
+def groups_main(args):
+    """The parameter-group study (see the module docstring): kernel rows and step rows, `rounds` fresh workers each."""
+    kernel_rounds, train = [], {"this": []}
+    if args.parent:
+        train["parent"] = []
+    for rnd in range(args.rounds):
+        kernel_rounds.append(_spawn(HERE, "group_kernels", args))
+        print(f"[round {rnd}] kernels: " + " ".join(f"{k['us']:.1f}" for k in kernel_rounds[-1]), flush=True)
+        if args.parent:
+            train["parent"].append(_spawn(os.path.abspath(args.parent), "group_train_parent", args))
+        train["this"].append(_spawn(HERE, "group_train", args))
+    kernels = []
+    for i, first in enumerate(kernel_rounds[0]):
+        us = [r[i]["us"] for r in kernel_rounds]
+        row = dict(first, us=round(statistics.median(us), 1), us_rounds=us, us_min=min(r[i]["us_min"] for r in kernel_rounds),
+                   us_max=max(r[i]["us_max"] for r in kernel_rounds))
+        row["gb_per_s"] = round(row["n"] * 30 / row["us"] / 1e3, 1)
+        kernels.append(row)
+        print(f"{row['kernel']:40s} {row['us']:8.1f} us, rounds {us}, samples [{row['us_min']:.1f} .. {row['us_max']:.1f}] = "
+              f"{row['gb_per_s']:.0f} GB/s", flush=True)
+    table = []
+    for tree, rounds in train.items():
+        for i, first in enumerate(rounds[0]):
+            ms = [r[i]["ms_per_step"] for r in rounds]
+            row = {k: first[k] for k in ("config", "batch", "hip_graph", "opt", "optimizer", "graph_in_use")}
+            row.update(tree=tree, param_groups=first.get("param_groups", 1), ms_median=round(statistics.median(ms), 4),
+                       ms_min=min(ms), ms_max=max(ms), ms_rounds=ms)
+            table.append(row)
+            print(f"{tree:6s} {row['config']} B={row['batch']} graph={int(row['graph_in_use'])} {row['opt']:13s} groups="
+                  f"{row['param_groups']:2d}: {row['ms_median']:.3f} ms [{row['ms_min']:.3f} .. {row['ms_max']:.3f}]", flush=True)
+    line = json.dumps({"optim_groups_bench": {"steps": args.steps, "warmup": args.warmup, "rounds": args.rounds,
+                                              "kernels": kernels, "train": table}})
+    print(line)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--parent", default="", help="a built checkout of the parent commit")
@@ -135,11 +250,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--worker-timeout", type=int, default=240)
     ap.add_argument("--out", default="")
-    ap.add_argument("--worker", default="", choices=["", "train", "kernels"])
+    ap.add_argument("--groups", action="store_true", help="the parameter-group study instead")
+    ap.add_argument("--worker", default="", choices=["", "train", "kernels", "group_kernels", "group_train", "group_train_parent"])
     ap.add_argument("--root", default=HERE)
     args = ap.parse_args()
     if args.worker:
         return worker(args)
+    if args.groups:
+        return groups_main(args)
     trees = ([("parent", os.path.abspath(args.parent))] if args.parent else []) + [("this", HERE)]
     runs = {t: [] for t, _ in trees}
     for rnd in range(args.rounds):

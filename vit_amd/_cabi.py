@@ -101,6 +101,14 @@ _PROTOS = {
     "vit_sgd_step_dyn": [_P, _P, _P, _P, _P, _I64, _F, _I, _P, _F, _P],
     "vit_adam_l2_step": [_P, _P, _P, _P, _P, _P, _I64, _F, _F, _F, _F, _F, _I, _P, _F, _P],
     "vit_adam_l2_step_dyn": [_P, _P, _P, _P, _P, _P, _I64, _F, _F, _F, _F, _P, _F, _P],
+    # (h, p, g, m, v, p_bf16, n, base, seg_end, seg_group, n_segments, groups, n_groups, beta1, beta2, eps, [step,] sqnorm, ...)
+    "vit_adamw_step_groups": [_P, _P, _P, _P, _P, _P, _I64, _I64, _P, _P, _I, _P, _I, _F, _F, _F, _I, _P, _F, _P],
+    "vit_adamw_step_groups_dyn": [_P, _P, _P, _P, _P, _P, _I64, _I64, _P, _P, _I, _P, _I, _F, _F, _F, _P, _F, _P],
+    "vit_adam_l2_step_groups": [_P, _P, _P, _P, _P, _P, _I64, _I64, _P, _P, _I, _P, _I, _F, _F, _F, _I, _P, _F, _P],
+    "vit_adam_l2_step_groups_dyn": [_P, _P, _P, _P, _P, _P, _I64, _I64, _P, _P, _I, _P, _I, _F, _F, _F, _P, _F, _P],
+    "vit_sgd_step_groups": [_P, _P, _P, _P, _P, _I64, _I64, _P, _P, _I, _P, _I, _I, _P, _F, _P],
+    "vit_sgd_step_groups_dyn": [_P, _P, _P, _P, _P, _I64, _I64, _P, _P, _I, _P, _I, _I, _P, _F, _P],
+    "vit_optim_groups_write": [_P, _P, _I, C.POINTER(C.c_float), _P],
 }
 _RESTYPES = {"vit_last_error": C.c_char_p, "vit_last_gemm_kernel": C.c_char_p, "vit_workspace_needed": C.c_size_t}
 

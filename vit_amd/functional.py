@@ -501,3 +501,90 @@ def sgd_step(p, g, buf, p_bf16, *, lr, momentum=0.0, weight_decay=0.0, nesterov=
     n = p.numel() if n is None else n
     h.call("vit_sgd_step", p.data_ptr(), g.data_ptr(), _ptr(buf), _ptr(p_bf16), n, lr, momentum, weight_decay, int(bool(nesterov)),
            _ptr(sqnorm), max_norm, _stream(p))
+
+
+# ------------------------------------------------------------------------------------------------ optimizer: parameter groups
+class GroupTables:
+    """The two device tables of the `*_step_groups` kernels (include/vit_amd_optim.h): `seg_end` (int64) / `seg_group` (int32),
+    one entry per segment, and `groups`, one f32 row {lr, weight_decay, momentum, 0} per group.  `values` mirrors on the host
+    what `groups` holds (None: nothing written yet), so that `optim_groups_write` launches only for a changed number."""
+
+    def __init__(self, seg_end, seg_group, groups):
+        self.seg_end, self.seg_group, self.groups = seg_end, seg_group, groups
+        self.n_segments, self.n_groups = seg_end.numel(), groups.shape[0]
+        self.values = None
+
+
+def optim_group_tables(triples, n_groups: int, device, total: Optional[int] = None) -> GroupTables:
+    """Build and validate the tables from (offset, numel, group) triples: sorted by offset, not overlapping, every offset and
+    every end a multiple of 4 (the last end may instead equal `total`, the buffer's length), group indices in
+    [0, n_groups).  Neighbouring triples of one group become one segment; a gap between two triples (parameters no group
+    owns, which no step covers) falls to the segment behind it."""
+    triples = [(int(o), int(k), int(gi)) for o, k, gi in triples]
+    if not triples or n_groups <= 0:
+        raise ValueError("optim_group_tables: needs at least one (offset, numel, group) triple and one group")
+    ends, owners, prev_end = [], [], 0
+    for i, (off, numel, gi) in enumerate(triples):
+        if off < 0 or numel <= 0:
+            raise ValueError(f"optim_group_tables: triple {i} = ({off}, {numel}, {gi}) is empty or negative")
+        if off < prev_end:
+            raise ValueError(f"optim_group_tables: triple {i} starts at {off}, before the end {prev_end} of the one in front "
+                             f"(triples must be sorted by offset and must not overlap)")
+        if not 0 <= gi < n_groups:
+            raise ValueError(f"optim_group_tables: triple {i} names group {gi}, outside [0, {n_groups})")
+        end = off + numel
+        last = i == len(triples) - 1
+        if off % 4 or (end % 4 and not (last and (total is None or end == total))):
+            raise ValueError(f"optim_group_tables: triple {i} = [{off}, {end}) is not aligned to 4 elements (only the last "
+                             f"end may be, when it is the buffer's length)")
+        if total is not None and end > total:
+            raise ValueError(f"optim_group_tables: triple {i} ends at {end}, past the buffer's length {total}")
+        if owners and owners[-1] == gi and off == prev_end:
+            ends[-1] = end
+        else:
+            ends.append(end)
+            owners.append(gi)
+        prev_end = end
+    return GroupTables(torch.tensor(ends, dtype=torch.int64, device=device), torch.tensor(owners, dtype=torch.int32, device=device),
+                       torch.zeros(n_groups, 4, dtype=torch.float32, device=device))
+
+
+def optim_groups_write(tables: GroupTables, values) -> bool:
+    """`values`: one (lr, weight_decay, momentum) per group.  Writes the device table on the current stream when a number
+    differs from what it holds (vit_optim_groups_write: the numbers travel in kernel arguments); returns whether it did."""
+    values = [(float(a), float(b), float(c)) for a, b, c in values]
+    if len(values) != tables.n_groups:
+        raise ValueError(f"optim_groups_write: {len(values)} rows for a table of {tables.n_groups} groups")
+    if values == tables.values:
+        return False
+    arr = (C.c_float * (3 * len(values)))(*[x for row in values for x in row])
+    _h(tables.groups).call("vit_optim_groups_write", tables.groups.data_ptr(), len(values), arr, _stream(tables.groups))
+    tables.values = values
+    return True
+
+
+def _groups_args(tables: GroupTables, base: int):
+    return int(base), tables.seg_end.data_ptr(), tables.seg_group.data_ptr(), tables.n_segments, tables.groups.data_ptr(), tables.n_groups
+
+
+def adamw_step_groups(p, g, m, v, p_bf16, tables: GroupTables, *, base=0, beta1=0.9, beta2=0.999, eps=1e-8, step=1, sqnorm=None,
+                      max_norm=0.0, n: Optional[int] = None, l2: bool = False):
+    """`adamw_step` (`l2`: `adam_l2_step`) over p = buffer[base : base + n] with each element's group's lr / weight_decay."""
+    h = _h(p)
+    n = p.numel() if n is None else n
+    h.call("vit_adam_l2_step_groups" if l2 else "vit_adamw_step_groups", p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(),
+           _ptr(p_bf16), n, *_groups_args(tables, base), beta1, beta2, eps, step, _ptr(sqnorm), max_norm, _stream(p))
+
+
+def adam_l2_step_groups(p, g, m, v, p_bf16, tables: GroupTables, **kw):
+    adamw_step_groups(p, g, m, v, p_bf16, tables, l2=True, **kw)
+
+
+def sgd_step_groups(p, g, buf, p_bf16, tables: GroupTables, *, base=0, nesterov=False, sqnorm=None, max_norm=0.0,
+                    n: Optional[int] = None):
+    """`sgd_step` over p = buffer[base : base + n] with each element's group's lr / momentum / weight_decay; `buf` may be None
+    when every group's momentum is 0."""
+    h = _h(p)
+    n = p.numel() if n is None else n
+    h.call("vit_sgd_step_groups", p.data_ptr(), g.data_ptr(), _ptr(buf), _ptr(p_bf16), n, *_groups_args(tables, base),
+           int(bool(nesterov)), _ptr(sqnorm), max_norm, _stream(p))

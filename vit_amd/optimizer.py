@@ -10,13 +10,15 @@ against its torch class in tests/.  Any other optimizer type falls through to to
 """
 from __future__ import annotations
 
+import fnmatch
+import re
 from typing import Optional
 
 import torch
 
 from . import functional as vf
 
-__all__ = ["OptModule", "FusedOptimizer", "FusedAdamW", "FusedSGD"]
+__all__ = ["OptModule", "FusedOptimizer", "FusedAdamW", "FusedSGD", "build_param_groups"]
 
 
 class FusedOptimizer(torch.optim.Optimizer):
@@ -38,16 +40,38 @@ class FusedOptimizer(torch.optim.Optimizer):
 
     A subclass provides: `_STATE` (attribute names of its flat state buffers, each None until allocated), `_ensure_state()`,
     `_step_args(group, sqnorm)`, `_update(p, g, states, p_bf16, kw)`, `_extra_buffers(p)`; and for a captured step
-    (vit_amd/graph.py) `_graph_record()`, `_graph_update(...)`, optionally `_graph_betas()` / `_graph_signature()`."""
+    (vit_amd/graph.py) `_graph_record()`, `_graph_update(...)`, optionally `_graph_betas()` / `_graph_signature()`.
+
+    Parameter groups (`param_groups=[{"params": [parameters or their names], "lr": ..., "weight_decay": ...}, ...]` at
+    construction, or `add_param_group`; keys a group omits take the defaults; a parameter no group names is not stepped, as in
+    torch).  One group is the path above, unchanged.  With more, every active run of the flat buffer is still ONE launch: the
+    `*_step_groups` kernels (include/vit_amd_optim.h) look each element's lr / weight_decay / momentum up in a segment table
+    built from the partition (rebuilt when it changes) and a group table that is rewritten, ahead of the step, only when a
+    scheduler changed a number.  What the kernel shares across groups (`_SHARED`) must agree, else ValueError.  For these a
+    subclass adds `_SHARED`, `_group_values(group)` and `_update_groups(p, g, states, p_bf16, tables, base, sqnorm)`."""
 
     _STATE = ()
+    _SHARED = ()
 
-    def __init__(self, model, defaults):
+    def __init__(self, model, defaults, param_groups=None):
         self.model = model
-        params = [p for p in model.parameters()]
+        if param_groups is None:
+            params = [p for p in model.parameters()]
+        else:
+            by_name = dict(model.named_parameters())
+            params = []
+            for grp in param_groups:
+                grp = dict(grp)
+                members = grp["params"]
+                members = [members] if isinstance(members, (str, torch.Tensor)) else list(members)
+                unknown = [m for m in members if isinstance(m, str) and m not in by_name]
+                if unknown:
+                    raise ValueError(f"param_groups names parameters the model does not have: {unknown}")
+                grp["params"] = [by_name[m] if isinstance(m, str) else m for m in members]
+                params.append(grp)
         super().__init__(params, defaults)
-        own = {id(p) for p in getattr(model, "_param_list", [])}
-        self._extras = [p for p in params if id(p) not in own]
+        self._part = None
+        self._refresh_members()
         self._extra_state = {}
         self._step = 0
         self._clip: Optional[float] = None
@@ -60,6 +84,62 @@ class FusedOptimizer(torch.optim.Optimizer):
 
     def attach_reducer(self, reducer):
         self._reducer = reducer
+
+    # ------------------------------------------------------------------ parameter groups
+    def add_param_group(self, param_group):
+        super().add_param_group(param_group)
+        if hasattr(self, "_part"):  # torch's constructor adds the initial groups through here, before ours has run
+            self._refresh_members()
+
+    def _partition_signature(self):
+        return tuple(tuple(id(p) for p in grp["params"]) for grp in self.param_groups)
+
+    def _refresh_members(self):
+        """Which group owns which parameter, and which owned parameters lie outside the engine's flat buffer."""
+        own = {id(p) for p in getattr(self.model, "_param_list", [])}
+        self._group_index = {id(p): gi for gi, grp in enumerate(self.param_groups) for p in grp["params"]}
+        self._extras = [p for grp in self.param_groups for p in grp["params"] if id(p) not in own]
+
+    def _group_for(self, p):
+        return self.param_groups[self._group_index[id(p)]]
+
+    def _all_params(self):
+        """Every group's parameters in torch's state_dict numbering (consecutive across the groups)."""
+        return [p for grp in self.param_groups for p in grp["params"]]
+
+    def _partition(self):
+        """(signature, device, vf.GroupTables) of the current partition of the flat buffer into groups; rebuilt when a
+        parameter changed its group (or the buffer its device).  The pad behind an entry belongs to the entry."""
+        sig, flat = self._partition_signature(), self.model.engine.flat
+        if self._part is None or self._part[0] != sig or self._part[1] != flat.device:
+            self._refresh_members()
+            lay, triples = self.model.engine.layout, []
+            for name, p in zip(self.model._param_names, self.model._param_list):
+                off, _ = lay.entries[name]
+                if off < lay.n_trainable and id(p) in self._group_index:
+                    triples.append((off, (lay.numel(name) + 7) // 8 * 8, self._group_index[id(p)]))
+            if not triples:
+                raise ValueError("no parameter group owns a parameter of the model's flat buffer")
+            triples.sort()
+            self._part = (sig, flat.device, vf.optim_group_tables(triples, len(self.param_groups), flat.device))
+        return self._part
+
+    def _check_shared(self):
+        """beta1 / beta2 / eps, or nesterov / dampening, are one kernel argument for the whole launch."""
+        first = self.param_groups[0]
+        for gi, grp in enumerate(self.param_groups[1:], 1):
+            for key in self._SHARED:
+                a, b = first[key], grp[key]
+                if (tuple(a) != tuple(b)) if isinstance(a, (tuple, list)) else (a != b):
+                    raise ValueError(f"{type(self).__name__}: param_groups[{gi}]['{key}'] = {b} differs from group 0's {a}; the "
+                                     f"fused step shares {', '.join(self._SHARED)} across all groups")
+
+    def _sync_group_table(self):
+        """The device group table <- the groups' current numbers, launched only when one changed; returns the tables."""
+        self._check_shared()
+        tables = self._partition()[2]
+        vf.optim_groups_write(tables, [self._group_values(grp) for grp in self.param_groups])
+        return tables
 
     def _flat_states(self):
         """The allocated flat state buffers, in `_STATE` order (all of them or none)."""
@@ -91,7 +171,7 @@ class FusedOptimizer(torch.optim.Optimizer):
         spans = []
         for name, p in zip(self.model._param_names, self.model._param_list):
             off, _ = lay.entries[name]
-            if off >= lay.n_trainable or p.grad is None:
+            if off >= lay.n_trainable or p.grad is None or id(p) not in self._group_index:
                 continue
             gv = eng.g(name)
             if p.grad.data_ptr() != gv.data_ptr():
@@ -120,6 +200,8 @@ class FusedOptimizer(torch.optim.Optimizer):
         eng = self.model.engine
         self._ensure_state()
         g = self.param_groups[0]
+        grouped = len(self.param_groups) > 1
+        tables = self._sync_group_table() if grouped else None  # also re-reads who owns what
         runs = self._active_ranges()
         extras = [p for p in self._extras if p.grad is not None]
         if not runs and not extras:
@@ -148,13 +230,19 @@ class FusedOptimizer(torch.optim.Optimizer):
         kw = self._step_args(g, sq)
         states = self._flat_states()
         for a, b in runs:
-            self._update(eng.flat[a:b], eng.grads[a:b], [s[a:b] for s in states], None if shadow is None else shadow[a:b], kw)
+            if grouped:  # one launch per run all the same: the kernel looks the groups up from the run's offset `a`
+                self._update_groups(eng.flat[a:b], eng.grads[a:b], [s[a:b] for s in states],
+                                    None if shadow is None else shadow[a:b], tables, a, sq)
+            else:
+                self._update(eng.flat[a:b], eng.grads[a:b], [s[a:b] for s in states], None if shadow is None else shadow[a:b], kw)
         if red is not None:
             red.all_gather_params(eng.flat)
             if shadow is not None:
                 vf.cast_f32_bf16(eng.flat, shadow)
         eng.mark_shadow_fresh()  # the kernel rewrote flat AND shadow through raw pointers
         for p in extras:
+            if grouped:
+                kw = self._step_args(self._group_for(p), sq)
             self._update(p.data.view(-1), p.grad.contiguous().view(-1), self._extra_buffers(p), None, kw)
         return loss
 
@@ -215,27 +303,35 @@ class FusedOptimizer(torch.optim.Optimizer):
 
     def _graph_signature(self):
         """What of this optimizer's set-up is frozen into a capture; `_graph_validate` raises ValueError when a replay would
-        no longer be the eager step."""
-        return None
+        no longer be the eager step.  Here: the partition into groups (None for a single group) -- the capture holds the
+        segment table's address and the choice between the plain and the grouped kernel."""
+        return self._partition_signature() if len(self.param_groups) > 1 else None
 
     def _graph_validate(self, signature):
-        pass
+        if signature != FusedOptimizer._graph_signature(self):
+            raise ValueError("the optimizer's parameter groups were repartitioned after the step was captured")
+
+    def _graph_groups(self):
+        """Inside `_graph_update`: the tables for the grouped `_dyn` launch, or None for a single group.  The group table was
+        brought up to date by `_graph_record()` ahead of the capture / the replay."""
+        return self._partition()[2] if len(self.param_groups) > 1 else None
 
     # ------------------------------------------------------------------ torch.optim-format state
     def _param_slices(self):
-        """(index in param_groups[0]["params"], offset, numel, shape) of every trainable parameter in the flat buffer."""
+        """(torch's state_dict index, offset, numel, shape) of every trainable parameter in the flat buffer a group owns."""
         lay = self.model.engine.layout
-        index = {id(p): i for i, p in enumerate(self.param_groups[0]["params"])}
+        index = {id(p): i for i, p in enumerate(self._all_params())}
         for name, p in zip(self.model._param_names, self.model._param_list):
             off, shape = lay.entries[name]
-            if off < lay.n_trainable:
+            if off < lay.n_trainable and id(p) in index:
                 yield index[id(p)], off, lay.numel(name), shape
 
     def _groups_dict(self):
-        groups = []
+        groups, start = [], 0
         for grp in self.param_groups:
             d = {k: (list(v) if isinstance(v, tuple) else v) for k, v in grp.items() if k != "params"}
-            d["params"] = list(range(len(grp["params"])))
+            d["params"] = list(range(start, start + len(grp["params"])))
+            start += len(grp["params"])
             groups.append(d)
         return groups
 
@@ -254,9 +350,11 @@ class FusedAdamW(FusedOptimizer):
     torch optimizer through a Lightning checkpoint."""
 
     _STATE = ("_m", "_v")
+    _SHARED = ("betas", "eps")
 
-    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, adam_l2: bool = False):
-        super().__init__(model, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, adam_l2: bool = False,
+                 param_groups=None):
+        super().__init__(model, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay), param_groups)
         self.adam_l2 = bool(adam_l2)
         self._m = None
         self._v = None
@@ -272,6 +370,14 @@ class FusedAdamW(FusedOptimizer):
     def _update(self, p, g, states, p_bf16, kw):
         (vf.adam_l2_step if self.adam_l2 else vf.adamw_step)(p, g, states[0], states[1], p_bf16, **kw)
 
+    def _group_values(self, grp):
+        return float(grp["lr"]), float(grp["weight_decay"]), 0.0
+
+    def _update_groups(self, p, g, states, p_bf16, tables, base, sq):
+        g0 = self.param_groups[0]
+        vf.adamw_step_groups(p, g, states[0], states[1], p_bf16, tables, base=base, beta1=g0["betas"][0], beta2=g0["betas"][1],
+                             eps=g0["eps"], step=self._step, sqnorm=sq, max_norm=float(self._clip or 0.0), l2=self.adam_l2)
+
     def _extra_buffers(self, p):
         st = self._extra_state.get(id(p))
         if st is None or st[0].device != p.device:
@@ -282,14 +388,26 @@ class FusedAdamW(FusedOptimizer):
         return tuple(self.param_groups[0]["betas"])
 
     def _graph_record(self):
+        if len(self.param_groups) > 1:  # the rates live in the group table, not in the record
+            self._sync_group_table()
+            return {}
         return {2: float(self.param_groups[0]["lr"])}
 
     def _graph_update(self, h, n, p_bf16, sqnorm, stream):
         """The update of flat[:n] inside a capture: lr and the bias corrections come from the bound record, everything else
-        is frozen at capture."""
+        is frozen at capture.  With parameter groups: the bias corrections from the record, lr and weight_decay from the group
+        table (written ahead of each replay when they changed)."""
         from . import _cabi
 
         eng, g = self.model.engine, self.param_groups[0]
+        t = self._graph_groups()
+        if t is not None:
+            name = "vit_adam_l2_step_groups_dyn" if self.adam_l2 else "vit_adamw_step_groups_dyn"
+            _cabi.check(getattr(h.lib, name)(h.h, eng.flat.data_ptr(), eng.grads.data_ptr(), self._m.data_ptr(),
+                                             self._v.data_ptr(), p_bf16, n, 0, t.seg_end.data_ptr(), t.seg_group.data_ptr(),
+                                             t.n_segments, t.groups.data_ptr(), t.n_groups, g["betas"][0], g["betas"][1],
+                                             g["eps"], sqnorm, float(self._clip or 0.0), stream), name)
+            return
         name = "vit_adam_l2_step_dyn" if self.adam_l2 else "vit_adamw_step_dyn"
         _cabi.check(getattr(h.lib, name)(h.h, eng.flat.data_ptr(), eng.grads.data_ptr(), self._m.data_ptr(), self._v.data_ptr(),
                                          p_bf16, n, g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"], sqnorm,
@@ -297,7 +415,7 @@ class FusedAdamW(FusedOptimizer):
 
     # ------------------------------------------------------------------ torch.optim.AdamW-format state
     def state_dict(self):
-        index = {id(p): i for i, p in enumerate(self.param_groups[0]["params"])}
+        index = {id(p): i for i, p in enumerate(self._all_params())}
         state = {}
         if self._m is not None and self._step > 0:
             for i, off, n, shape in self._param_slices():
@@ -324,7 +442,7 @@ class FusedAdamW(FusedOptimizer):
         flat = self.model.engine.flat
         if self._m is None or self._m.device != flat.device:
             self._m, self._v = torch.zeros_like(flat), torch.zeros_like(flat)
-        params = self.param_groups[0]["params"]
+        params = self._all_params()
         names = {id(p): n for n, p in zip(self.model._param_names, self.model._param_list)}
         step = 0
         for idx, st in sd["state"].items():
@@ -352,8 +470,9 @@ class FusedSGD(FusedOptimizer):
     `model.parameters()` order, absent while no buffer exists)."""
 
     _STATE = ("_buf",)
+    _SHARED = ("nesterov", "dampening")
 
-    def __init__(self, model, lr=1e-3, momentum=0, dampening=0, weight_decay=0, nesterov=False):
+    def __init__(self, model, lr=1e-3, momentum=0, dampening=0, weight_decay=0, nesterov=False, param_groups=None):
         if dampening != 0:
             raise ValueError("FusedSGD supports dampening = 0 only (a zero momentum buffer then reproduces torch's first step)")
         if lr < 0 or momentum < 0 or weight_decay < 0:
@@ -361,13 +480,24 @@ class FusedSGD(FusedOptimizer):
         if nesterov and momentum <= 0:
             raise ValueError("Nesterov momentum requires a momentum and zero dampening")
         super().__init__(model, dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov,
-                                     maximize=False, foreach=None, differentiable=False, fused=None))
+                                     maximize=False, foreach=None, differentiable=False, fused=None), param_groups)
         self._buf = None
 
     def _ensure_state(self):
         self._ensure_sq()
-        if self._buf is not None or self.param_groups[0]["momentum"] != 0:
+        if self._buf is not None or any(grp["momentum"] != 0 for grp in self.param_groups):
             self._ensure_flat(self._STATE)
+
+    def _group_values(self, grp):
+        if grp["dampening"] != 0 or grp.get("maximize"):
+            raise ValueError("FusedSGD supports neither dampening nor maximize")
+        if grp["momentum"] < 0 or (grp["nesterov"] and grp["momentum"] <= 0):
+            raise ValueError(f"FusedSGD: momentum = {grp['momentum']} (nesterov = {grp['nesterov']})")
+        return float(grp["lr"]), float(grp["weight_decay"]), float(grp["momentum"])
+
+    def _update_groups(self, p, g, states, p_bf16, tables, base, sq):
+        vf.sgd_step_groups(p, g, states[0] if states else None, p_bf16, tables, base=base,
+                           nesterov=bool(self.param_groups[0]["nesterov"]), sqnorm=sq, max_norm=float(self._clip or 0.0))
 
     def _step_args(self, g, sq):
         if g["dampening"] != 0 or g.get("maximize"):
@@ -379,7 +509,7 @@ class FusedSGD(FusedOptimizer):
         vf.sgd_step(p, g, states[0] if states and kw["momentum"] != 0 else None, p_bf16, **kw)
 
     def _extra_buffers(self, p):
-        if self.param_groups[0]["momentum"] == 0:
+        if self._group_for(p)["momentum"] == 0:
             return ()
         st = self._extra_state.get(id(p))
         if st is None or st[0].device != p.device:
@@ -387,17 +517,22 @@ class FusedSGD(FusedOptimizer):
         return st
 
     def _graph_record(self):
+        if len(self.param_groups) > 1:  # rates and momenta live in the group table, not in the record
+            self._sync_group_table()
+            return {}
         g = self.param_groups[0]
         return {2: float(g["lr"]), 6: float(g["momentum"])}
 
     def _graph_signature(self):
-        return self._buf is not None
+        return self._buf is not None, super()._graph_signature()
 
-    def _graph_validate(self, had_buffer):
-        mu = self.param_groups[0]["momentum"]
+    def _graph_validate(self, signature):
+        had_buffer, partition = signature
+        super()._graph_validate(partition)
+        mu = max(grp["momentum"] for grp in self.param_groups)
         if mu != 0 and not had_buffer:
             raise ValueError(f"SGD's momentum became {mu} after the step was captured without a momentum buffer")
-        if mu == 0 and had_buffer:
+        if mu == 0 and had_buffer and partition is None:  # (the grouped kernel skips a zero-momentum group's buffer itself)
             raise ValueError("SGD's momentum became 0 after the step was captured with a momentum buffer")
 
     def _graph_update(self, h, n, p_bf16, sqnorm, stream):
@@ -406,6 +541,14 @@ class FusedSGD(FusedOptimizer):
         from . import _cabi
 
         eng, g = self.model.engine, self.param_groups[0]
+        t = self._graph_groups()
+        if t is not None:  # lr, momentum and weight decay per group from the table; nesterov frozen at capture
+            _cabi.check(h.lib.vit_sgd_step_groups_dyn(h.h, eng.flat.data_ptr(), eng.grads.data_ptr(),
+                                                      None if self._buf is None else self._buf.data_ptr(), p_bf16, n, 0,
+                                                      t.seg_end.data_ptr(), t.seg_group.data_ptr(), t.n_segments,
+                                                      t.groups.data_ptr(), t.n_groups, int(bool(g["nesterov"])), sqnorm,
+                                                      float(self._clip or 0.0), stream), "vit_sgd_step_groups_dyn")
+            return
         if g["dampening"] != 0 or g.get("maximize"):
             raise ValueError("FusedSGD supports neither dampening nor maximize")
         _cabi.check(h.lib.vit_sgd_step_dyn(h.h, eng.flat.data_ptr(), eng.grads.data_ptr(),
@@ -415,7 +558,7 @@ class FusedSGD(FusedOptimizer):
 
     # ------------------------------------------------------------------ torch.optim.SGD-format state
     def state_dict(self):
-        index = {id(p): i for i, p in enumerate(self.param_groups[0]["params"])}
+        index = {id(p): i for i, p in enumerate(self._all_params())}
         state = {}
         if self._buf is not None:
             for i, off, n, shape in self._param_slices():
@@ -428,7 +571,7 @@ class FusedSGD(FusedOptimizer):
 
     def load_state_dict(self, sd):
         lay = self.model.engine.layout
-        params = self.param_groups[0]["params"]
+        params = self._all_params()
         names = {id(p): n for n, p in zip(self.model._param_names, self.model._param_list)}
         self._buf, self._extra_state = None, {}
         for idx, st in sd["state"].items():
@@ -485,14 +628,61 @@ def _scheduler_kwargs(fam: str, cfg: dict, lr: float) -> dict:
     return kw
 
 
+_NO_DECAY_NAMES = ("vit.embeddings.cls_token", "vit.embeddings.position_embeddings")
+_LAYER = re.compile(r"(?:^|\.)encoder\.layer\.(\d+)\.")
+
+
+def _layer_id(name: str, n_layers: int) -> int:
+    """Depth of a parameter for `opt.layer_decay`: 0 for the embeddings, i + 1 for encoder layer i, L + 1 for what follows the
+    encoder (final LayerNorm, pooler, head) -- and for whatever sits outside the ViT's depth (an input preprocessor), which
+    therefore keeps `lr`."""
+    m = _LAYER.search(name)
+    if m:
+        return int(m.group(1)) + 1
+    return 0 if name.startswith("vit.embeddings.") else n_layers + 1
+
+
+def build_param_groups(model, lr: float, weight_decay, no_decay=None, layer_decay=None):
+    """torch-style parameter groups over `model.named_parameters()` for `opt.no_decay` / `opt.layer_decay`, or None when
+    neither is set.  Every parameter lands in exactly one group; groups are ordered by depth, the decaying one first.
+
+    no_decay: True = weight_decay 0 for parameters of at most one dimension (biases, LayerNorm weight and bias) and for
+    vit.embeddings.cls_token / vit.embeddings.position_embeddings (the Conv1D patch weight [D, 1, P] decays); a list = exactly
+    the parameters whose name matches one of its fnmatch patterns.
+    layer_decay f: lr * f ** (L + 1 - id), id as in `_layer_id`."""
+    if not no_decay and layer_decay is None:
+        return None
+    named = list(model.named_parameters())
+    if isinstance(no_decay, str):
+        no_decay = [no_decay]
+    n_layers = 1 + max((int(m.group(1)) for m in (_LAYER.search(n) for n, _ in named) if m), default=-1)
+    groups = {}
+    for name, p in named:
+        if no_decay is True:
+            skip = p.ndim <= 1 or name in _NO_DECAY_NAMES
+        else:
+            skip = bool(no_decay) and any(fnmatch.fnmatchcase(name, pat) for pat in no_decay)
+        depth = n_layers + 1 if layer_decay is None else _layer_id(name, n_layers)
+        groups.setdefault((depth, skip), []).append(p)
+    scale = 1.0 if layer_decay is None else float(layer_decay)
+    return [{"params": members, "lr": lr * scale ** (n_layers + 1 - depth), "weight_decay": 0.0 if skip else weight_decay}
+            for (depth, skip), members in sorted(groups.items(), key=lambda kv: kv[0])]
+
+
 class OptModule:
     """The optimizer / scheduler factory behind `configure_optimizers` (reference: src/opt/optimizer.py:1-173).  Same config
     keys (`lr`, `type`, `weight_decay`, `lr_sch`, `warmup.{ratio,epochs}` / `warmup_ratio` / `warmup_epochs`, the scheduler's
     own keys), same result shape (an optimizer, or Lightning's {"optimizer", "lr_scheduler": {scheduler, monitor, ...}});
-    behaviour pinned case by case on the reference's class in tests/golden/opt.json."""
+    behaviour pinned case by case on the reference's class in tests/golden/opt.json.
+
+    Two keys beside the reference's, both absent by default (then nothing differs): `no_decay` and `layer_decay`
+    (`build_param_groups`).  With either, every optimizer type -- fused or torch's -- is built over those parameter groups, and
+    a one-cycle scheduler gets the groups' rates as its `max_lr` list (a scalar would flatten them)."""
 
     def __init__(self, lr, monitor_metric="loss", opt_type="adam", weight_decay=0.0, lr_scheduler_name=None,
-                 warmup_ratio=0.0, warmup_epochs=None, **kwargs) -> None:
+                 warmup_ratio=0.0, warmup_epochs=None, no_decay=None, layer_decay=None, **kwargs) -> None:
+        self.no_decay = no_decay
+        self.layer_decay = None if layer_decay is None else float(layer_decay)
         self.lr = float(lr)
         self.monitor_metric = monitor_metric
         self.opt_type = opt_type
@@ -514,6 +704,9 @@ class OptModule:
             warmup_ratio=warm.get("ratio", config.get("warmup_ratio", 0.0)),
             warmup_epochs=warm.get("epochs", config.get("warmup_epochs", None)),
         )
+        for key in ("no_decay", "layer_decay"):  # absent by default: the reference's call, argument for argument
+            if config.get(key) is not None and config.get(key) is not False:
+                common[key] = config[key]
         if "lr_sch" not in config:
             return cls(**common)
         name = config["lr_sch"].lower()
@@ -522,14 +715,17 @@ class OptModule:
     def _make_optimizer(self, model):
         from .specvit import MyViT
 
+        groups = build_param_groups(model, self.lr, self.weight_decay, self.no_decay, self.layer_decay)
+        fused = {} if groups is None else {"param_groups": groups}
         if isinstance(model, MyViT) and self.opt_type in ("adam", "adamw"):
             # torch.optim.Adam's weight_decay is L2-in-the-gradient; with the reference's default weight_decay=0
             # (optimizer.py:51) Adam == AdamW, and only with a decay does 'adam' need the L2 form of the kernel
             return FusedAdamW(model, lr=self.lr, weight_decay=self.weight_decay,
-                              adam_l2=self.opt_type == "adam" and bool(self.weight_decay))
+                              adam_l2=self.opt_type == "adam" and bool(self.weight_decay), **fused)
         if isinstance(model, MyViT) and self.opt_type == "sgd":
-            return FusedSGD(model, lr=self.lr, weight_decay=self.weight_decay)
-        return self.opt_fns[self.opt_type](model.parameters(), lr=self.lr, weight_decay=self.weight_decay)
+            return FusedSGD(model, lr=self.lr, weight_decay=self.weight_decay, **fused)
+        return self.opt_fns[self.opt_type](model.parameters() if groups is None else groups, lr=self.lr,
+                                           weight_decay=self.weight_decay)
 
     def _warmup_length(self) -> Optional[int]:
         """Epochs of linear warm-up in front of the scheduler, or None.  One-cycle brings its own."""
@@ -550,12 +746,15 @@ class OptModule:
             raise ValueError(f"Unknown scheduler: {name}")
         sched_mod = torch.optim.lr_scheduler
         n_warm = self._warmup_length()
+        kwargs = self.kwargs
+        if len(optimizer.param_groups) > 1 and "max_lr" in kwargs:  # one-cycle: each group cycles up to its own rate
+            kwargs = dict(kwargs, max_lr=[grp["lr"] for grp in optimizer.param_groups])
         if n_warm is None:
-            scheduler = self.lr_schedulers[name](optimizer, **self.kwargs)
+            scheduler = self.lr_schedulers[name](optimizer, **kwargs)
         else:  # LinearLR from 10 % of the target rate, then the scheduler proper (constructed in this order: each
             # constructor records / touches the optimizer's learning rate)
             ramp = sched_mod.LinearLR(optimizer, start_factor=0.1, total_iters=n_warm)
-            main = self.lr_schedulers[name](optimizer, **self.kwargs)
+            main = self.lr_schedulers[name](optimizer, **kwargs)
             scheduler = sched_mod.SequentialLR(optimizer, schedulers=[ramp, main], milestones=[n_warm])
         entry = {"scheduler": scheduler, "monitor": f"val_{self.monitor_metric}"}
         fam = _family(name)
