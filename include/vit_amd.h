@@ -92,21 +92,18 @@ int vit_handle_set_option(vit_handle h, const char* name, int value);
 
 /* Per-step state in device memory, for a training step captured as a hipGraph (HIP streams and graphs instead of a tracing
  * compiler: kernel arguments are frozen at capture, so what changes from step to step must be read from memory).
- * `state`: 32 bytes, 16-byte aligned: { u32 key0, key1; f32 lr, bc1, rsqrt_bc2; u32 step; f32 momentum; u32 pad },
+ * `state`: 32 bytes, 16-byte aligned: { u32 key0, key1; u32 reserved; f32 bc1, rsqrt_bc2; u32 step; u32 reserved[2] },
  * caller-owned.
  * While bound (NULL unbinds), every call through this handle that takes (dropout_p, seed, site) XORs the state's keys
  * into its dropout keys at kernel entry: the masks of a replay are those of (seed, site, step).  vit_step_advance (one
  * tiny kernel, first node of the captured step) does step += 1, derives the keys from (base_seed, step) and AdamW's
- * bias corrections from step; `lr` and `momentum` are the host's to write (a scheduler changes them between replays: one-cycle
- * cycles both on every step).
- * vit_adamw_step_dyn = vit_adamw_step with lr / bias corrections read from the state; vit_adam_l2_step_dyn and
- * vit_sgd_step_dyn (vit_amd_optim.h) read lr / bias corrections and lr / momentum from it in the same way.
+ * bias corrections from step.  The reserved words are neither written nor read: what a scheduler changes between replays
+ * (learning rates, SGD's momentum; one-cycle cycles both on every step) lives in the optimizer's group table
+ * (vit_optim_groups_write, vit_amd_optim.h), and the vit_*_step_groups_dyn forms take only the bias corrections from here.
  * Replaces what Lightning's loop hands torch per step: the generator advance behind nn.Dropout and optimizer.step()'s
  * step count (basemodule.py:230-251). */
 int vit_step_state_bind(vit_handle h, void* state);
 int vit_step_advance(vit_handle h, uint64_t base_seed, float beta1, float beta2, vit_stream stream);
-int vit_adamw_step_dyn(vit_handle h, float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, float beta1,
-                       float beta2, float eps, float weight_decay, const float* sqnorm, float max_norm, vit_stream stream);
 
 /* ------------------------------------------------------------------------------------------------ GEMM
  * C = epilogue(alpha * op(A) * op(B)), bf16 MFMA (v_mfma_f32_16x16x32_bf16), fp32 accumulate.

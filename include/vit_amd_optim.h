@@ -21,9 +21,6 @@
  *   after the subtraction (float(1 - 0.999) = 0.001f; 1.f - 0.999f = 0.00099998713 would leave exp_avg_sq 1.3e-5 off).  The
  *   f32 arguments have lost those bits, so each beta is read back as the shortest decimal that names it (0.999f -> 0.999),
  *   which is the caller's own number for any beta of up to 7 significant digits.  vit_adamw_step keeps 1.f - beta.
- * vit_sgd_step_dyn / vit_adam_l2_step_dyn: the forms for a captured step (vit_step_state_bind): lr and momentum, or lr and the
- *   bias corrections, are read from the bound record at kernel entry.  vit_sgd_step_dyn with buf == NULL is the momentum-free
- *   update whatever the record holds.  VIT_ERR_ARG when no record is bound.
  *
  * Parameter groups (torch.optim's param_groups: no-decay sets, layer-wise learning rates) in ONE launch: vit_*_step_groups.
  *   The flat buffer alternates decaying and non-decaying parameters (8 runs per encoder layer), so a launch per run would be
@@ -37,15 +34,18 @@
  *   `base` is the absolute element offset of p[0] in the segment table's coordinates (a multiple of 4, as the 16-byte accesses
  *   need anyway): the call updates [base, base + n).  A sub-run of the buffer (the active runs when parameters are frozen, a
  *   rank's shard) gives the bits the whole-buffer call gives there, wherever it starts and ends.
- *   Arithmetic: the ungrouped entry point's, with the element's group's numbers in place of the scalar arguments -- on any
- *   segment bit-identical to that entry point called on the slice.  beta1, beta2, eps, nesterov, `step` and the clip
- *   coefficient stay call-wide.  vit_sgd_step_groups: a group whose momentum is 0 neither reads nor writes its part of buf
+ *   Arithmetic: the by-value entry point's, with the element's group's numbers in place of the scalar arguments -- on any
+ *   segment bit-identical to that entry point called on the slice: each family is ONE kernel, and the by-value entry points
+ *   launch it without tables, their scalars as its only row.  Without tables, or with a table of one segment, the row is taken
+ *   once per kernel and the loop is the plain grid-stride loop: a one-group optimizer is a one-row table at no cost.
+ *   beta1, beta2, eps, nesterov, `step` and the clip coefficient stay call-wide.  vit_sgd_step_groups: a group whose momentum is 0 neither reads nor writes its part of buf
  *   (vit_sgd_step with momentum 0); buf == NULL is the momentum-free update whatever the table holds.  No atomics,
  *   deterministic.  Offsets past the last end count to the last segment and a group index past the table to the last group,
  *   so a malformed table cannot make a kernel read outside the tables; beyond that the tables' contents are the caller's job
  *   (vit_amd.functional.optim_group_tables checks them where they are built).
- *   The `_dyn` forms (a captured step) take the bias corrections, and nothing else, from the bound record; learning rates and
- *   momenta come from the group table in both forms (vit_sgd_step_groups_dyn only insists on the bound record).
+ *   The `_dyn` forms (a captured step, vit_step_state_bind) take the bias corrections, and nothing else, from the bound record;
+ *   learning rates and momenta come from the group table in both forms (vit_sgd_step_groups_dyn only insists on the bound
+ *   record).  They are the only forms for a captured step, for one group or many.
  *   VIT_ERR_ARG, before anything is launched: a NULL p, g, state buffer or table; n <= 0; n_segments <= 0; n_groups <= 0;
  *   base < 0 or not a multiple of 4; step < 1; nesterov with buf == NULL; no record bound (`_dyn`).
  * vit_optim_groups_write: writes groups[0 .. n_groups) from `values`, n_groups HOST rows of {lr, weight_decay, momentum}.  The
@@ -64,14 +64,9 @@ extern "C" {
 
 int vit_sgd_step(vit_handle h, float* p, const float* g, float* buf, void* p_bf16, int64_t n, float lr, float momentum,
                  float weight_decay, int nesterov, const float* sqnorm, float max_norm, vit_stream stream);
-int vit_sgd_step_dyn(vit_handle h, float* p, const float* g, float* buf, void* p_bf16, int64_t n, float weight_decay,
-                     int nesterov, const float* sqnorm, float max_norm, vit_stream stream);
 int vit_adam_l2_step(vit_handle h, float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, float lr,
                      float beta1, float beta2, float eps, float weight_decay, int step, const float* sqnorm,
                      float max_norm, vit_stream stream);
-int vit_adam_l2_step_dyn(vit_handle h, float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, float beta1,
-                         float beta2, float eps, float weight_decay, const float* sqnorm, float max_norm,
-                         vit_stream stream);
 
 #define VIT_OPTIM_GROUP_STRIDE 4 /* f32 per group-table row: lr, weight_decay, momentum, 0 */
 

@@ -318,7 +318,7 @@ def test_one_stream_and_two_streams_give_the_same_bits(dev, tag, tail):
 # every export of the parent's header with its parameter count: the CLS tail ADDS entry points and one descriptor field
 _EXPORTS = {
     'vit_version': 0, 'vit_last_error': 0, 'vit_create': 2, 'vit_destroy': 1, 'vit_set_workspace': 3, 'vit_set_option': 2,
-    'vit_handle_set_option': 3, 'vit_step_state_bind': 2, 'vit_step_advance': 5, 'vit_adamw_step_dyn': 14, 'vit_gemm': 3,
+    'vit_handle_set_option': 3, 'vit_step_state_bind': 2, 'vit_step_advance': 5, 'vit_gemm': 3,
     'vit_last_gemm_kernel': 0, 'vit_linear_fwd': 16, 'vit_linear_bwd_dx': 10, 'vit_linear_bwd_dw': 9, 'vit_layernorm_fwd': 12,
     'vit_layernorm_fwd_residual': 15, 'vit_layernorm_bwd': 14, 'vit_layernorm_bwd_fused': 20, 'vit_attention_fwd': 15,
     'vit_attention_bwd': 19, 'vit_attention_probs': 10, 'vit_unfold_cast': 10, 'vit_fold_add': 9, 'vit_add_noise': 8,

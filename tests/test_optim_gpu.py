@@ -189,6 +189,62 @@ def test_fused_optimizer_equals_torch_on_the_model(dev, kind):
     assert any(not torch.equal(p.detach(), p0) for p, p0 in zip(model.parameters(), start))
 
 
+@pytest.mark.parametrize("kind", ["adamw", "sgd"])
+def test_one_group_follows_its_param_group_from_step_to_step(dev, kind):
+    """One group is a one-segment, one-row table: `param_groups[0]["lr"]` (for SGD also the momentum, 0 -> 0.9 -> 0) changes
+    between the steps and every step agrees with torch's class at the model-level gate.  While SGD's momentum is 0 the buffer
+    is neither read nor written: there is none after step 1, and a NaN-poisoned slice of it stays poisoned in step 4."""
+    from test_parity_gpu import setup
+    from vit_amd.optimizer import FusedAdamW, FusedSGD
+
+    rc, g, sd, model, x, labels = setup("c1", dev)
+    model.eval()
+    twins = [torch.nn.Parameter(p.detach().clone()) for p in model.parameters()]
+    start = [p.detach().clone() for p in model.parameters()]
+    if kind == "sgd":
+        kw = dict(lr=1e-2, weight_decay=0.01)
+        fused, ref = FusedSGD(model, **kw), torch.optim.SGD(twins, **kw)
+        lrs, mus = [1e-2, 5e-3, 2e-2, 1e-3], [0.0, 0.9, 0.9, 0.0]
+    else:
+        kw = dict(lr=1e-3, weight_decay=0.05)
+        fused, ref = FusedAdamW(model, **kw), torch.optim.AdamW(twins, **kw)
+        lrs, mus = [1e-3, 5e-4, 2e-3, 1e-4], [None] * 4
+    assert len(fused.param_groups) == 1
+    fused.set_grad_clip(MAX_NORM)
+    poisoned = slice(1024, 1024 + 264)
+    for s, (lr, mu) in enumerate(zip(lrs, mus)):
+        for opt in (fused, ref):
+            opt.param_groups[0]["lr"] = lr
+            if mu is not None:
+                opt.param_groups[0]["momentum"] = mu
+        if kind == "sgd" and s == 3:
+            fused._buf[poisoned] = float("nan")
+        fused.zero_grad()
+        model(x, labels=labels).loss.backward()
+        norm = torch.nn.utils.clip_grad_norm_(_hand_over_grads(model, twins), MAX_NORM)
+        fused.step()
+        ref.step()
+        got = float(fused.last_grad_norm.sqrt())
+        assert abs(got - float(norm)) <= 1e-6 * float(norm), (s, got, float(norm))
+        _assert_same(model, twins, start, s)
+        if kind == "sgd" and s == 0:
+            assert fused._buf is None
+        if kind == "sgd" and s == 2:  # the buffer torch keeps, before a slice of ours is poisoned
+            lay = model.engine.layout
+            for (name, p), tw in zip(model.named_parameters(), twins):
+                if p.grad is not None:
+                    off = lay.entries[name][0]
+                    e = rel(fused._buf[off:off + p.numel()], ref.state[tw]["momentum_buffer"].reshape(-1))
+                    assert e < 2e-6, (name, e)
+    t = fused._partition()[2]
+    assert (t.n_segments, t.n_groups) == (1, 1)
+    if kind == "sgd":
+        assert torch.isnan(fused._buf[poisoned]).all() and torch.isfinite(model.engine.flat).all()
+        rest = fused._buf.clone()
+        rest[poisoned] = 0
+        assert torch.isfinite(rest).all() and float(rest.abs().max()) > 0
+
+
 # ------------------------------------------------------------------------------------------------------- state and trainer
 @pytest.mark.parametrize("kind", ["sgd_momentum", "adam_l2"])
 def test_fused_state_is_torch_state(dev, kind):
@@ -331,7 +387,7 @@ def _graph_vs_eager(dev, precision, opt_cfg, mid_run_lr):
 
 @pytest.mark.parametrize("precision", ["32", "bf16-mixed"])
 def test_hip_graph_sgd_one_cycle_equals_eager(dev, precision):
-    """lr AND momentum change on every replay (both read from the device record): four replays == four eager steps bit for
+    """lr AND momentum change on every replay (both read from the group table): four replays == four eager steps bit for
     bit in losses, parameters, momentum buffer and clipping norm."""
     e = _graph_vs_eager(dev, precision, {"type": "SGD", "lr": 1e-2, "lr_sch": "onecycle"}, None)
     assert len({t for t in e[5]}) == 4 and all(mu for _, mu in e[5])
@@ -359,6 +415,38 @@ def test_hip_graph_refuses_a_momentum_that_appears_after_capture(dev):
         loss = trainer.training_step(module, b, 1)
     assert not trainer.use_graph and torch.isfinite(loss) and trainer.optimizer._buf is not None
     assert trainer.global_step == 2
+
+
+def test_hip_graph_keeps_a_momentum_that_becomes_zero_on_the_graph(dev):
+    """Captured with a momentum buffer, a momentum that becomes 0 stays on the graph: the kernel skips a zero-momentum row's
+    buffer itself.  No warning, the buffer keeps its bits over the replay, and the parameters are the eager twin's bit for bit."""
+    from test_trainer_gpu import Batches, c1_config, make
+
+    b = tuple(t.to(dev) for t in next(iter(Batches(16, 5))))
+    finals = {}
+    for mode in ("eager", "graph"):
+        cfg = c1_config(precision="bf16-mixed", hip_graph=(mode == "graph"))
+        cfg["opt"] = {"type": "SGD", "lr": 1e-2}
+        module, trainer = make(cfg)
+        module.model.config.hidden_dropout_prob = 0.0
+        module.model.config.attention_probs_dropout_prob = 0.0
+        trainer._setup(module)
+        module.train()
+        opt = trainer.optimizer
+        opt.param_groups[0]["momentum"] = 0.9
+        with warnings.catch_warnings(record=True) as caught:
+            warnings.simplefilter("always")
+            trainer.training_step(module, b, 0)
+            assert opt._buf is not None and float(opt._buf.abs().max()) > 0
+            before = opt._buf.detach().clone()
+            opt.param_groups[0]["momentum"] = 0
+            loss = trainer.training_step(module, b, 1)
+        assert not [w for w in caught if "hip_graph" in str(w.message)], [str(w.message) for w in caught]
+        assert trainer.use_graph == (mode == "graph") and torch.isfinite(loss) and trainer.global_step == 2
+        assert torch.equal(opt._buf, before)
+        finals[mode] = (module.model.engine.flat.detach().clone(), before, float(loss))
+    assert torch.equal(finals["eager"][0], finals["graph"][0]) and torch.equal(finals["eager"][1], finals["graph"][1])
+    assert finals["eager"][2] == finals["graph"][2]
 
 
 # -------------------------------------------------------------------------------------------------------- data parallelism

@@ -299,6 +299,29 @@ def test_groups_by_name_at_construction_and_by_add_param_group(vit):
     assert part._graph_signature() == opt._graph_signature() != None  # noqa: E711  (the partition is part of a capture)
 
 
+def test_one_group_capture_signature_is_the_partition(vit):
+    """A capture of a one-group optimizer pins the partition like any other: it holds the segment table's address."""
+    from vit_amd.optimizer import FusedAdamW, FusedSGD
+
+    rest = [p for n, p in vit.named_parameters() if not n.endswith(".bias")]
+    biases = [p for n, p in vit.named_parameters() if n.endswith(".bias")]
+    opt = FusedAdamW(vit, lr=1e-3, param_groups=[{"params": rest}])
+    old = opt._graph_signature()
+    assert len(opt.param_groups) == 1 and old == opt._partition_signature() == (tuple(id(p) for p in rest),)
+    opt._graph_validate(old)
+    opt.add_param_group({"params": biases, "weight_decay": 0.0})
+    with pytest.raises(ValueError, match="repartitioned"):
+        opt._graph_validate(old)
+    sgd = FusedSGD(vit, lr=1e-2)
+    old = sgd._graph_signature()
+    assert len(sgd.param_groups) == 1 and old == (False, sgd._partition_signature())
+    sgd._graph_validate(old)
+    moved = sgd.param_groups[0]["params"].pop()
+    sgd.add_param_group({"params": [moved]})
+    with pytest.raises(ValueError, match="repartitioned"):
+        sgd._graph_validate(old)
+
+
 def test_groups_that_disagree_on_what_the_kernel_shares_raise(vit):
     from vit_amd.optimizer import FusedAdamW, FusedSGD
 

@@ -16,9 +16,13 @@ pytestmark = pytest.mark.gpu
 MAX_NORM = 0.5
 BIG = 4096 * 256 * 4 + 1032  # past one full pass of the launch's grid (tests/test_optim_gpu.py: SIZES): the stride loop runs twice
 # name -> (n, segment ends, group of each segment).  One segment | two of 8 | a boundary inside a wave's 256-element row |
-# the n & 3 tail in the last segment | more segments than a wave has lanes | a second pass of the grid-stride loop
+# the n & 3 tail in the last segment | more segments than a wave has lanes | a second pass of the grid-stride loop.
+# One segment (a one-group optimizer: the kernel takes the row once and runs the plain loop): 8 | with the n & 3 tail | a
+# second pass of the loop
 LAYOUTS = {
     "n8": (8, [8], [0]),
+    "one1027": (1027, [1027], [0]),
+    "onebig": (BIG, [BIG], [0]),
     "n16": (16, [8, 16], [0, 1]),
     "n1032": (1032, [8, 264, 1032], [0, 1, 2]),
     "n1027": (1027, [8, 1024, 1027], [0, 1, 2]),
@@ -26,7 +30,7 @@ LAYOUTS = {
     "big": (BIG, [264, 1000 * 1024 + 8, 1000 * 1024 + 16, 4096 * 256 * 4 - 512, BIG], [0, 1, 2, 1, 0]),
 }
 # sub-runs [0, a), [a, b), [b, n): every cut a multiple of 4 (16-byte accesses) that lies INSIDE a segment
-CUTS = {"n16": (4, 12), "n1032": (100, 600), "n1027": (12, 1000), "300x8": (100, 1204), "big": (1000 * 1024 + 12, 4096 * 256 * 4 + 4)}
+CUTS = {"one1027": (12, 1000), "onebig": (1000 * 1024 + 12, 4096 * 256 * 4 + 4), "n16": (4, 12), "n1032": (100, 600), "n1027": (12, 1000), "300x8": (100, 1204), "big": (1000 * 1024 + 12, 4096 * 256 * 4 + 4)}
 # (lr, weight_decay, momentum) of groups 0..2; group 2 has no momentum: its part of the buffer must stay untouched
 HYPER = {"adamw": [(1e-3, 0.01, 0.0), (3e-4, 0.0, 0.0), (2e-3, 0.1, 0.0)],
          "adam_l2": [(1e-3, 0.01, 0.0), (3e-4, 0.0, 0.0), (2e-3, 0.1, 0.0)],
@@ -328,6 +332,70 @@ def test_groups_with_a_trainable_preprocessor_and_a_frozen_layer(dev, kind):
     moved = {n: not torch.equal(q.detach(), q0) for (n, q), q0 in zip(model.named_parameters(), start)}
     assert moved["preprocessor.linear.weight"] and moved["preprocessor.linear.bias"] and moved["regressor.weight"]
     assert not any(v for n, v in moved.items() if n.startswith("vit.encoder.layer.1."))
+
+
+@pytest.mark.parametrize("n_groups", [1, 2])
+@pytest.mark.parametrize("kind", ["adamw", "sgd"])
+def test_a_frozen_flat_buffer_beside_a_trainable_preprocessor(dev, kind, n_groups):
+    """No parameter of the flat buffer is stepped: the ViT is frozen and the optimizer is built over what still trains, the
+    preprocessor outside the flat buffer.  (The head keeps requires_grad, in no group: the model runs a backward only while some
+    parameter of the flat buffer wants a gradient.)  There is no run and no table to build -- the step takes the by-value kernel
+    on the preprocessor alone, three clipped steps against the torch twin at the model-level gate, and the flat buffer keeps its
+    bits."""
+    from oracle import refvit
+    from test_optim_gpu import _assert_same, _hand_over_grads
+    from vit_amd.config import ViTConfig
+    from vit_amd.optimizer import FusedAdamW, FusedSGD
+    from vit_amd.preprocessor import LinearPreprocessor
+    from vit_amd.specvit import MyViT
+
+    L_in, r = 96, 64
+    rc = refvit.RefConfig(image_size=r, patch_size=16, hidden_size=32, num_hidden_layers=3, num_attention_heads=2,
+                          stride_size=16, loss_name="mae")
+    sd = refvit.make_state_dict(rc, 71)
+    gen = torch.Generator().manual_seed(72)
+    P0, b0 = torch.randn(r, L_in, generator=gen) / L_in ** 0.5, torch.randn(r, generator=gen) * 0.1
+    x, labels = torch.randn(5, L_in, generator=gen).to(dev), torch.rand(5, generator=gen).to(dev)
+    cfg = ViTConfig(task_type="reg", image_size=r, patch_size=16, hidden_size=32, num_hidden_layers=3, num_attention_heads=2,
+                    stride_size=16)
+    model = MyViT(cfg, loss_name="mae", preprocessor=LinearPreprocessor(P0.clone(), bias=b0.clone(), freeze=False))
+    model.set_precision("32")
+    model.load_state_dict({**sd, "preprocessor.linear.weight": P0, "preprocessor.linear.bias": b0}, strict=True)
+    model = model.to(dev).eval()
+    for n, prm in model.named_parameters():
+        if n.startswith("vit."):
+            prm.requires_grad_(False)
+    named = dict(model.named_parameters())
+    w, b = named["preprocessor.linear.weight"], named["preprocessor.linear.bias"]
+    lr, wd = (1e-2, 0.05) if kind == "sgd" else (1e-3, 0.05)
+    groups = [{"params": [w, b]}] if n_groups == 1 else [{"params": [w]}, {"params": [b], "lr": lr * 0.5, "weight_decay": 0.0}]
+    twins = [torch.nn.Parameter(q.detach().clone()) for q in model.parameters()]
+    start = [q.detach().clone() for q in model.parameters()]
+    twin_of = {id(q): tw for q, tw in zip(model.parameters(), twins)}
+    ref_groups = [dict(g, params=[twin_of[id(q)] for q in g["params"]]) for g in groups]
+    kw = dict(lr=lr, weight_decay=wd, **({"momentum": 0.9} if kind == "sgd" else {}))
+    if kind == "sgd":
+        fused, ref = FusedSGD(model, param_groups=groups, **kw), torch.optim.SGD(ref_groups, **kw)
+    else:
+        fused, ref = FusedAdamW(model, param_groups=groups, **kw), torch.optim.AdamW(ref_groups, **kw)
+    assert len(fused.param_groups) == n_groups and len(fused._extras) == 2
+    with pytest.raises(ValueError, match="no parameter group owns"):
+        fused._partition()  # the state in question: a table cannot be built, and the step must not ask for one
+    fused.set_grad_clip(MAX_NORM)
+    flat0 = model.engine.flat.detach().clone()
+    for s in range(3):
+        fused.zero_grad()
+        model(x, labels=labels).loss.backward()
+        assert fused._active_ranges() == []
+        _hand_over_grads(model, twins)
+        norm = torch.nn.utils.clip_grad_norm_([twin_of[id(w)], twin_of[id(b)]], MAX_NORM)
+        fused.step()
+        ref.step()
+        got = float(fused.last_grad_norm.sqrt())
+        assert abs(got - float(norm)) <= 1e-6 * float(norm), (s, got, float(norm))
+        _assert_same(model, twins, start, s)
+    assert fused._step == 3 and torch.equal(model.engine.flat, flat0)
+    assert not torch.equal(w.detach(), start[list(named).index("preprocessor.linear.weight")])
 
 
 # -------------------------------------------------------------------------------------------------------------- trainer

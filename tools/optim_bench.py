@@ -16,11 +16,13 @@ The last worker (this tree only) times the bare kernels at n = 85.8 M against th
 
     python tools/optim_bench.py --groups [--parent DIR] [--rounds 3] [--out profiles/optim_groups_bench.json]
 
-The parameter-group study instead (vit_*_step_groups).  Kernel rows at n = 85.8 M, one fresh worker per round, all four in
-the same process: vit_adamw_step | the grouped kernel with one segment | with ViT-B's no-decay table | with ViT-L's
-layer-decay + no-decay table (its segments below n).  The yardstick is the plain kernel of the same session; the allowance
-is the spread that kernel shows across the session's rounds.  Step rows: C1 (eager and hip_graph) and C3 with AdamW,
-weight_decay 0.05, with and without `no_decay: true` + `layer_decay: 0.75` (`--parent`: its one-group step beside them)."""
+The parameter-group study instead (vit_*_step_groups).  Kernel rows at n = 85.8 M, one fresh worker per round, all of them
+interleaved in the same process: vit_adamw_step (by value) | the table kernel with one segment | with ViT-B's no-decay table |
+with ViT-L's layer-decay + no-decay table (its segments below n) | vit_sgd_step with momentum by value | with one segment.
+With `--parent` the same process also loads the parent's library and times its entry points of the same names on the same
+buffers (rows "parent: ..."): the yardstick is the parent's by-value kernel, the allowance is the spread that row shows
+across the session's rounds.  Step rows: C1 (eager and hip_graph) and C3 with AdamW, weight_decay 0.05, with and without
+`no_decay: true` + `layer_decay: 0.75` (`--parent`: its steps beside them)."""
 from __future__ import annotations
 
 import argparse
@@ -132,7 +134,25 @@ def _model_table(hidden, layers, heads, dev, layer_decay):
     return t
 
 
-def _group_kernels(dev):
+def _parent_calls(lib_path):
+    """The parent library's optimizer entry points under this tree's prototypes (their signatures are the ABI both share),
+    called without a handle: they need neither a workspace nor a bound record."""
+    import ctypes as C
+
+    from vit_amd import _cabi
+
+    lib = C.CDLL(lib_path)
+    for name in ("vit_adamw_step", "vit_adamw_step_groups", "vit_sgd_step", "vit_sgd_step_groups"):
+        fn = getattr(lib, name)
+        fn.argtypes, fn.restype = _cabi._PROTOS[name], C.c_int
+
+    def call(name, *args):
+        if getattr(lib, name)(None, *args) != 0:
+            raise SystemExit(f"parent {name} failed")
+    return call
+
+
+def _group_kernels(dev, parent_lib=""):
     import torch
     import vit_amd.functional as vf
 
@@ -145,25 +165,43 @@ def _group_kernels(dev):
     clip = dict(sqnorm=sq, max_norm=0.5)
     one = vf.optim_group_tables([(0, n, 0)], 1, dev, total=n)
     vf.optim_groups_write(one, [(1e-3, 0.01, 0.0)])
-    tables = {"grouped, 1 segment": one, "grouped, ViT-B no_decay": _model_table(768, 12, 12, dev, False),
-              "grouped, ViT-L layer_decay + no_decay": _model_table(1024, 24, 16, dev, True)}
-    calls = {"adamw (plain)": (None, lambda: vf.adamw_step(p, g, a, b, pb, lr=1e-3, weight_decay=0.01, step=3, **clip))}
+    one_sgd = vf.optim_group_tables([(0, n, 0)], 1, dev, total=n)
+    vf.optim_groups_write(one_sgd, [(1e-2, 0.01, 0.9)])
+    tables = {"1 segment": one, "ViT-B no_decay": _model_table(768, 12, 12, dev, False),
+              "ViT-L layer_decay + no_decay": _model_table(1024, 24, 16, dev, True)}
+    # name -> (bytes per parameter, table or None, call)
+    calls = {"adamw (by value)": (30, None, lambda: vf.adamw_step(p, g, a, b, pb, lr=1e-3, weight_decay=0.01, step=3, **clip))}
     for name, t in tables.items():
-        calls[name] = (t, lambda t=t: vf.adamw_step_groups(p, g, a, b, pb, t, step=3, **clip))
+        calls["adamw table, " + name] = (30, t, lambda t=t: vf.adamw_step_groups(p, g, a, b, pb, t, step=3, **clip))
+    calls["sgd momentum (by value)"] = (22, None, lambda: vf.sgd_step(p, g, a, pb, lr=1e-2, momentum=0.9, weight_decay=0.01, **clip))
+    calls["sgd momentum table, 1 segment"] = (22, one_sgd, lambda: vf.sgd_step_groups(p, g, a, pb, one_sgd, **clip))
+    if parent_lib:
+        call = _parent_calls(parent_lib)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        ptrs = (p.data_ptr(), g.data_ptr(), a.data_ptr(), b.data_ptr(), pb.data_ptr(), n)
+        sgd_ptrs = (p.data_ptr(), g.data_ptr(), a.data_ptr(), pb.data_ptr(), n)
+        tail = (sq.data_ptr(), 0.5, stream)
+        calls["parent: adamw (by value)"] = (30, None, lambda: call("vit_adamw_step", *ptrs, 1e-3, 0.9, 0.999, 1e-8, 0.01, 3, *tail))
+        for name, t in tables.items():
+            calls["parent: adamw table, " + name] = (30, t, lambda t=t: call(
+                "vit_adamw_step_groups", *ptrs, *vf._groups_args(t, 0), 0.9, 0.999, 1e-8, 3, *tail))
+        calls["parent: sgd momentum (by value)"] = (22, None, lambda: call("vit_sgd_step", *sgd_ptrs, 1e-2, 0.9, 0.01, 0, *tail))
+        calls["parent: sgd momentum table, 1 segment"] = (22, one_sgd, lambda: call(
+            "vit_sgd_step_groups", *sgd_ptrs, *vf._groups_args(one_sgd, 0), 0, *tail))
     out, ts = [], {name: [] for name in calls}
-    for f in (f for _, f in calls.values()):
+    for _, _, f in calls.values():
         f(); f()
     torch.cuda.synchronize()
     for _ in range(7):  # interleaved: every kernel sees the same minutes
-        for name, (_, f) in calls.items():
+        for name, (_, _, f) in calls.items():
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record(); f(); f(); f(); e1.record()
             torch.cuda.synchronize()
             ts[name].append(e0.elapsed_time(e1) / 3 * 1e3)
-    for name, (t, _) in calls.items():
+    for name, (nbytes, t, _) in calls.items():
         us = statistics.median(ts[name])
-        row = {"kernel": name, "n": n, "us": round(us, 1), "us_min": round(min(ts[name]), 1), "us_max": round(max(ts[name]), 1),
-               "gb_per_s": round(n * 30 / us / 1e3, 1)}
+        row = {"kernel": name, "n": n, "bytes_per_param": nbytes, "us": round(us, 1), "us_min": round(min(ts[name]), 1),
+               "us_max": round(max(ts[name]), 1), "gb_per_s": round(n * nbytes / us / 1e3, 1)}
         if t is not None:
             row.update(n_groups=t.n_groups, n_segments=t.n_segments, segments_below_n=int((t.seg_end <= n).sum()) + 1)
         out.append(row)
@@ -182,11 +220,10 @@ def worker(args):
     if args.worker == "kernels":
         res = _kernels(dev)
     elif args.worker == "group_kernels":
-        res = _group_kernels(dev)
-    elif args.worker in ("group_train", "group_train_parent"):  # the parent knows no groups: its one-group step only
-        opts = {k: v for k, v in GROUP_OPTS.items() if args.worker == "group_train" or k == "adamw"}
-        res = [_train_case(name, batch, graph, opt, args.steps, args.warmup, dev, opts)
-               for name, batch, graph in CASES for opt in opts]
+        res = _group_kernels(dev, args.parent_lib)
+    elif args.worker == "group_train":
+        res = [_train_case(name, batch, graph, opt, args.steps, args.warmup, dev, GROUP_OPTS)
+               for name, batch, graph in CASES for opt in GROUP_OPTS]
     else:
         res = [_train_case(name, batch, graph, opt, args.steps, args.warmup, dev)
                for name, batch, graph in CASES for opt in OPTS]
@@ -196,6 +233,8 @@ def worker(args):
 def _spawn(root, what, args):
     cmd = [sys.executable, os.path.abspath(__file__), "--worker", what, "--root", root, "--steps", str(args.steps),
            "--warmup", str(args.warmup)]
+    if what == "group_kernels" and args.parent:
+        cmd += ["--parent-lib", os.path.join(os.path.abspath(args.parent), "vit_amd", "lib", "libvit_amd.so")]
     env = {k: v for k, v in os.environ.items() if k != "VIT_AMD_LIB"}
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=args.worker_timeout)
     if r.returncode != 0:
@@ -213,14 +252,14 @@ def groups_main(args):
         kernel_rounds.append(_spawn(HERE, "group_kernels", args))
         print(f"[round {rnd}] kernels: " + " ".join(f"{k['us']:.1f}" for k in kernel_rounds[-1]), flush=True)
         if args.parent:
-            train["parent"].append(_spawn(os.path.abspath(args.parent), "group_train_parent", args))
+            train["parent"].append(_spawn(os.path.abspath(args.parent), "group_train", args))
         train["this"].append(_spawn(HERE, "group_train", args))
     kernels = []
     for i, first in enumerate(kernel_rounds[0]):
         us = [r[i]["us"] for r in kernel_rounds]
         row = dict(first, us=round(statistics.median(us), 1), us_rounds=us, us_min=min(r[i]["us_min"] for r in kernel_rounds),
                    us_max=max(r[i]["us_max"] for r in kernel_rounds))
-        row["gb_per_s"] = round(row["n"] * 30 / row["us"] / 1e3, 1)
+        row["gb_per_s"] = round(row["n"] * row["bytes_per_param"] / row["us"] / 1e3, 1)
         kernels.append(row)
         print(f"{row['kernel']:40s} {row['us']:8.1f} us, rounds {us}, samples [{row['us_min']:.1f} .. {row['us_max']:.1f}] = "
               f"{row['gb_per_s']:.0f} GB/s", flush=True)
@@ -251,7 +290,8 @@ def main():
     ap.add_argument("--worker-timeout", type=int, default=240)
     ap.add_argument("--out", default="")
     ap.add_argument("--groups", action="store_true", help="the parameter-group study instead")
-    ap.add_argument("--worker", default="", choices=["", "train", "kernels", "group_kernels", "group_train", "group_train_parent"])
+    ap.add_argument("--worker", default="", choices=["", "train", "kernels", "group_kernels", "group_train"])
+    ap.add_argument("--parent-lib", default="", help=argparse.SUPPRESS)
     ap.add_argument("--root", default=HERE)
     args = ap.parse_args()
     if args.worker:

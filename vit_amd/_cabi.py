@@ -62,7 +62,6 @@ _PROTOS = {
     "vit_handle_set_option": [_P, C.c_char_p, _I],
     "vit_step_state_bind": [_P, _P],
     "vit_step_advance": [_P, _U64, _F, _F, _P],
-    "vit_adamw_step_dyn": [_P, _P, _P, _P, _P, _P, _I64, _F, _F, _F, _F, _P, _F, _P],
     "vit_gemm": [_P, C.POINTER(GemmDesc), _P],
     "vit_last_gemm_kernel": [],
     "vit_linear_fwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _F, _U64, _U64, _P, _P],
@@ -98,9 +97,7 @@ _PROTOS = {
     "vit_grad_sqnorm_acc": [_P, _P, _I64, _P, _P],
     "vit_adamw_step": [_P, _P, _P, _P, _P, _P, _I64, _F, _F, _F, _F, _F, _I, _P, _F, _P],
     "vit_sgd_step": [_P, _P, _P, _P, _P, _I64, _F, _F, _F, _I, _P, _F, _P],
-    "vit_sgd_step_dyn": [_P, _P, _P, _P, _P, _I64, _F, _I, _P, _F, _P],
     "vit_adam_l2_step": [_P, _P, _P, _P, _P, _P, _I64, _F, _F, _F, _F, _F, _I, _P, _F, _P],
-    "vit_adam_l2_step_dyn": [_P, _P, _P, _P, _P, _P, _I64, _F, _F, _F, _F, _P, _F, _P],
     # (h, p, g, m, v, p_bf16, n, base, seg_end, seg_group, n_segments, groups, n_groups, beta1, beta2, eps, [step,] sqnorm, ...)
     "vit_adamw_step_groups": [_P, _P, _P, _P, _P, _P, _I64, _I64, _P, _P, _I, _P, _I, _F, _F, _F, _I, _P, _F, _P],
     "vit_adamw_step_groups_dyn": [_P, _P, _P, _P, _P, _P, _I64, _I64, _P, _P, _I, _P, _I, _F, _F, _F, _P, _F, _P],

@@ -288,8 +288,8 @@ __device__ __forceinline__ void lds_dma4_s(const void* sbase /* wave-uniform */,
   asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %0, %1" ::"v"(voff), "s"(sbase), "s"(a) : "memory", "m0");
 }
 
-// the handle's bound per-step state (api.hip): [key0, key1, lr, bc1, rsqrt_bc2, step, momentum, pad] in device memory, or NULL
-struct StepState { unsigned key0, key1; float lr, bc1, rsqrt_bc2; unsigned step; float momentum; unsigned pad; };
+// the handle's bound per-step state (api.hip): [key0, key1, -, bc1, rsqrt_bc2, step, -, -] in device memory, or NULL
+struct StepState { unsigned key0, key1, reserved2; float bc1, rsqrt_bc2; unsigned step, reserved6, pad; };
 const StepState* ctx_step_state(vit_handle h);
 int ctx_num_cus(vit_handle h);  // compute units of the handle's device (api.hip)
 // vit_handle_set_option("grad_accumulate"): non-zero = every parameter-gradient output of a call through this handle stores

@@ -727,7 +727,7 @@ int vit_grad_sqnorm_acc(vit_handle h, const float* g, int64_t n, float* out, vit
 }
 
 // ---- per-step state in device memory (hipGraph replays): one thread advances the step counter and derives from it the
-// dropout keys of the step and Adam's bias corrections; lr and momentum are whatever the host last wrote into the state
+// dropout keys of the step and Adam's bias corrections (learning rates and momenta live in the optimizer's group table)
 __global__ void step_advance_kernel(StepState* s, unsigned long long base_seed, float b1, float b2) {
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     const unsigned step = s->step + 1;

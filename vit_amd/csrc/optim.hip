@@ -1,16 +1,29 @@
 // Optimizer steps over a flat f32 parameter buffer for gfx950: AdamW, Adam with L2 decay, SGD (momentum / Nesterov).
 // One pass each: the global-norm clip coefficient is applied to g on the fly, the bf16 shadow of p is written beside p.
 // HBM-bound (14 / 22 / 30 B per parameter), 16 B per lane, grid-stride, scalar tail for n & 3, no atomics: deterministic.
-// The `_dyn` forms (a step captured as a hipGraph) read what changes between replays from the handle's bound StepState.
-// The `_groups` forms take lr / weight_decay / momentum per element from a segment table and a group table in device memory
-// (torch.optim's param_groups in one launch); the update itself is stated once, below, for both.
+// One kernel per family.  The `_groups` forms take lr / weight_decay / momentum per element from a segment table and a group
+// table in device memory (torch.optim's param_groups in one launch); the by-value forms are that kernel without a table, their
+// scalars as its one row.  The `_groups_dyn` forms (a step captured as a hipGraph) read the bias corrections from the handle's
+// bound StepState; what a scheduler changes between replays lives in the group table.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
 #include "common.h"
 
+// Every multiply-add that is fused is written as one (fma_): left to the compiler's contraction, the same source rounded
+// differently in different kernels (fused in one loop, a packed multiply and a separate add in another), and the contract
+// "bit-identical on any segment, through any entry point" held only by luck.
+#pragma clang fp contract(off)
+
 namespace vit {
+
+__device__ __forceinline__ float fma_(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+__device__ __forceinline__ f32x4 fma_(f32x4 a, float b, f32x4 c) {
+#pragma unroll
+  for (int k = 0; k < 4; ++k) c[k] = __builtin_fmaf(a[k], b, c[k]);
+  return c;
+}
 
 __device__ __forceinline__ float clip_coef(const float* __restrict__ sqnorm, float max_norm) {
   return sqnorm ? fminf(1.f, max_norm / (sqrtf(sqnorm[0]) + 1e-6f)) : 1.f;
@@ -25,11 +38,11 @@ __device__ __forceinline__ void store_shadow(short* __restrict__ pb, long at, fl
 
 __device__ __forceinline__ f32x4 adam_descend(f32x4 pp, f32x4 mm, f32x4 vv, float decay, float step, float rsqrt_bc2, float eps) {
 #pragma unroll
-  for (int k = 0; k < 4; ++k) pp[k] = pp[k] * decay - step * mm[k] / (sqrtf(vv[k]) * rsqrt_bc2 + eps);
+  for (int k = 0; k < 4; ++k) pp[k] = fma_(pp[k], decay, -(step * mm[k] / fma_(sqrtf(vv[k]), rsqrt_bc2, eps)));
   return pp;
 }
 __device__ __forceinline__ float adam_descend(float pp, float mm, float vv, float decay, float step, float rsqrt_bc2, float eps) {
-  return pp * decay - step * mm / (sqrtf(vv) * rsqrt_bc2 + eps);
+  return fma_(pp, decay, -(step * mm / fma_(sqrtf(vv), rsqrt_bc2, eps)));
 }
 
 // what Adam shares across a call (and across groups): the EMA weights, eps, the second bias correction
@@ -45,11 +58,11 @@ __device__ __forceinline__ void adam_update(float* __restrict__ p, const float* 
                                             const AdamShared a, float step, float decay, float wd) {
   T pp = *(const T*)(p + at);
   T gg = *(const T*)(g + at) * clip;
-  if (L2) gg = gg + pp * wd;
+  if (L2) gg = fma_(pp, wd, gg);
   T mm = *(const T*)(m + at);
   T vv = *(const T*)(v + at);
-  mm = mm * a.b1 + gg * a.omb1;
-  vv = vv * a.b2 + gg * gg * a.omb2;
+  mm = fma_(mm, a.b1, gg * a.omb1);
+  vv = fma_(vv, a.b2, gg * gg * a.omb2);
   pp = adam_descend(pp, mm, vv, decay, step, a.rsqrt_bc2, a.eps);
   *(T*)(p + at) = pp;
   *(T*)(m + at) = mm;
@@ -65,51 +78,15 @@ __device__ __forceinline__ void sgd_update(float* __restrict__ p, const float* _
                                            int nesterov) {
   T pp = *(const T*)(p + at);
   T d = *(const T*)(g + at) * clip;
-  if (wd != 0.f) d = d + pp * wd;
+  if (wd != 0.f) d = fma_(pp, wd, d);
   if (MOM) {
-    const T bb = *(const T*)(buf + at) * mu + d;
+    const T bb = fma_(*(const T*)(buf + at), mu, d);
     *(T*)(buf + at) = bb;
-    d = nesterov ? d + bb * mu : bb;
+    d = nesterov ? fma_(bb, mu, d) : bb;
   }
-  pp = pp - d * lr;
+  pp = fma_(d, -lr, pp);
   *(T*)(p + at) = pp;
   if (pb) store_shadow(pb, at, pp);
-}
-
-// DYN: lr, bc1, rsqrt_bc2 come from the step record instead of the arguments.
-template <bool L2, bool DYN>
-__global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                    float* __restrict__ m, float* __restrict__ v,
-                                                    short* __restrict__ pb, long n, float lr, float b1, float b2,
-                                                    float omb1, float omb2, float eps, float wd, float bc1,
-                                                    float rsqrt_bc2, const StepState* __restrict__ st,
-                                                    const float* __restrict__ sqnorm, float max_norm) {
-  const float clip = clip_coef(sqnorm, max_norm);
-  if (DYN) {
-    lr = st->lr; bc1 = st->bc1; rsqrt_bc2 = st->rsqrt_bc2;
-  }
-  const float step = lr / bc1, decay = L2 ? 1.f : 1.f - lr * wd;
-  const AdamShared a = {b1, b2, omb1, omb2, eps, rsqrt_bc2};
-  const long nv = n >> 2;
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < nv; i += (long)gridDim.x * blockDim.x)
-    adam_update<L2, f32x4>(p, g, m, v, pb, 4 * i, clip, a, step, decay, wd);
-  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) adam_update<L2, float>(p, g, m, v, pb, (nv << 2) + threadIdx.x, clip, a, step, decay, wd);
-}
-
-// DYN: lr and mu come from the step record.
-template <bool MOM, bool DYN>
-__global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
-                                                  short* __restrict__ pb, long n, float lr, float mu, float wd, int nesterov,
-                                                  const StepState* __restrict__ st, const float* __restrict__ sqnorm,
-                                                  float max_norm) {
-  const float clip = clip_coef(sqnorm, max_norm);
-  if (DYN) {
-    lr = st->lr; mu = st->momentum;
-  }
-  const long nv = n >> 2;
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < nv; i += (long)gridDim.x * blockDim.x)
-    sgd_update<MOM, f32x4>(p, g, buf, pb, 4 * i, clip, lr, mu, wd, nesterov);
-  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) sgd_update<MOM, float>(p, g, buf, pb, (nv << 2) + threadIdx.x, clip, lr, mu, wd, nesterov);
 }
 
 // ---- parameter groups ------------------------------------------------------------------------------------------------------
@@ -122,6 +99,9 @@ __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const f
 // a boundary lets each lane walk on from the tile's first segment.  Offsets past the last end and group indices past the
 // table are clamped, so a malformed table cannot make the kernel read outside it.
 struct alignas(16) GroupRow { float lr, wd, mu, pad; };
+// Lanes per block of the step kernels, a compile-time number: read from blockDim the tile arithmetic below starts every wave
+// with a vector load of the dispatch packet, a round trip behind the streaming loads of the waves already running.
+constexpr int STEP_BLOCK = 256;
 
 __device__ __forceinline__ int seg_find(const long* __restrict__ seg_end, int n_seg, long off) {
   int lo = 0, hi = n_seg - 1;  // the first s with seg_end[s] > off, or the last segment
@@ -137,67 +117,74 @@ __device__ __forceinline__ GroupRow seg_row(const int* __restrict__ seg_group, c
   return rows[gi < (unsigned)n_groups ? gi : (unsigned)n_groups - 1u];
 }
 
-// calls body(at, row) for every 16-byte vector of [0, 4 * (n >> 2)) and tail(at, row) for the n & 3 elements behind them
-template <typename Body, typename Tail>
+// calls body(at, prep(row)) for every 16-byte vector of [0, 4 * (n >> 2)) and tail(at, prep(row)) for the n & 3 elements behind
+// them.  n_seg <= 1 is kernel-uniform: the row -- `row` itself without a table (n_seg == 0: the by-value entry points), the one
+// segment's otherwise -- is taken and prepared once, and the body runs in the plain grid-stride loop.
+template <typename Prep, typename Body, typename Tail>
 __device__ __forceinline__ void for_each_grouped(long n, long base, const long* __restrict__ seg_end,
                                                  const int* __restrict__ seg_group, int n_seg,
-                                                 const GroupRow* __restrict__ rows, int n_groups, Body body, Tail tail) {
+                                                 const GroupRow* __restrict__ rows, int n_groups, GroupRow row, Prep prep,
+                                                 Body body, Tail tail) {
   const long nv = n >> 2;
-  for (long v0 = blockIdx.x * (long)blockDim.x; v0 < nv; v0 += (long)gridDim.x * blockDim.x) {  // block-uniform
-    const long v1 = v0 + blockDim.x < nv ? v0 + blockDim.x : nv;
+  if (n_seg <= 1) {
+    if (n_seg == 1) row = seg_row(seg_group, rows, n_groups, 0);
+    const auto k = prep(row);
+    for (long i = blockIdx.x * (long)STEP_BLOCK + threadIdx.x; i < nv; i += (long)gridDim.x * STEP_BLOCK) body(4 * i, k);
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) tail((nv << 2) + threadIdx.x, k);
+    return;
+  }
+  for (long v0 = blockIdx.x * (long)STEP_BLOCK; v0 < nv; v0 += (long)gridDim.x * STEP_BLOCK) {  // block-uniform
+    const long v1 = v0 + STEP_BLOCK < nv ? v0 + STEP_BLOCK : nv;
     const int s0 = seg_find(seg_end, n_seg, base + 4 * v0);
     const long i = v0 + threadIdx.x;
     if (s0 == n_seg - 1 || seg_end[s0] >= base + 4 * v1) {  // the whole tile lies in segment s0
       const GroupRow r = seg_row(seg_group, rows, n_groups, s0);
-      if (i < v1) body(4 * i, r);
+      if (i < v1) body(4 * i, prep(r));
     } else if (i < v1) {
       int s = s0;
       while (s < n_seg - 1 && seg_end[s] <= base + 4 * i) ++s;
-      body(4 * i, seg_row(seg_group, rows, n_groups, s));
+      body(4 * i, prep(seg_row(seg_group, rows, n_groups, s)));
     }
   }
   if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
     const long i = (nv << 2) + threadIdx.x;
-    tail(i, seg_row(seg_group, rows, n_groups, seg_find(seg_end, n_seg, base + i)));
+    tail(i, prep(seg_row(seg_group, rows, n_groups, seg_find(seg_end, n_seg, base + i))));
   }
 }
 
-// DYN: bc1 and rsqrt_bc2 come from the step record; the learning rates are the table's in both forms.
-template <bool L2, bool DYN>
-__global__ __launch_bounds__(256) void adamw_groups_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                           float* __restrict__ m, float* __restrict__ v,
-                                                           short* __restrict__ pb, long n, long base,
-                                                           const long* __restrict__ seg_end, const int* __restrict__ seg_group,
-                                                           int n_seg, const GroupRow* __restrict__ rows, int n_groups, float b1,
-                                                           float b2, float omb1, float omb2, float eps, float bc1,
-                                                           float rsqrt_bc2, const StepState* __restrict__ st,
-                                                           const float* __restrict__ sqnorm, float max_norm) {
+// One kernel per family.  `st` (a captured step) supplies the bias corrections and nothing else; learning rates, weight decays
+// and momenta are the row's: the by-value `row` (n_seg == 0) or the group table's.
+struct AdamRow { float step, decay, wd; };  // step = lr / bc1, decay = L2 ? 1 : 1 - lr * wd
+template <bool L2>
+__global__ __launch_bounds__(STEP_BLOCK) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                   float* __restrict__ v, short* __restrict__ pb, long n, long base,
+                                                   const long* __restrict__ seg_end, const int* __restrict__ seg_group,
+                                                   int n_seg, const GroupRow* __restrict__ rows, int n_groups, GroupRow row,
+                                                   float b1, float b2, float omb1, float omb2, float eps, float bc1,
+                                                   float rsqrt_bc2, const StepState* __restrict__ st,
+                                                   const float* __restrict__ sqnorm, float max_norm) {
   const float clip = clip_coef(sqnorm, max_norm);
-  if (DYN) {
+  if (st) {
     bc1 = st->bc1; rsqrt_bc2 = st->rsqrt_bc2;
   }
   const AdamShared a = {b1, b2, omb1, omb2, eps, rsqrt_bc2};
   for_each_grouped(
-      n, base, seg_end, seg_group, n_seg, rows, n_groups,
-      [&](long at, GroupRow r) {
-        adam_update<L2, f32x4>(p, g, m, v, pb, at, clip, a, r.lr / bc1, L2 ? 1.f : 1.f - r.lr * r.wd, r.wd);
-      },
-      [&](long at, GroupRow r) {
-        adam_update<L2, float>(p, g, m, v, pb, at, clip, a, r.lr / bc1, L2 ? 1.f : 1.f - r.lr * r.wd, r.wd);
-      });
+      n, base, seg_end, seg_group, n_seg, rows, n_groups, row,
+      [&](GroupRow r) { return AdamRow{r.lr / bc1, L2 ? 1.f : fma_(-r.lr, r.wd, 1.f), r.wd}; },
+      [&](long at, AdamRow k) { adam_update<L2, f32x4>(p, g, m, v, pb, at, clip, a, k.step, k.decay, k.wd); },
+      [&](long at, AdamRow k) { adam_update<L2, float>(p, g, m, v, pb, at, clip, a, k.step, k.decay, k.wd); });
 }
 
-// MOM: there is a momentum buffer; a group whose momentum is 0 still neither reads nor writes its part of it (vit_sgd_step
-// with momentum 0 on that slice).
+// MOM: there is a momentum buffer; a row whose momentum is 0 still neither reads nor writes its part of it.
 template <bool MOM>
-__global__ __launch_bounds__(256) void sgd_groups_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                         float* __restrict__ buf, short* __restrict__ pb, long n, long base,
-                                                         const long* __restrict__ seg_end, const int* __restrict__ seg_group,
-                                                         int n_seg, const GroupRow* __restrict__ rows, int n_groups,
-                                                         int nesterov, const float* __restrict__ sqnorm, float max_norm) {
+__global__ __launch_bounds__(STEP_BLOCK) void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
+                                                  short* __restrict__ pb, long n, long base, const long* __restrict__ seg_end,
+                                                  const int* __restrict__ seg_group, int n_seg,
+                                                  const GroupRow* __restrict__ rows, int n_groups, GroupRow row, int nesterov,
+                                                  const float* __restrict__ sqnorm, float max_norm) {
   const float clip = clip_coef(sqnorm, max_norm);
   for_each_grouped(
-      n, base, seg_end, seg_group, n_seg, rows, n_groups,
+      n, base, seg_end, seg_group, n_seg, rows, n_groups, row, [](GroupRow r) { return r; },
       [&](long at, GroupRow r) {
         if (MOM && r.mu != 0.f) sgd_update<true, f32x4>(p, g, buf, pb, at, clip, r.lr, r.mu, r.wd, nesterov);
         else sgd_update<false, f32x4>(p, g, buf, pb, at, clip, r.lr, r.mu, r.wd, 0);
@@ -235,106 +222,70 @@ static float one_minus(float beta) {
   return (float)(1.0 - (double)beta);
 }
 
+// a grouped call's tables as its entry point received them; the by-value entry points pass none, and their scalars as `row`
+struct GroupTable {
+  int64_t base;
+  const int64_t* seg_end;
+  const int32_t* seg_group;
+  int n_segments;
+  const float* groups;
+  int n_groups;
+};
+
+// what every grouped entry point checks of its tables' description (their contents live on the device: the caller's job)
+static int groups_check(const char* who, int64_t n, const GroupTable& t) {
+  VIT_CHECK(n > 0, VIT_ERR_ARG, "%s: n = %lld must be positive", who, (long long)n);
+  VIT_CHECK(t.seg_end && t.seg_group && t.groups, VIT_ERR_ARG, "%s: null table (seg_end, seg_group, groups)", who);
+  VIT_CHECK(t.n_segments > 0 && t.n_groups > 0, VIT_ERR_ARG, "%s: n_segments = %d and n_groups = %d must be positive", who,
+            t.n_segments, t.n_groups);
+  VIT_CHECK(t.base >= 0 && t.base % 4 == 0, VIT_ERR_ARG, "%s: base = %lld must be a non-negative multiple of 4", who,
+            (long long)t.base);
+  return VIT_OK;
+}
+
 template <bool L2>
 static int adam_launch(const char* who, vit_handle h, bool dyn, float* p, const float* g, float* m, float* v, void* p_bf16,
-                       int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
+                       int64_t n, const GroupTable* table, GroupRow row, float beta1, float beta2, float eps, int step,
                        const float* sqnorm, float max_norm, vit_stream stream) {
   const StepState* st = dyn ? ctx_step_state(h) : nullptr;
   VIT_CHECK(!dyn || st, VIT_ERR_ARG, "%s: no step state bound (vit_step_state_bind)", who);
-  VIT_CHECK(p && g && m && v && n > 0 && (dyn || step >= 1), VIT_ERR_ARG, "%s: bad arguments", who);
-  const dim3 grid(grid_for(n / 4 + 1)), block(256);
+  VIT_CHECK(p && g && m && v && (table || n > 0) && (dyn || step >= 1), VIT_ERR_ARG, "%s: bad arguments", who);
+  if (table)
+    if (int rc = groups_check(who, n, *table)) return rc;
+  const GroupTable t = table ? *table : GroupTable{};
   const float omb1 = one_minus<L2>(beta1), omb2 = one_minus<L2>(beta2);
-  if (dyn) {
-    hipLaunchKernelGGL((adamw_kernel<L2, true>), grid, block, 0, (hipStream_t)stream, p, g, m, v, (short*)p_bf16, (long)n, 0.f,
-                       beta1, beta2, omb1, omb2, eps, weight_decay, 1.f, 1.f, st, sqnorm, max_norm);
-  } else {
-    const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
-    hipLaunchKernelGGL((adamw_kernel<L2, false>), grid, block, 0, (hipStream_t)stream, p, g, m, v, (short*)p_bf16, (long)n, lr,
-                       beta1, beta2, omb1, omb2, eps, weight_decay, (float)bc1, (float)(1.0 / sqrt(bc2)), st, sqnorm, max_norm);
-  }
+  const double bc1 = dyn ? 1.0 : 1.0 - pow((double)beta1, step), bc2 = dyn ? 1.0 : 1.0 - pow((double)beta2, step);
+  hipLaunchKernelGGL((adam_kernel<L2>), dim3(grid_for(n / 4 + 1)), dim3(STEP_BLOCK), 0, (hipStream_t)stream, p, g, m, v,
+                     (short*)p_bf16, (long)n, (long)t.base, (const long*)t.seg_end, (const int*)t.seg_group, t.n_segments,
+                     (const GroupRow*)t.groups, t.n_groups, row, beta1, beta2, omb1, omb2, eps, (float)bc1,
+                     (float)(1.0 / sqrt(bc2)), st, sqnorm, max_norm);
   VIT_LAUNCH_CHECK();
   return VIT_OK;
 }
 
 static int sgd_launch(const char* who, vit_handle h, bool dyn, float* p, const float* g, float* buf, void* p_bf16, int64_t n,
-                      float lr, float momentum, float weight_decay, int nesterov, const float* sqnorm, float max_norm,
+                      const GroupTable* table, GroupRow row, int nesterov, const float* sqnorm, float max_norm,
                       vit_stream stream) {
-  const StepState* st = dyn ? ctx_step_state(h) : nullptr;
-  VIT_CHECK(!dyn || st, VIT_ERR_ARG, "%s: no step state bound (vit_step_state_bind)", who);
-  VIT_CHECK(p && g, VIT_ERR_ARG, "%s: null pointer (p, g)", who);
-  VIT_CHECK(n > 0, VIT_ERR_ARG, "%s: n = %lld must be positive", who, (long long)n);
-  if (!dyn) {
-    VIT_CHECK(momentum >= 0.f, VIT_ERR_ARG, "%s: momentum = %g is negative", who, (double)momentum);
-    VIT_CHECK(momentum == 0.f || buf, VIT_ERR_ARG, "%s: momentum = %g needs a momentum buffer (buf is NULL)", who,
-              (double)momentum);
-    if (momentum == 0.f) buf = nullptr;  // torch.optim.SGD keeps no buffer then: neither read nor written
-  }
-  VIT_CHECK(!nesterov || buf, VIT_ERR_ARG, "%s: nesterov needs a momentum and its buffer", who);
-  const dim3 grid(grid_for(n / 4 + 1)), block(256);
-  hipStream_t s = (hipStream_t)stream;
-  short* pb = (short*)p_bf16;
-#define VIT_SGD(MOM, DYN)                                                                                              \
-  hipLaunchKernelGGL((sgd_kernel<MOM, DYN>), grid, block, 0, s, p, g, buf, pb, (long)n, lr, momentum, weight_decay, nesterov, \
-                     st, sqnorm, max_norm)
-  if (buf) {
-    if (dyn) VIT_SGD(true, true); else VIT_SGD(true, false);
-  } else {
-    if (dyn) VIT_SGD(false, true); else VIT_SGD(false, false);
-  }
-#undef VIT_SGD
-  VIT_LAUNCH_CHECK();
-  return VIT_OK;
-}
-
-// what every grouped entry point checks of its tables' description (their contents live on the device: the caller's job)
-static int groups_check(const char* who, int64_t n, int64_t base, const int64_t* seg_end, const int32_t* seg_group,
-                        int n_segments, const float* groups, int n_groups) {
-  VIT_CHECK(n > 0, VIT_ERR_ARG, "%s: n = %lld must be positive", who, (long long)n);
-  VIT_CHECK(seg_end && seg_group && groups, VIT_ERR_ARG, "%s: null table (seg_end, seg_group, groups)", who);
-  VIT_CHECK(n_segments > 0 && n_groups > 0, VIT_ERR_ARG, "%s: n_segments = %d and n_groups = %d must be positive", who,
-            n_segments, n_groups);
-  VIT_CHECK(base >= 0 && base % 4 == 0, VIT_ERR_ARG, "%s: base = %lld must be a non-negative multiple of 4", who,
-            (long long)base);
-  return VIT_OK;
-}
-
-template <bool L2>
-static int adam_groups_launch(const char* who, vit_handle h, bool dyn, float* p, const float* g, float* m, float* v,
-                              void* p_bf16, int64_t n, int64_t base, const int64_t* seg_end, const int32_t* seg_group,
-                              int n_segments, const float* groups, int n_groups, float beta1, float beta2, float eps, int step,
-                              const float* sqnorm, float max_norm, vit_stream stream) {
-  const StepState* st = dyn ? ctx_step_state(h) : nullptr;
-  VIT_CHECK(!dyn || st, VIT_ERR_ARG, "%s: no step state bound (vit_step_state_bind)", who);
-  VIT_CHECK(p && g && m && v && (dyn || step >= 1), VIT_ERR_ARG, "%s: bad arguments", who);
-  if (int rc = groups_check(who, n, base, seg_end, seg_group, n_segments, groups, n_groups)) return rc;
-  const dim3 grid(grid_for(n / 4 + 1)), block(256);
-  const float omb1 = one_minus<L2>(beta1), omb2 = one_minus<L2>(beta2);
-  const double bc1 = dyn ? 1.0 : 1.0 - pow((double)beta1, step), bc2 = dyn ? 1.0 : 1.0 - pow((double)beta2, step);
-#define VIT_ADAM_GROUPS(DYN)                                                                                                  \
-  hipLaunchKernelGGL((adamw_groups_kernel<L2, DYN>), grid, block, 0, (hipStream_t)stream, p, g, m, v, (short*)p_bf16, (long)n, \
-                     (long)base, (const long*)seg_end, (const int*)seg_group, n_segments, (const GroupRow*)groups, n_groups,   \
-                     beta1, beta2, omb1, omb2, eps, (float)bc1, (float)(1.0 / sqrt(bc2)), st, sqnorm, max_norm)
-  if (dyn) VIT_ADAM_GROUPS(true); else VIT_ADAM_GROUPS(false);
-#undef VIT_ADAM_GROUPS
-  VIT_LAUNCH_CHECK();
-  return VIT_OK;
-}
-
-static int sgd_groups_launch(const char* who, vit_handle h, bool dyn, float* p, const float* g, float* buf, void* p_bf16,
-                             int64_t n, int64_t base, const int64_t* seg_end, const int32_t* seg_group, int n_segments,
-                             const float* groups, int n_groups, int nesterov, const float* sqnorm, float max_norm,
-                             vit_stream stream) {
   VIT_CHECK(!dyn || ctx_step_state(h), VIT_ERR_ARG, "%s: no step state bound (vit_step_state_bind)", who);
   VIT_CHECK(p && g, VIT_ERR_ARG, "%s: null pointer (p, g)", who);
-  if (int rc = groups_check(who, n, base, seg_end, seg_group, n_segments, groups, n_groups)) return rc;
+  if (table) {
+    if (int rc = groups_check(who, n, *table)) return rc;
+  } else {
+    VIT_CHECK(n > 0, VIT_ERR_ARG, "%s: n = %lld must be positive", who, (long long)n);
+    VIT_CHECK(row.mu >= 0.f, VIT_ERR_ARG, "%s: momentum = %g is negative", who, (double)row.mu);
+    VIT_CHECK(row.mu == 0.f || buf, VIT_ERR_ARG, "%s: momentum = %g needs a momentum buffer (buf is NULL)", who,
+              (double)row.mu);
+    if (row.mu == 0.f) buf = nullptr;  // torch.optim.SGD keeps no buffer then: neither read nor written
+  }
   VIT_CHECK(!nesterov || buf, VIT_ERR_ARG, "%s: nesterov needs a momentum and its buffer", who);
-  const dim3 grid(grid_for(n / 4 + 1)), block(256);
-#define VIT_SGD_GROUPS(MOM)                                                                                                   \
-  hipLaunchKernelGGL((sgd_groups_kernel<MOM>), grid, block, 0, (hipStream_t)stream, p, g, buf, (short*)p_bf16, (long)n,         \
-                     (long)base, (const long*)seg_end, (const int*)seg_group, n_segments, (const GroupRow*)groups, n_groups,   \
-                     nesterov, sqnorm, max_norm)
-  if (buf) VIT_SGD_GROUPS(true); else VIT_SGD_GROUPS(false);
-#undef VIT_SGD_GROUPS
+  const GroupTable t = table ? *table : GroupTable{};
+  const dim3 grid(grid_for(n / 4 + 1)), block(STEP_BLOCK);
+#define VIT_SGD(MOM)                                                                                                          \
+  hipLaunchKernelGGL((sgd_kernel<MOM>), grid, block, 0, (hipStream_t)stream, p, g, buf, (short*)p_bf16, (long)n, (long)t.base, \
+                     (const long*)t.seg_end, (const int*)t.seg_group, t.n_segments, (const GroupRow*)t.groups, t.n_groups,     \
+                     row, nesterov, sqnorm, max_norm)
+  if (buf) VIT_SGD(true); else VIT_SGD(false);
+#undef VIT_SGD
   VIT_LAUNCH_CHECK();
   return VIT_OK;
 }
@@ -348,77 +299,64 @@ extern "C" {
 int vit_adamw_step(vit_handle h, float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, float lr,
                    float beta1, float beta2, float eps, float weight_decay, int step, const float* sqnorm,
                    float max_norm, vit_stream stream) {
-  return adam_launch<false>("vit_adamw_step", h, false, p, g, m, v, p_bf16, n, lr, beta1, beta2, eps, weight_decay, step,
-                            sqnorm, max_norm, stream);
-}
-int vit_adamw_step_dyn(vit_handle h, float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, float beta1,
-                       float beta2, float eps, float weight_decay, const float* sqnorm, float max_norm, vit_stream stream) {
-  return adam_launch<false>("vit_adamw_step_dyn", h, true, p, g, m, v, p_bf16, n, 0.f, beta1, beta2, eps, weight_decay, 0,
-                            sqnorm, max_norm, stream);
+  return adam_launch<false>("vit_adamw_step", h, false, p, g, m, v, p_bf16, n, nullptr, {lr, weight_decay, 0.f, 0.f}, beta1,
+                            beta2, eps, step, sqnorm, max_norm, stream);
 }
 int vit_adam_l2_step(vit_handle h, float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, float lr,
                      float beta1, float beta2, float eps, float weight_decay, int step, const float* sqnorm,
                      float max_norm, vit_stream stream) {
-  return adam_launch<true>("vit_adam_l2_step", h, false, p, g, m, v, p_bf16, n, lr, beta1, beta2, eps, weight_decay, step,
-                           sqnorm, max_norm, stream);
+  return adam_launch<true>("vit_adam_l2_step", h, false, p, g, m, v, p_bf16, n, nullptr, {lr, weight_decay, 0.f, 0.f}, beta1,
+                           beta2, eps, step, sqnorm, max_norm, stream);
 }
-int vit_adam_l2_step_dyn(vit_handle h, float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, float beta1,
-                         float beta2, float eps, float weight_decay, const float* sqnorm, float max_norm,
-                         vit_stream stream) {
-  return adam_launch<true>("vit_adam_l2_step_dyn", h, true, p, g, m, v, p_bf16, n, 0.f, beta1, beta2, eps, weight_decay, 0,
-                           sqnorm, max_norm, stream);
-}
-
 int vit_sgd_step(vit_handle h, float* p, const float* g, float* buf, void* p_bf16, int64_t n, float lr, float momentum,
                  float weight_decay, int nesterov, const float* sqnorm, float max_norm, vit_stream stream) {
-  return sgd_launch("vit_sgd_step", h, false, p, g, buf, p_bf16, n, lr, momentum, weight_decay, nesterov, sqnorm, max_norm,
-                    stream);
-}
-int vit_sgd_step_dyn(vit_handle h, float* p, const float* g, float* buf, void* p_bf16, int64_t n, float weight_decay,
-                     int nesterov, const float* sqnorm, float max_norm, vit_stream stream) {
-  return sgd_launch("vit_sgd_step_dyn", h, true, p, g, buf, p_bf16, n, 0.f, 0.f, weight_decay, nesterov, sqnorm, max_norm,
-                    stream);
+  return sgd_launch("vit_sgd_step", h, false, p, g, buf, p_bf16, n, nullptr, {lr, weight_decay, momentum, 0.f}, nesterov,
+                    sqnorm, max_norm, stream);
 }
 
 int vit_adamw_step_groups(vit_handle h, float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, int64_t base,
                           const int64_t* seg_end, const int32_t* seg_group, int n_segments, const float* groups, int n_groups,
                           float beta1, float beta2, float eps, int step, const float* sqnorm, float max_norm,
                           vit_stream stream) {
-  return adam_groups_launch<false>("vit_adamw_step_groups", h, false, p, g, m, v, p_bf16, n, base, seg_end, seg_group,
-                                   n_segments, groups, n_groups, beta1, beta2, eps, step, sqnorm, max_norm, stream);
+  const GroupTable t = {base, seg_end, seg_group, n_segments, groups, n_groups};
+  return adam_launch<false>("vit_adamw_step_groups", h, false, p, g, m, v, p_bf16, n, &t, {}, beta1, beta2, eps, step, sqnorm,
+                            max_norm, stream);
 }
 int vit_adamw_step_groups_dyn(vit_handle h, float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n,
                               int64_t base, const int64_t* seg_end, const int32_t* seg_group, int n_segments,
                               const float* groups, int n_groups, float beta1, float beta2, float eps, const float* sqnorm,
                               float max_norm, vit_stream stream) {
-  return adam_groups_launch<false>("vit_adamw_step_groups_dyn", h, true, p, g, m, v, p_bf16, n, base, seg_end, seg_group,
-                                   n_segments, groups, n_groups, beta1, beta2, eps, 0, sqnorm, max_norm, stream);
+  const GroupTable t = {base, seg_end, seg_group, n_segments, groups, n_groups};
+  return adam_launch<false>("vit_adamw_step_groups_dyn", h, true, p, g, m, v, p_bf16, n, &t, {}, beta1, beta2, eps, 0, sqnorm,
+                            max_norm, stream);
 }
 int vit_adam_l2_step_groups(vit_handle h, float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, int64_t base,
                             const int64_t* seg_end, const int32_t* seg_group, int n_segments, const float* groups,
                             int n_groups, float beta1, float beta2, float eps, int step, const float* sqnorm, float max_norm,
                             vit_stream stream) {
-  return adam_groups_launch<true>("vit_adam_l2_step_groups", h, false, p, g, m, v, p_bf16, n, base, seg_end, seg_group,
-                                  n_segments, groups, n_groups, beta1, beta2, eps, step, sqnorm, max_norm, stream);
+  const GroupTable t = {base, seg_end, seg_group, n_segments, groups, n_groups};
+  return adam_launch<true>("vit_adam_l2_step_groups", h, false, p, g, m, v, p_bf16, n, &t, {}, beta1, beta2, eps, step, sqnorm,
+                           max_norm, stream);
 }
 int vit_adam_l2_step_groups_dyn(vit_handle h, float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n,
                                 int64_t base, const int64_t* seg_end, const int32_t* seg_group, int n_segments,
                                 const float* groups, int n_groups, float beta1, float beta2, float eps, const float* sqnorm,
                                 float max_norm, vit_stream stream) {
-  return adam_groups_launch<true>("vit_adam_l2_step_groups_dyn", h, true, p, g, m, v, p_bf16, n, base, seg_end, seg_group,
-                                  n_segments, groups, n_groups, beta1, beta2, eps, 0, sqnorm, max_norm, stream);
+  const GroupTable t = {base, seg_end, seg_group, n_segments, groups, n_groups};
+  return adam_launch<true>("vit_adam_l2_step_groups_dyn", h, true, p, g, m, v, p_bf16, n, &t, {}, beta1, beta2, eps, 0, sqnorm,
+                           max_norm, stream);
 }
 int vit_sgd_step_groups(vit_handle h, float* p, const float* g, float* buf, void* p_bf16, int64_t n, int64_t base,
                         const int64_t* seg_end, const int32_t* seg_group, int n_segments, const float* groups, int n_groups,
                         int nesterov, const float* sqnorm, float max_norm, vit_stream stream) {
-  return sgd_groups_launch("vit_sgd_step_groups", h, false, p, g, buf, p_bf16, n, base, seg_end, seg_group, n_segments, groups,
-                           n_groups, nesterov, sqnorm, max_norm, stream);
+  const GroupTable t = {base, seg_end, seg_group, n_segments, groups, n_groups};
+  return sgd_launch("vit_sgd_step_groups", h, false, p, g, buf, p_bf16, n, &t, {}, nesterov, sqnorm, max_norm, stream);
 }
 int vit_sgd_step_groups_dyn(vit_handle h, float* p, const float* g, float* buf, void* p_bf16, int64_t n, int64_t base,
                             const int64_t* seg_end, const int32_t* seg_group, int n_segments, const float* groups,
                             int n_groups, int nesterov, const float* sqnorm, float max_norm, vit_stream stream) {
-  return sgd_groups_launch("vit_sgd_step_groups_dyn", h, true, p, g, buf, p_bf16, n, base, seg_end, seg_group, n_segments,
-                           groups, n_groups, nesterov, sqnorm, max_norm, stream);
+  const GroupTable t = {base, seg_end, seg_group, n_segments, groups, n_groups};
+  return sgd_launch("vit_sgd_step_groups_dyn", h, true, p, g, buf, p_bf16, n, &t, {}, nesterov, sqnorm, max_norm, stream);
 }
 
 int vit_optim_groups_write(vit_handle h, float* groups, int n_groups, const float* values, vit_stream stream) {

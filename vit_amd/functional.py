@@ -568,12 +568,14 @@ def _groups_args(tables: GroupTables, base: int):
 
 
 def adamw_step_groups(p, g, m, v, p_bf16, tables: GroupTables, *, base=0, beta1=0.9, beta2=0.999, eps=1e-8, step=1, sqnorm=None,
-                      max_norm=0.0, n: Optional[int] = None, l2: bool = False):
-    """`adamw_step` (`l2`: `adam_l2_step`) over p = buffer[base : base + n] with each element's group's lr / weight_decay."""
+                      max_norm=0.0, n: Optional[int] = None, l2: bool = False, dyn: bool = False):
+    """`adamw_step` (`l2`: `adam_l2_step`) over p = buffer[base : base + n] with each element's group's lr / weight_decay.
+    `dyn` (inside a captured step): the bias corrections come from the handle's bound record instead of `step`."""
     h = _h(p)
     n = p.numel() if n is None else n
-    h.call("vit_adam_l2_step_groups" if l2 else "vit_adamw_step_groups", p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(),
-           _ptr(p_bf16), n, *_groups_args(tables, base), beta1, beta2, eps, step, _ptr(sqnorm), max_norm, _stream(p))
+    name = ("vit_adam_l2_step_groups" if l2 else "vit_adamw_step_groups") + ("_dyn" if dyn else "")
+    h.call(name, p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), _ptr(p_bf16), n, *_groups_args(tables, base), beta1, beta2,
+           eps, *(() if dyn else (step,)), _ptr(sqnorm), max_norm, _stream(p))
 
 
 def adam_l2_step_groups(p, g, m, v, p_bf16, tables: GroupTables, **kw):
@@ -581,10 +583,10 @@ def adam_l2_step_groups(p, g, m, v, p_bf16, tables: GroupTables, **kw):
 
 
 def sgd_step_groups(p, g, buf, p_bf16, tables: GroupTables, *, base=0, nesterov=False, sqnorm=None, max_norm=0.0,
-                    n: Optional[int] = None):
+                    n: Optional[int] = None, dyn: bool = False):
     """`sgd_step` over p = buffer[base : base + n] with each element's group's lr / momentum / weight_decay; `buf` may be None
-    when every group's momentum is 0."""
+    when every group's momentum is 0.  `dyn` (inside a captured step): insists on the handle's bound record."""
     h = _h(p)
     n = p.numel() if n is None else n
-    h.call("vit_sgd_step_groups", p.data_ptr(), g.data_ptr(), _ptr(buf), _ptr(p_bf16), n, *_groups_args(tables, base),
-           int(bool(nesterov)), _ptr(sqnorm), max_norm, _stream(p))
+    h.call("vit_sgd_step_groups_dyn" if dyn else "vit_sgd_step_groups", p.data_ptr(), g.data_ptr(), _ptr(buf), _ptr(p_bf16), n,
+           *_groups_args(tables, base), int(bool(nesterov)), _ptr(sqnorm), max_norm, _stream(p))

@@ -2,10 +2,11 @@
 
 A ViT-B step is ~340 kernel launches from Python through ctypes; eagerly the host keeps up, but ~0.7-1 ms of the 42 ms
 step were gaps between launches.  Captured once, the step is replayed with one `hipGraphLaunch`.  What changes from step
-to step cannot live in kernel arguments (they are frozen at capture), so it lives in a 32-byte device record the library
-reads at kernel entry (`vit_step_state_bind`, include/vit_amd.h): the dropout keys of the step and Adam's step count /
-bias corrections, advanced by the first node of the graph (`vit_step_advance`); the learning rate (and SGD's momentum) is
-written into that record by the host whenever a scheduler changes it.
+to step cannot live in kernel arguments (they are frozen at capture), so it lives in device memory the kernels read at
+entry: a 32-byte record (`vit_step_state_bind`, include/vit_amd.h) with the dropout keys of the step and Adam's step count /
+bias corrections, advanced by the first node of the graph (`vit_step_advance`); and the optimizer's group table with the
+learning rates, weight decays and SGD's momenta, which the optimizer rewrites ahead of a replay whenever a scheduler changed
+one (`FusedOptimizer._sync_group_table`).  The host writes nothing into the record but the step counter.
 
 Scope: one process, one GPU (the RCCL exchange of N > 1 is not captured), a fused optimizer (vit_amd/optimizer.py:
 FusedAdamW, FusedSGD), no trainable input preprocessor, a fixed batch shape.  The reference's step semantics are unchanged
@@ -49,10 +50,8 @@ class GraphedTrainStep:
         dev = eng.flat.device
         eng._ensure_device_state()
         self.h = eng.handle()  # the engine's own handle: its calls read the bound per-step record
-        # per-step device record: [key0, key1 (u32) | lr, bc1, rsqrt_bc2 (f32) | step (u32) | momentum (f32) | pad]
+        # per-step device record: [key0, key1 (u32) | reserved | bc1, rsqrt_bc2 (f32) | step (u32) | reserved, reserved]
         self.state = torch.zeros(8, dtype=torch.int32, device=dev)
-        self._record = {}  # host mirror of the words the host writes
-        self._write_record()
         self.state[5] = int(optimizer._step)
         self.x = flux.detach().to(dev, torch.float32).contiguous().clone()
         self.labels = labels.detach().to(dev).contiguous().clone()
@@ -63,6 +62,7 @@ class GraphedTrainStep:
         self._betas = optimizer._graph_betas()
         optimizer._ensure_state()
         self._captured = optimizer._graph_signature()
+        self._tables = optimizer._sync_group_table()  # the capture holds their addresses; `_captured` pins the partition
         module.train()
         # the warm-up steps below are real optimisation steps; parameters, optimizer state and counters are put back afterwards
         # so that the first replay IS the run's next step
@@ -104,13 +104,6 @@ class GraphedTrainStep:
             eng.mark_shadow_fresh()
             torch.cuda.synchronize(dev)
 
-    def _write_record(self):
-        """The record's words that are the host's to write (lr; SGD's momentum), each only when it has changed."""
-        for word, value in self.opt._graph_record().items():
-            if self._record.get(word) != value:
-                self.state[word:word + 1].view(torch.float32).fill_(value)
-                self._record[word] = value
-
     def _body(self):
         """The captured sequence.  Host-side scalars below (seed, step) are frozen at capture; their per-step versions
         come from the bound device record.  Every call goes through the engine's handle (one workspace, held below)."""
@@ -130,8 +123,7 @@ class GraphedTrainStep:
         if opt._clip is not None:
             sq = vf.grad_sqnorm(eng.grads[:n], out=opt._sq)
             opt.last_grad_norm = sq
-        shadow = eng.shadow if eng.precision == "bf16" else None
-        opt._graph_update(self.h, n, None if shadow is None else shadow.data_ptr(), None if sq is None else sq.data_ptr(), st)
+        opt._launch(0, n, self._tables, eng.shadow if eng.precision == "bf16" else None, sq, dyn=True)
         return loss
 
     def step(self, batch) -> torch.Tensor:
@@ -143,7 +135,7 @@ class GraphedTrainStep:
         if labels is not self._src[1] or labels._version != self._src[3]:
             self.labels.copy_(labels, non_blocking=True)
             self._src = (self._src[0], None, self._src[2], -1)
-        self._write_record()
+        self.opt._sync_group_table()  # on the current stream, ahead of the replay: a launch only when a scheduler changed a number
         if self._dev_step != int(self.opt._step):
             # the record's step counter (Adam's bias corrections, dropout keys) is advanced by THIS graph's replays only: steps
             # taken elsewhere in between -- another captured shape (an epoch's partial last batch), eager steps -- put it back

@@ -38,17 +38,18 @@ class FusedOptimizer(torch.optim.Optimizer):
     average with a local gradient, so it is an error there.  With a sharding reducer ('zero1') each rank updates only its
     shard of every sharded bucket and the updated parameters are all-gathered.
 
-    A subclass provides: `_STATE` (attribute names of its flat state buffers, each None until allocated), `_ensure_state()`,
-    `_step_args(group, sqnorm)`, `_update(p, g, states, p_bf16, kw)`, `_extra_buffers(p)`; and for a captured step
-    (vit_amd/graph.py) `_graph_record()`, `_graph_update(...)`, optionally `_graph_betas()` / `_graph_signature()`.
-
     Parameter groups (`param_groups=[{"params": [parameters or their names], "lr": ..., "weight_decay": ...}, ...]` at
     construction, or `add_param_group`; keys a group omits take the defaults; a parameter no group names is not stepped, as in
-    torch).  One group is the path above, unchanged.  With more, every active run of the flat buffer is still ONE launch: the
-    `*_step_groups` kernels (include/vit_amd_optim.h) look each element's lr / weight_decay / momentum up in a segment table
-    built from the partition (rebuilt when it changes) and a group table that is rewritten, ahead of the step, only when a
-    scheduler changed a number.  What the kernel shares across groups (`_SHARED`) must agree, else ValueError.  For these a
-    subclass adds `_SHARED`, `_group_values(group)` and `_update_groups(p, g, states, p_bf16, tables, base, sqnorm)`."""
+    torch).  One group or many, every active run of the flat buffer is ONE launch of the `*_step_groups` kernels
+    (include/vit_amd_optim.h): they look each element's lr / weight_decay / momentum up in a segment table built from the
+    partition (rebuilt when it changes) and a group table that is rewritten, ahead of the step, only when a scheduler changed a
+    number; a single group is a table of one segment and one row.  The step captured as a hipGraph (vit_amd/graph.py) issues
+    the same launch in its `dyn` form.  What the kernel shares across groups (`_SHARED`) must agree, else ValueError.
+
+    A subclass provides: `_STATE` (attribute names of its flat state buffers, each None until allocated), `_SHARED`,
+    `_ensure_state()`, `_group_values(group)` (the group's table row, validated), `_launch(lo, hi, tables, shadow, sqnorm, dyn)`
+    (the table launch over flat[lo:hi]), `_update_extra(p, group, sqnorm)` and `_extra_buffers(p)` (a parameter outside the flat
+    buffer, by value); optionally `_graph_betas()` / `_graph_signature()` / `_graph_validate()`."""
 
     _STATE = ()
     _SHARED = ()
@@ -97,6 +98,7 @@ class FusedOptimizer(torch.optim.Optimizer):
     def _refresh_members(self):
         """Which group owns which parameter, and which owned parameters lie outside the engine's flat buffer."""
         own = {id(p) for p in getattr(self.model, "_param_list", [])}
+        self._members_of = self._partition_signature()
         self._group_index = {id(p): gi for gi, grp in enumerate(self.param_groups) for p in grp["params"]}
         self._extras = [p for grp in self.param_groups for p in grp["params"] if id(p) not in own]
 
@@ -199,9 +201,8 @@ class FusedOptimizer(torch.optim.Optimizer):
                 loss = closure()
         eng = self.model.engine
         self._ensure_state()
-        g = self.param_groups[0]
-        grouped = len(self.param_groups) > 1
-        tables = self._sync_group_table() if grouped else None  # also re-reads who owns what
+        if self._members_of != self._partition_signature():  # a group's member list was edited in place
+            self._refresh_members()
         runs = self._active_ranges()
         extras = [p for p in self._extras if p.grad is not None]
         if not runs and not extras:
@@ -227,23 +228,16 @@ class FusedOptimizer(torch.optim.Optimizer):
                 vf.grad_sqnorm(p.grad.contiguous().view(-1), out=sq, accumulate=True)
             self.last_grad_norm = sq
         shadow = eng.shadow if eng.precision == "bf16" else None  # f32 mode has no bf16 copy to refresh
-        kw = self._step_args(g, sq)
-        states = self._flat_states()
-        for a, b in runs:
-            if grouped:  # one launch per run all the same: the kernel looks the groups up from the run's offset `a`
-                self._update_groups(eng.flat[a:b], eng.grads[a:b], [s[a:b] for s in states],
-                                    None if shadow is None else shadow[a:b], tables, a, sq)
-            else:
-                self._update(eng.flat[a:b], eng.grads[a:b], [s[a:b] for s in states], None if shadow is None else shadow[a:b], kw)
+        tables = self._sync_group_table() if runs else None  # no run (all of the flat buffer frozen): no table to ask for
+        for a, b in runs:  # one launch per run: the kernel looks the groups up from the run's offset `a`
+            self._launch(a, b, tables, shadow, sq)
         if red is not None:
             red.all_gather_params(eng.flat)
             if shadow is not None:
                 vf.cast_f32_bf16(eng.flat, shadow)
         eng.mark_shadow_fresh()  # the kernel rewrote flat AND shadow through raw pointers
         for p in extras:
-            if grouped:
-                kw = self._step_args(self._group_for(p), sq)
-            self._update(p.data.view(-1), p.grad.contiguous().view(-1), self._extra_buffers(p), None, kw)
+            self._update_extra(p, self._group_for(p), sq)
         return loss
 
     def _shard_runs(self, runs, red):
@@ -303,18 +297,12 @@ class FusedOptimizer(torch.optim.Optimizer):
 
     def _graph_signature(self):
         """What of this optimizer's set-up is frozen into a capture; `_graph_validate` raises ValueError when a replay would
-        no longer be the eager step.  Here: the partition into groups (None for a single group) -- the capture holds the
-        segment table's address and the choice between the plain and the grouped kernel."""
-        return self._partition_signature() if len(self.param_groups) > 1 else None
+        no longer be the eager step.  Here: the partition into groups -- the capture holds the segment table's address."""
+        return self._partition_signature()
 
     def _graph_validate(self, signature):
         if signature != FusedOptimizer._graph_signature(self):
             raise ValueError("the optimizer's parameter groups were repartitioned after the step was captured")
-
-    def _graph_groups(self):
-        """Inside `_graph_update`: the tables for the grouped `_dyn` launch, or None for a single group.  The group table was
-        brought up to date by `_graph_record()` ahead of the capture / the replay."""
-        return self._partition()[2] if len(self.param_groups) > 1 else None
 
     # ------------------------------------------------------------------ torch.optim-format state
     def _param_slices(self):
@@ -363,20 +351,23 @@ class FusedAdamW(FusedOptimizer):
         self._ensure_sq()
         self._ensure_flat(self._STATE)
 
-    def _step_args(self, g, sq):
-        return dict(lr=float(g["lr"]), beta1=g["betas"][0], beta2=g["betas"][1], eps=g["eps"], weight_decay=g["weight_decay"],
-                    step=self._step, sqnorm=sq, max_norm=float(self._clip or 0.0))
-
-    def _update(self, p, g, states, p_bf16, kw):
-        (vf.adam_l2_step if self.adam_l2 else vf.adamw_step)(p, g, states[0], states[1], p_bf16, **kw)
-
     def _group_values(self, grp):
         return float(grp["lr"]), float(grp["weight_decay"]), 0.0
 
-    def _update_groups(self, p, g, states, p_bf16, tables, base, sq):
-        g0 = self.param_groups[0]
-        vf.adamw_step_groups(p, g, states[0], states[1], p_bf16, tables, base=base, beta1=g0["betas"][0], beta2=g0["betas"][1],
-                             eps=g0["eps"], step=self._step, sqnorm=sq, max_norm=float(self._clip or 0.0), l2=self.adam_l2)
+    def _launch(self, lo, hi, tables, shadow, sq, dyn=False):
+        """The update of flat[lo:hi]; `dyn` (inside a capture): the bias corrections come from the bound record."""
+        eng, g0 = self.model.engine, self.param_groups[0]
+        vf.adamw_step_groups(eng.flat[lo:hi], eng.grads[lo:hi], self._m[lo:hi], self._v[lo:hi],
+                             None if shadow is None else shadow[lo:hi], tables, base=lo, beta1=g0["betas"][0],
+                             beta2=g0["betas"][1], eps=g0["eps"], step=self._step, sqnorm=sq, max_norm=float(self._clip or 0.0),
+                             l2=self.adam_l2, dyn=dyn)
+
+    def _update_extra(self, p, grp, sq):
+        m, v = self._extra_buffers(p)
+        (vf.adam_l2_step if self.adam_l2 else vf.adamw_step)(
+            p.data.view(-1), p.grad.contiguous().view(-1), m, v, None, lr=float(grp["lr"]), beta1=grp["betas"][0],
+            beta2=grp["betas"][1], eps=grp["eps"], weight_decay=grp["weight_decay"], step=self._step, sqnorm=sq,
+            max_norm=float(self._clip or 0.0))
 
     def _extra_buffers(self, p):
         st = self._extra_state.get(id(p))
@@ -386,32 +377,6 @@ class FusedAdamW(FusedOptimizer):
 
     def _graph_betas(self):
         return tuple(self.param_groups[0]["betas"])
-
-    def _graph_record(self):
-        if len(self.param_groups) > 1:  # the rates live in the group table, not in the record
-            self._sync_group_table()
-            return {}
-        return {2: float(self.param_groups[0]["lr"])}
-
-    def _graph_update(self, h, n, p_bf16, sqnorm, stream):
-        """The update of flat[:n] inside a capture: lr and the bias corrections come from the bound record, everything else
-        is frozen at capture.  With parameter groups: the bias corrections from the record, lr and weight_decay from the group
-        table (written ahead of each replay when they changed)."""
-        from . import _cabi
-
-        eng, g = self.model.engine, self.param_groups[0]
-        t = self._graph_groups()
-        if t is not None:
-            name = "vit_adam_l2_step_groups_dyn" if self.adam_l2 else "vit_adamw_step_groups_dyn"
-            _cabi.check(getattr(h.lib, name)(h.h, eng.flat.data_ptr(), eng.grads.data_ptr(), self._m.data_ptr(),
-                                             self._v.data_ptr(), p_bf16, n, 0, t.seg_end.data_ptr(), t.seg_group.data_ptr(),
-                                             t.n_segments, t.groups.data_ptr(), t.n_groups, g["betas"][0], g["betas"][1],
-                                             g["eps"], sqnorm, float(self._clip or 0.0), stream), name)
-            return
-        name = "vit_adam_l2_step_dyn" if self.adam_l2 else "vit_adamw_step_dyn"
-        _cabi.check(getattr(h.lib, name)(h.h, eng.flat.data_ptr(), eng.grads.data_ptr(), self._m.data_ptr(), self._v.data_ptr(),
-                                         p_bf16, n, g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"], sqnorm,
-                                         float(self._clip or 0.0), stream), name)
 
     # ------------------------------------------------------------------ torch.optim.AdamW-format state
     def state_dict(self):
@@ -473,14 +438,10 @@ class FusedSGD(FusedOptimizer):
     _SHARED = ("nesterov", "dampening")
 
     def __init__(self, model, lr=1e-3, momentum=0, dampening=0, weight_decay=0, nesterov=False, param_groups=None):
-        if dampening != 0:
-            raise ValueError("FusedSGD supports dampening = 0 only (a zero momentum buffer then reproduces torch's first step)")
-        if lr < 0 or momentum < 0 or weight_decay < 0:
-            raise ValueError(f"FusedSGD: lr = {lr}, momentum = {momentum}, weight_decay = {weight_decay} must not be negative")
-        if nesterov and momentum <= 0:
-            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
-        super().__init__(model, dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov,
-                                     maximize=False, foreach=None, differentiable=False, fused=None), param_groups)
+        defaults = dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov,
+                        maximize=False, foreach=None, differentiable=False, fused=None)
+        self._group_values(defaults)
+        super().__init__(model, defaults, param_groups)
         self._buf = None
 
     def _ensure_state(self):
@@ -489,24 +450,28 @@ class FusedSGD(FusedOptimizer):
             self._ensure_flat(self._STATE)
 
     def _group_values(self, grp):
+        """The group's table row; what FusedSGD refuses is refused here, for the constructor's defaults and on every step."""
         if grp["dampening"] != 0 or grp.get("maximize"):
-            raise ValueError("FusedSGD supports neither dampening nor maximize")
-        if grp["momentum"] < 0 or (grp["nesterov"] and grp["momentum"] <= 0):
-            raise ValueError(f"FusedSGD: momentum = {grp['momentum']} (nesterov = {grp['nesterov']})")
-        return float(grp["lr"]), float(grp["weight_decay"]), float(grp["momentum"])
+            raise ValueError("FusedSGD supports neither dampening nor maximize (dampening = 0: a zero momentum buffer then "
+                             "reproduces torch's first step)")
+        lr, wd, mu = float(grp["lr"]), float(grp["weight_decay"]), float(grp["momentum"])
+        if lr < 0 or mu < 0 or wd < 0:
+            raise ValueError(f"FusedSGD: lr = {lr}, momentum = {mu}, weight_decay = {wd} must not be negative")
+        if grp["nesterov"] and mu <= 0:
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        return lr, wd, mu
 
-    def _update_groups(self, p, g, states, p_bf16, tables, base, sq):
-        vf.sgd_step_groups(p, g, states[0] if states else None, p_bf16, tables, base=base,
-                           nesterov=bool(self.param_groups[0]["nesterov"]), sqnorm=sq, max_norm=float(self._clip or 0.0))
+    def _launch(self, lo, hi, tables, shadow, sq, dyn=False):
+        """The update of flat[lo:hi]; whether there is a momentum buffer at all, and nesterov, are frozen into a capture."""
+        eng = self.model.engine
+        vf.sgd_step_groups(eng.flat[lo:hi], eng.grads[lo:hi], None if self._buf is None else self._buf[lo:hi],
+                           None if shadow is None else shadow[lo:hi], tables, base=lo,
+                           nesterov=bool(self.param_groups[0]["nesterov"]), sqnorm=sq, max_norm=float(self._clip or 0.0), dyn=dyn)
 
-    def _step_args(self, g, sq):
-        if g["dampening"] != 0 or g.get("maximize"):
-            raise ValueError("FusedSGD supports neither dampening nor maximize")
-        return dict(lr=float(g["lr"]), momentum=float(g["momentum"]), weight_decay=float(g["weight_decay"]),
-                    nesterov=bool(g["nesterov"]), sqnorm=sq, max_norm=float(self._clip or 0.0))
-
-    def _update(self, p, g, states, p_bf16, kw):
-        vf.sgd_step(p, g, states[0] if states and kw["momentum"] != 0 else None, p_bf16, **kw)
+    def _update_extra(self, p, grp, sq):
+        lr, wd, mu = self._group_values(grp)
+        vf.sgd_step(p.data.view(-1), p.grad.contiguous().view(-1), *(self._extra_buffers(p) or (None,)), None, lr=lr, momentum=mu,
+                    weight_decay=wd, nesterov=bool(grp["nesterov"]), sqnorm=sq, max_norm=float(self._clip or 0.0))
 
     def _extra_buffers(self, p):
         if self._group_for(p)["momentum"] == 0:
@@ -516,13 +481,6 @@ class FusedSGD(FusedOptimizer):
             st = self._extra_state[id(p)] = (torch.zeros_like(p.data).view(-1),)
         return st
 
-    def _graph_record(self):
-        if len(self.param_groups) > 1:  # rates and momenta live in the group table, not in the record
-            self._sync_group_table()
-            return {}
-        g = self.param_groups[0]
-        return {2: float(g["lr"]), 6: float(g["momentum"])}
-
     def _graph_signature(self):
         return self._buf is not None, super()._graph_signature()
 
@@ -530,31 +488,8 @@ class FusedSGD(FusedOptimizer):
         had_buffer, partition = signature
         super()._graph_validate(partition)
         mu = max(grp["momentum"] for grp in self.param_groups)
-        if mu != 0 and not had_buffer:
+        if mu != 0 and not had_buffer:  # (a momentum that becomes 0 needs nothing: the kernel skips such a row's buffer itself)
             raise ValueError(f"SGD's momentum became {mu} after the step was captured without a momentum buffer")
-        if mu == 0 and had_buffer and partition is None:  # (the grouped kernel skips a zero-momentum group's buffer itself)
-            raise ValueError("SGD's momentum became 0 after the step was captured with a momentum buffer")
-
-    def _graph_update(self, h, n, p_bf16, sqnorm, stream):
-        """The update of flat[:n] inside a capture: lr and momentum come from the bound record; weight decay, nesterov and
-        whether there is a momentum buffer at all are frozen at capture."""
-        from . import _cabi
-
-        eng, g = self.model.engine, self.param_groups[0]
-        t = self._graph_groups()
-        if t is not None:  # lr, momentum and weight decay per group from the table; nesterov frozen at capture
-            _cabi.check(h.lib.vit_sgd_step_groups_dyn(h.h, eng.flat.data_ptr(), eng.grads.data_ptr(),
-                                                      None if self._buf is None else self._buf.data_ptr(), p_bf16, n, 0,
-                                                      t.seg_end.data_ptr(), t.seg_group.data_ptr(), t.n_segments,
-                                                      t.groups.data_ptr(), t.n_groups, int(bool(g["nesterov"])), sqnorm,
-                                                      float(self._clip or 0.0), stream), "vit_sgd_step_groups_dyn")
-            return
-        if g["dampening"] != 0 or g.get("maximize"):
-            raise ValueError("FusedSGD supports neither dampening nor maximize")
-        _cabi.check(h.lib.vit_sgd_step_dyn(h.h, eng.flat.data_ptr(), eng.grads.data_ptr(),
-                                           None if self._buf is None else self._buf.data_ptr(), p_bf16, n,
-                                           float(g["weight_decay"]), int(bool(g["nesterov"])), sqnorm,
-                                           float(self._clip or 0.0), stream), "vit_sgd_step_dyn")
 
     # ------------------------------------------------------------------ torch.optim.SGD-format state
     def state_dict(self):
