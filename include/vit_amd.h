@@ -49,7 +49,9 @@ const char* vit_last_error(void);
  * holds returns VIT_ERR_WORKSPACE BEFORE launching anything -- nothing was written, and the call may simply be repeated with a
  * larger workspace, also under "grad_accumulate" -- and vit_workspace_needed() then returns the bytes that whole call needs
  * (thread-local, like vit_last_error).  The need depends on the call's arguments and the handle's options alone, and no call
- * chooses its kernels or its summation order by the size of the workspace. */
+ * chooses its kernels or its summation order by the size of the workspace.  vit_gemm's need is exact: the maximum over the stages
+ * the call really runs (its split-K slabs; the column sums' partials of the one route it takes), plus the scratch matrix below
+ * where there is one; and every argument error of a vit_gemm is reported before its workspace is asked for. */
 int vit_create(vit_handle* out, int device);
 int vit_destroy(vit_handle h);
 int vit_set_workspace(vit_handle h, void* ws, size_t bytes);
@@ -87,7 +89,8 @@ int vit_set_option(const char* name, int value);
  * + old C); single-slice products -- the epilogue's residual port reads old C; vit_linear_bwd_dw_rows -- the final store of
  * the slice total; every vector output -- the last stage of the partial-row reducer.  A vit_gemm whose C accumulates AND that
  * carries colsum_out (two parameter gradients from one descriptor; no training step issues it) runs the product into a
- * scratch matrix at the end of the workspace (part of what the call needs of it), sums its columns and adds it into C. */
+ * scratch matrix in the workspace, behind what its stages use (part of what the call needs of it), sums its columns and adds it
+ * into C. */
 int vit_handle_set_option(vit_handle h, const char* name, int value);
 
 /* Per-step state in device memory, for a training step captured as a hipGraph (HIP streams and graphs instead of a tracing
@@ -162,8 +165,10 @@ typedef struct vit_gemm_desc {
   int drop_row_stride;
 } vit_gemm_desc;
 int vit_gemm(vit_handle h, const vit_gemm_desc* d, vit_stream stream);
-/* Symbol (as rocprofv3 prints it, without the "void vit::" prefix and argument list) of the kernel the calling thread's
- * last vit_gemm launched: lets a benchmark attribute its per-call timings to the kernels a profiler lists. */
+/* Symbol (as rocprofv3 prints it, without the "void vit::" prefix and argument list) of the kernel of the calling thread's
+ * last vit_gemm that passed its argument checks: written when the call is planned, before its workspace is claimed, so a call
+ * refused with VIT_ERR_WORKSPACE (or one that cannot launch) still names the kernel it would run.  Lets a benchmark attribute
+ * its per-call timings to the kernels a profiler lists. */
 const char* vit_last_gemm_kernel(void);
 
 /* Convenience forms named after SURVEY.md section 8b.  x:[M,K] bf16, W:[N,K] bf16 (nn.Linear layout), y:[M,N]. */

@@ -27,17 +27,32 @@ def lib():
     return _cabi.load()
 
 
-def gemm_desc(M, N, K, *, ab=BF16, c=F32, a_trans=1, b_trans=1, split_k=-1, colsum=False):
+ACT_DGELU, ACT_GELU_GRAD = 2, 3
+
+
+def gemm_desc(M, N, K, *, ab=BF16, c=F32, a_trans=1, b_trans=1, split_k=-1, colsum=False, bias=False, act=0, rope=None,
+              accumulate=0, buf=lambda name, rows, cols, dtype: P):
+    """A vit_gemm descriptor over dense operands; buf(name, rows, cols, dtype) -> the address of that tensor (here: made up)."""
     from vit_amd import _cabi
 
     d = _cabi.GemmDesc()
     d.M, d.N, d.K, d.a_trans, d.b_trans, d.ab_dtype = M, N, K, a_trans, b_trans, ab
-    d.A, d.lda = P, M if a_trans else K
-    d.B, d.ldb = P, N if b_trans else K
-    d.C, d.ldc, d.c_dtype = P, N, c
-    d.alpha, d.split_k = 1.0, split_k
+    d.lda, d.ldb, d.ldc, d.ldaux = (M if a_trans else K), (N if b_trans else K), N, N
+    d.A = buf("A", K if a_trans else M, d.lda, ab)
+    d.B = buf("B", K if b_trans else N, d.ldb, ab)
+    d.C, d.c_dtype = buf("C", M, N, c), c
+    d.alpha, d.split_k, d.act, d.accumulate = 1.0, split_k, act, accumulate
     if colsum:
-        d.colsum_out = P
+        d.colsum_out = buf("colsum_out", 1, N, F32)
+    if bias:
+        d.bias = buf("bias", 1, N, F32)
+    if act == ACT_GELU_GRAD:
+        d.aux_out = buf("aux_out", M, N, BF16)
+    if act == ACT_DGELU:
+        d.aux_in = buf("aux_in", M, N, BF16)
+    if rope:
+        d.rope_T, d.rope_dh, d.rope_cols = rope
+        d.rope_cos, d.rope_sin = buf("rope_cos", d.rope_T, d.rope_dh // 2, F32), buf("rope_sin", d.rope_T, d.rope_dh // 2, F32)
     return d
 
 
@@ -94,12 +109,61 @@ def test_colsum_rows_claims_before_any_launch(lib):
 
 
 def test_gemm_with_colsum_out(lib):
+    """The claim is that of the column-sum route the plan takes, not the larger of both."""
     d = gemm_desc(512, 256, 256, c=BF16, a_trans=0, b_trans=1, split_k=0, colsum=True)  # ping-pong: sums in the epilogue
     assert lib.vit_gemm(None, ctypes.byref(d), None) == WS
-    assert lib.vit_workspace_needed() >= (512 // 256) * 2 * 256 * 4
+    assert lib.vit_workspace_needed() == (512 // 256) * 2 * 256 * 4 == 4096
     d = gemm_desc(200, 64, 64, c=BF16, a_trans=0, b_trans=0, split_k=0, colsum=True)  # generic: a vit_colsum pass behind it
     assert lib.vit_gemm(None, ctypes.byref(d), None) == WS
-    assert lib.vit_workspace_needed() >= colsum_ws_bytes(200, 64)
+    assert lib.vit_workspace_needed() == colsum_ws_bytes(200, 64) == 1024
+
+
+# What the plan of one vit_gemm decides, asked without a device: a call with a need is refused (-4) and states it, one without
+# gets as far as its launch (-2); either way vit_last_gemm_kernel() names the kernel planned.  A NULL handle sees 256 CUs.
+# Needs and symbols are the parent commit's: the needs as it stated them (colsum_out: of the route it then took), the symbols as
+# its library reported them after running each call on an MI355X with real buffers.
+FWD, DX, DW = dict(a_trans=0, b_trans=0), dict(a_trans=0, b_trans=1), dict(a_trans=1, b_trans=1)
+GEMM_TABLE = {
+    # split-K on each core
+    "dw_splitk_pingpong": (dict(M=256, N=256, K=4096, **DW), 2097152, "gemm3_kernel<1, 1, 7, 8>"),
+    "dw_splitk_generic": (dict(M=128, N=128, K=4096, **DW), 1048576, "gemm_bf16_kernel<1, 1>"),
+    "dw_splitk_x3": (dict(M=128, N=128, K=4096, ab=F32, **DW), 2097152, "gemm_f32x3_kernel<1, 1>"),
+    # column sums: passed behind the generic epilogue (0) and the generic core, fused into epilogues 5 and 6
+    "dx_f32_colsum_pass": (dict(M=256, N=256, K=64, split_k=0, colsum=True, **DX), 4096, "gemm3_kernel<0, 1, 0, 8>"),
+    "generic_colsum_pass": (dict(M=200, N=64, K=64, c=BF16, split_k=0, colsum=True, **FWD), 1024, "gemm_bf16_kernel<0, 0>"),
+    "dx_dgelu_colsum_fused": (dict(M=256, N=256, K=64, c=BF16, split_k=0, act=ACT_DGELU, colsum=True, **DX), 2048,
+                              "gemm3_kernel<0, 1, 5, 8>"),
+    "dx_colsum_fused": (dict(M=512, N=256, K=256, c=BF16, split_k=0, colsum=True, **DX), 4096, "gemm3_kernel<0, 1, 6, 8>"),
+    # no workspace: epilogues 3, 4, 7, 8, the rope pass behind epilogue 3 at head_dim 128 and behind the generic core, x3
+    "fwd_bias": (dict(M=256, N=256, K=64, c=BF16, split_k=0, bias=True, **FWD), 0, "gemm3_kernel<0, 0, 3, 8>"),
+    "fwd_gelu_grad": (dict(M=256, N=256, K=64, c=BF16, split_k=0, bias=True, act=ACT_GELU_GRAD, **FWD), 0,
+                      "gemm3_kernel<0, 0, 4, 8>"),
+    "dw_one_slice": (dict(M=256, N=256, K=64, split_k=1, **DW), 0, "gemm3_kernel<1, 1, 7, 8>"),
+    "dw_one_slice_accumulate": (dict(M=256, N=256, K=64, split_k=1, accumulate=1, **DW), 0, "gemm3_kernel<1, 1, 0, 8>"),
+    "qk_rope_epilogue": (dict(M=256, N=256, K=64, c=BF16, split_k=0, bias=True, rope=(16, 64, 256), **FWD), 0,
+                         "gemm3_kernel<0, 0, 8, 8>"),
+    "qk_rope_pass_dh128": (dict(M=256, N=512, K=64, c=BF16, split_k=0, bias=True, rope=(16, 128, 256), **FWD), 0,
+                           "gemm3_kernel<0, 0, 3, 8>"),
+    "projection_generic_rope_pass": (dict(M=256, N=384, K=64, c=BF16, split_k=0, bias=True, rope=(16, 64, 256), **FWD), 0,
+                                     "gemm_bf16_kernel<0, 0>"),
+    "fwd_x3": (dict(M=64, N=64, K=64, ab=F32, split_k=0, **FWD), 0, "gemm_f32x3_kernel<0, 0>"),
+}
+
+
+@pytest.mark.parametrize("name", list(GEMM_TABLE))
+def test_gemm_plan_table(lib, name):
+    kw, need, symbol = GEMM_TABLE[name]
+    d = gemm_desc(**kw)
+    assert lib.vit_gemm(None, ctypes.byref(d), None) == (WS if need else -2), lib.vit_last_error()
+    if need:
+        assert lib.vit_workspace_needed() == need
+    assert lib.vit_last_gemm_kernel().decode() == symbol
+
+
+def test_gemm_argument_errors_come_before_the_claim(lib):
+    d = gemm_desc(128, 128, 4096, split_k=4, bias=True)  # the parent claimed the four slabs first (-4), then refused the bias
+    assert lib.vit_gemm(None, ctypes.byref(d), None) == -1
+    assert b"split_k supports only alpha and an f32 C" in lib.vit_last_error()
 
 
 def test_handle_free_entry_points_no_longer_reject_a_null_handle(lib):

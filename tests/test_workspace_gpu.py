@@ -285,3 +285,91 @@ def test_engine_on_an_empty_workspace(dev, precision):
         if empty:
             assert eng._main_handle.workspace_bytes > 0
     assert torch.equal(grads[0], grads[1])
+
+
+# ---------------------------------------------------------------------------------- (e) vit_gemm's exact claim is a sufficient one
+GUARD = 1 << 16  # sentinel bytes behind the workspace
+GUARD_BYTE = 0xA5
+
+
+def real_gemm_desc(dev, kw):
+    """The descriptor of tests/test_workspace_cpu.py's gemm_desc over real tensors: inputs seeded by their name, outputs filled
+    with SENTINEL (an accumulating C reads it as its old value).  Returns (descriptor, {name: tensor})."""
+    from test_workspace_cpu import BF16, gemm_desc
+
+    held = {}
+
+    def buf(name, rows, cols, dtype):
+        tdt = torch.bfloat16 if dtype == BF16 else torch.float32
+        if name in ("C", "colsum_out", "aux_out"):
+            t = filled((rows, cols), dev, tdt)
+        elif name in ("rope_cos", "rope_sin"):  # the reference's table: angle t * theta_i
+            ang = torch.arange(rows, dtype=torch.float32)[:, None] * 10000.0 ** (-torch.arange(cols, dtype=torch.float32) / cols)
+            t = (ang.cos() if name == "rope_cos" else ang.sin()).to(dev)
+        else:
+            t = randn((rows, cols), dev, 60 + sum(map(ord, name)), tdt)
+        held[name] = t
+        return t.data_ptr()
+
+    return gemm_desc(**kw, buf=buf), held
+
+
+def gemm_on_exact_workspace(dev, kw, need, **options):
+    """Refused on an empty workspace (where it needs one), then run on exactly vit_workspace_needed() bytes with sentinel bytes
+    behind them, then on a large one: returns the outputs of the exact and of the large run."""
+    import vit_amd.functional as vf
+
+    h = handle(dev, 0, **options)
+    lib, st = h.lib, vf._stream(torch.empty(1, device=dev))
+    d, held = real_gemm_desc(dev, kw)
+    rc = lib.vit_gemm(h.h, ctypes.byref(d), st)
+    if need:
+        assert rc == WS, (rc, lib.vit_last_error())
+        assert lib.vit_workspace_needed() == need
+        assert untouched(*(t for name, t in held.items() if name in ("C", "colsum_out", "aux_out")))
+        big = torch.full((need + GUARD,), GUARD_BYTE, dtype=torch.uint8, device=dev)
+        assert lib.vit_set_workspace(h.h, big.data_ptr(), need) == 0
+        rc = lib.vit_gemm(h.h, ctypes.byref(d), st)
+        torch.cuda.synchronize()
+        assert bool((big[need:] == GUARD_BYTE).all())
+    assert rc == 0, (rc, lib.vit_last_error())
+    large = handle(dev, 8 << 20, **options)
+    d2, held2 = real_gemm_desc(dev, kw)
+    assert lib.vit_gemm(large.h, ctypes.byref(d2), st) == 0, lib.vit_last_error()
+    torch.cuda.synchronize()
+    return held, held2
+
+
+def _gemm_table():
+    from test_workspace_cpu import GEMM_TABLE
+
+    return GEMM_TABLE
+
+
+@pytest.mark.parametrize("name", list(_gemm_table()))
+def test_gemm_exact_claim_is_sufficient(dev, name):
+    kw, need, symbol = _gemm_table()[name]
+    exact, large = gemm_on_exact_workspace(dev, kw, need)
+    assert _cabi_lib().vit_last_gemm_kernel().decode() == symbol
+    for out in ("C", "colsum_out", "aux_out"):
+        if out in exact:
+            assert not untouched(exact[out]), out
+            assert torch.equal(exact[out], large[out]), (name, out)
+
+
+def _cabi_lib():
+    from vit_amd import _cabi
+
+    return _cabi.load()
+
+
+# accumulate with colsum_out under grad_accumulate: the stages' front (split-K slabs: 4 x 128 x 128 x 4 bytes on the generic core,
+# 8 x 256 x 256 x 4 on the ping-pong core; vit_colsum's partials are smaller) and the M x N scratch matrix behind it
+@pytest.mark.parametrize("M,N,K,need", [(128, 128, 1024, 4 * 65536 + 65536), (256, 256, 4096, 8 * 262144 + 262144)])
+def test_gemm_scratch_route_on_its_exact_claim_adds_once(dev, M, N, K, need):
+    kw = dict(M=M, N=N, K=K, a_trans=1, b_trans=1, split_k=-1, colsum=True)
+    exact, large = gemm_on_exact_workspace(dev, kw, need, grad_accumulate=1)  # refused once, then repeated
+    new, _ = gemm_on_exact_workspace(dev, kw, need - M * N * 4)  # overwrite mode: `new` itself, no scratch matrix
+    for out in ("C", "colsum_out"):
+        assert torch.equal(exact[out], large[out]), out
+        assert torch.equal(exact[out], SENTINEL + new[out]), out  # old + new, one f32 add

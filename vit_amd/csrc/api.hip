@@ -11,7 +11,6 @@ struct vit_ctx {
   int device;
   void* ws;
   size_t ws_bytes;
-  size_t ws_hidden;        // bytes at the end of the workspace lent out by ctx_reserve_tail (not counted in ws_bytes)
   const void* step_state;  // device memory: vit::StepState, or NULL (vit_step_state_bind)
   int num_cus;             // compute units of the device (read once in vit_create): grid size of the persistent kernels
   int reserve_cus;         // vit_handle_set_option("reserve_cus"): -1 = the process default (vit_set_option), else this handle's own
@@ -24,7 +23,7 @@ extern int g_gemm2_mode;  // gemm2.hip
 extern int g_attn_split, g_attn_bwd_fused;  // attention.hip
 
 static thread_local char g_err[512] = "";
-thread_local char g_last_gemm[96] = "";  // symbol of the kernel the last vit_gemm on this thread launched
+thread_local char g_last_gemm[96] = "";  // symbol of the kernel of the last vit_gemm planned on this thread (gemm_launch)
 
 void set_error(const char* fmt, ...) {
   va_list ap;
@@ -56,22 +55,6 @@ int ctx_num_cus(vit_handle h) {
 }
 
 int ctx_grad_accumulate(vit_handle h) { return h ? h->grad_accumulate : 0; }
-
-// Take at least `bytes` off the END of the handle's workspace for the caller (256-byte aligned start) and hide them from
-// ctx_claim until ctx_release_tail gives them back: a scratch region that the kernels launched in between (which size
-// their own partials from the front of the workspace) cannot overlap.  Host-side bookkeeping only; NULL when the workspace
-// is too small.  One reservation at a time.
-void* ctx_reserve_tail(vit_handle h, size_t bytes) {
-  if (!h || !h->ws || h->ws_hidden || h->ws_bytes < bytes) return nullptr;
-  const size_t keep = (h->ws_bytes - bytes) & ~(size_t)255;
-  h->ws_hidden = h->ws_bytes - keep;
-  h->ws_bytes = keep;
-  return (char*)h->ws + keep;
-}
-void ctx_release_tail(vit_handle h) {
-  h->ws_bytes += h->ws_hidden;
-  h->ws_hidden = 0;
-}
 
 static thread_local size_t g_ws_needed = 0;  // vit_workspace_needed()
 void* ctx_claim(vit_handle h, size_t need_bytes, const char* who) {
@@ -105,7 +88,6 @@ int vit_create(vit_handle* out, int device) {
   c->device = device;
   c->ws = nullptr;
   c->ws_bytes = 0;
-  c->ws_hidden = 0;
   c->step_state = nullptr;
   c->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
   c->reserve_cus = -1;
@@ -179,7 +161,6 @@ int vit_set_workspace(vit_handle h, void* ws, size_t bytes) {
   VIT_CHECK(((uintptr_t)ws & 255) == 0, VIT_ERR_ARG, "vit_set_workspace: workspace must be 256-byte aligned");
   h->ws = ws;
   h->ws_bytes = bytes;
-  h->ws_hidden = 0;
   return VIT_OK;
 }
 

@@ -323,4 +323,59 @@ int launch_reduce_partials(const float* part, int nblk, int width, float* out0, 
                            hipStream_t st, int stride = 0 /* floats between partial rows; 0 = width */, int split2 = 0,
                            float* out2 = nullptr);
 
+// ---- vit_gemm: everything one call does, as data.  gemm_plan (gemm.hip) builds it from (handle, descriptor, KRows) -- every
+// argument check, the core, the epilogue, the K slices, the grid, who sums the columns, who rotates, the workspace -- and
+// gemm_launch then claims `need` once and launches by it; nothing below decides anything again.
+// compact K rows of an x3 weight-gradient product (GemmArgs::krs / krs_rows); stride 0 = the descriptor's rows as they are
+struct KRows { int stride, rows; };
+enum GemmCore { GEMM_PP, GEMM_BF16, GEMM_X3 };        // ping-pong 256x256x64 (gemm2.hip); generic 128x128 bf16 / x3 (gemm.hip)
+enum GemmPass { PASS_NONE, PASS_FUSED, PASS_BEHIND };  // in the core's epilogue, or a kernel of its own behind the product
+struct GemmPlan {
+  int core;                     // GemmCore
+  int a_t, b_t, epi;            // the kernel's template arguments (epi: ping-pong core only)
+  int splits, k_per_split;
+  int tiles_m, tiles_n;
+  dim3 grid;
+  int nblk, lin_split, grp2;    // ping-pong core: Gemm2Args' fields of these names
+  int colsum;                   // GemmPass: PASS_FUSED = epilogue partials + reduce_partials, PASS_BEHIND = vit_colsum on C
+  int rope;                     // GemmPass: PASS_FUSED = the rotating epilogue, PASS_BEHIND = vit_rope_qk on C
+  int accumulate;               // the core's own C store adds: the descriptor's flag OR the handle's "grad_accumulate" for the
+                                // weight-gradient form; 0 on the scratch route, whose add_into pass adds instead
+  int grad_accumulate;          // the handle's option: colsum_out stores old + new
+  int scratch;                  // accumulate with colsum_out: the product goes to a scratch matrix in the workspace first
+  DropCfg drop;
+  int drs;
+  KRows kr;
+  // workspace: the stages use its front one after another (split-K slabs, then the column sums' partials of either route);
+  // the scratch matrix lies behind them at scratch_off.  need = the whole call's claim, 0 = none.
+  size_t slab_bytes, colsum_bytes, scratch_off, need;
+  char* ws;                     // the claimed base (gemm_launch)
+  char symbol[96];              // vit_last_gemm_kernel()
+};
+int gemm_plan(vit_handle h, const vit_gemm_desc* d, KRows kr, GemmPlan* pl);   // gemm.hip
+bool pp_plan(vit_handle h, const vit_gemm_desc* d, GemmPlan* pl);              // gemm2.hip: the ping-pong core's part of it
+int pp_launch(const GemmPlan& pl, const vit_gemm_desc* d, hipStream_t st);
+// vit_gemm (gemm.hip): plan, claim, launch.  k_row_stride > 1: the K rows are compact (KRows), k_rows of them
+int gemm_launch(vit_handle h, const vit_gemm_desc* d, hipStream_t st, int k_row_stride = 0, int k_rows = 0);
+
+// the operand fields GemmArgs and Gemm2Args share
+template <class Args>
+static inline void fill_gemm_args(Args& a, const GemmPlan& pl, const vit_gemm_desc* d) {
+  a.A = (const char*)d->A; a.B = (const char*)d->B; a.C = (char*)d->C;
+  a.lda = d->lda; a.ldb = d->ldb; a.ldc = d->ldc;
+  a.M = d->M; a.N = d->N; a.K = d->K;
+  a.tiles_m = pl.tiles_m; a.tiles_n = pl.tiles_n;
+  a.splits = pl.splits; a.k_per_split = pl.k_per_split;
+  a.slab = pl.splits > 1 ? (float*)pl.ws : nullptr;
+  a.bias = d->bias;
+  a.aux_in = (const short*)d->aux_in; a.aux_out = (short*)d->aux_out; a.ldaux = d->ldaux;
+  a.residual = d->residual; a.ldres = d->ldres;
+  if (pl.accumulate && pl.splits == 1) { a.residual = (const float*)d->C; a.ldres = d->ldc; }  // C += through the residual port
+  a.alpha = d->alpha;
+  a.act = d->act; a.c_dtype = d->c_dtype;
+  a.drop = pl.drop;
+  a.rpb = d->rows_per_batch; a.orb = d->out_batch_rows; a.roff = d->out_row_offset;
+  a.drs = pl.drs;
+}
+
 }  // namespace vit

@@ -19,6 +19,7 @@
 // columns n of one row m: bias/aux/residual loads and the C store are 8/16-byte vectors.
 #include <algorithm>
 #include <stdio.h>
+#include <string.h>
 
 #include "common.h"
 
@@ -485,7 +486,7 @@ __global__ void splitk_reduce_kernel(const float* __restrict__ slab, float* __re
   }
 }
 
-// C[M, N] (ld = ldc) += src[M, N] (dense): the second half of gemm_accumulate_with_colsum below
+// C[M, N] (ld = ldc) += src[M, N] (dense): the last pass of gemm_launch's scratch route below
 __global__ void add_into_kernel(float* __restrict__ C, long ldc, const float* __restrict__ src, int M, int N) {
   const long nvec = (long)M * (N >> 2);
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < nvec; i += (long)gridDim.x * blockDim.x) {
@@ -495,11 +496,6 @@ __global__ void add_into_kernel(float* __restrict__ C, long ldc, const float* __
     *(f32x4*)c = *(const f32x4*)c + *(const f32x4*)(src + m * N + n);
   }
 }
-
-void* ctx_reserve_tail(vit_handle h, size_t bytes);   // api.hip
-void ctx_release_tail(vit_handle h);
-int gemm2_try_launch(vit_handle h, const vit_gemm_desc* d, hipStream_t st, int* rc);  // gemm2.hip
-bool gemm2_ws_bytes(vit_handle h, const vit_gemm_desc* d, size_t* bytes);
 
 int launch_splitk_reduce(const float* slab, float* C, long ldc, int M, int N, int splits, float alpha, int accumulate,
                          hipStream_t st) {
@@ -511,38 +507,7 @@ int launch_splitk_reduce(const float* slab, float* C, long ldc, int M, int N, in
 }
 
 static bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-thread_local int g_colsum_fused = 0;  // set by a core whose epilogue produced d->colsum_out itself
-thread_local int g_rope_fused = 0;    // set by a core whose epilogue applied d->rope_* itself
-// compact K rows of an x3 weight-gradient product (GemmArgs::krs / krs_rows); stride 0 = the descriptor's rows as they are
-struct KRows { int stride, rows; };
-int gemm_launch(vit_handle h, const vit_gemm_desc* d, hipStream_t st, int k_row_stride = 0, int k_rows = 0);
-static int gemm_launch_core(vit_handle h, const vit_gemm_desc* d, hipStream_t st, KRows kr = {0, 0});
-
 static size_t round256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
-
-// grad_accumulate with BOTH outputs of one descriptor being parameter gradients (an f32 C that accumulates and colsum_out):
-// the column sums are those of the NEW product, which an accumulated C no longer holds.  The product goes to a scratch matrix
-// at the end of the workspace in overwrite mode (the same kernels as a plain call: `new` bit for bit), its column sums are
-// added into colsum_out, and one pass adds it into C.  The engine never issues this combination (its weight-gradient products
-// carry no column sums), so no weight matrix of a training step takes the extra pass.  The scratch matrix is what such a call
-// needs on top of its stages' workspace (gemm_launch claims both).
-static size_t accum_scratch_bytes(const vit_gemm_desc* d) { return round256((size_t)d->M * d->N * sizeof(float)); }
-static int gemm_accumulate_with_colsum(vit_handle h, const vit_gemm_desc* d, hipStream_t st) {
-  float* scr = (float*)ctx_reserve_tail(h, accum_scratch_bytes(d));  // gemm_launch claimed it on top of the stages' need
-  VIT_CHECK(scr, VIT_ERR_WORKSPACE, "vit_gemm: the workspace's tail is already lent out");
-  vit_gemm_desc t = *d;
-  t.C = scr; t.ldc = d->N; t.accumulate = 0; t.colsum_out = nullptr;
-  int rc = gemm_launch_core(h, &t, st);
-  if (rc == VIT_OK) rc = vit_colsum(h, scr, VIT_F32, d->N, d->colsum_out, d->M, d->N, 1, (vit_stream)st);
-  ctx_release_tail(h);
-  if (rc != VIT_OK) return rc;
-  const long nvec = (long)d->M * (d->N / 4);
-  hipLaunchKernelGGL(add_into_kernel, dim3((int)std::min<long>((nvec + 255) / 256, 2048)), dim3(256), 0, st, (float*)d->C,
-                     (long)d->ldc, scr, d->M, d->N);
-  VIT_LAUNCH_CHECK();
-  return VIT_OK;
-}
 
 // K slices of a product on the generic core (bk: rows of a K tile): how many, and rows per slice
 static void split_plan(const vit_gemm_desc* d, int bk, int* splits_out, int* kps_out) {
@@ -558,20 +523,6 @@ static void split_plan(const vit_gemm_desc* d, int bk, int* splits_out, int* kps
   const int kps = cdiv(ktiles, splits) * bk;
   *splits_out = cdiv(d->K, kps);
   *kps_out = kps;
-}
-
-// Workspace bytes of one (checked) product, the maximum over its stages: the split-K slabs of the core that runs it, by the plan
-// that core launches by, and for colsum_out the fused partials or the vit_colsum pass (both: the choice is the core's).
-static size_t gemm_ws_bytes(vit_handle h, const vit_gemm_desc* d) {
-  size_t need = 0;
-  const bool f32in = d->ab_dtype == VIT_F32;
-  if (f32in || !gemm2_ws_bytes(h, d, &need)) {
-    int splits, kps;
-    split_plan(d, f32in ? XBK : BK, &splits, &kps);
-    if (splits > 1) need = (size_t)splits * d->M * d->N * sizeof(float);
-  }
-  if (d->colsum_out) need = std::max(need, colsum_ws_bytes(d->M, d->N));
-  return need;
 }
 
 static int gemm_check_args(const vit_gemm_desc* d, KRows kr) {
@@ -610,26 +561,27 @@ static int gemm_check_args(const vit_gemm_desc* d, KRows kr) {
   return VIT_OK;
 }
 
-int gemm_launch(vit_handle h, const vit_gemm_desc* d, hipStream_t st, int k_row_stride, int k_rows) {
-  g_colsum_fused = 0;
-  g_rope_fused = 0;
-  const KRows kr = {k_row_stride, k_rows};
+// The plan of one vit_gemm (GemmPlan, common.h).  Every VIT_ERR_ARG of the call is raised here, before anything is claimed.
+int gemm_plan(vit_handle h, const vit_gemm_desc* d, KRows kr, GemmPlan* pl) {
   int rc = gemm_check_args(d, kr);
   if (rc != VIT_OK) return rc;
   // vit_handle_set_option("grad_accumulate"): colsum_out is always a parameter gradient (a bias gradient); C is one iff the
   // product has the weight-gradient form dW = dY^T X (a_trans, f32 C) -- a forward product or a dX of the fp32 path also has
   // an f32 C, and activation gradients never accumulate.  OR-ed with the descriptor's own `accumulate`.
   const int accum = ctx_grad_accumulate(h);
-  vit_gemm_desc dd;
-  if (accum && d->a_trans && d->c_dtype == VIT_F32 && !d->accumulate) {
-    dd = *d;
-    dd.accumulate = 1;
-    d = &dd;
-  }
-  const bool scratch = accum && d->accumulate && d->colsum_out;
-  if (scratch)
+  vit_gemm_desc e = *d;  // the product the core runs
+  e.accumulate = d->accumulate || (accum && d->a_trans && d->c_dtype == VIT_F32);
+  // grad_accumulate with BOTH outputs of one descriptor being parameter gradients (an f32 C that accumulates and colsum_out):
+  // the column sums are those of the NEW product, which an accumulated C no longer holds.  The product goes to a scratch matrix
+  // behind the stages' workspace in overwrite mode (the same kernels as a plain call: `new` bit for bit), vit_colsum adds its
+  // column sums into colsum_out, and one pass adds it into C.  The engine never issues this combination (its weight-gradient
+  // products carry no column sums), so no weight matrix of a training step takes the extra pass.
+  const bool scratch = accum && e.accumulate && d->colsum_out;
+  if (scratch) {
     VIT_CHECK(d->c_dtype == VIT_F32 && d->rows_per_batch == 0 && !d->rope_cos && !d->residual, VIT_ERR_ARG,
               "vit_gemm: accumulate with colsum_out needs an f32 C and no row map, rope or residual");
+    e.ldc = d->N; e.accumulate = 0; e.colsum_out = nullptr;
+  }
   if (d->colsum_out) VIT_CHECK(d->rows_per_batch == 0, VIT_ERR_ARG, "vit_gemm: colsum_out with a row map is not supported");
   if (d->rope_cos) {
     VIT_CHECK(d->rope_sin && d->rope_T > 0 && d->rope_dh >= 8 && (d->rope_dh % 8) == 0 && d->rope_cols > 0 &&
@@ -639,66 +591,55 @@ int gemm_launch(vit_handle h, const vit_gemm_desc* d, hipStream_t st, int k_row_
                            "projection (a bias is fine) without dropout, row map, column sums, residual or split-K: the pass "
                            "behind a dropped-out product would rotate AFTER the dropout, which is not the reference's order");
   }
-  // the whole call's workspace before its first launch: a call that returns VIT_ERR_WORKSPACE has written nothing
-  size_t need = gemm_ws_bytes(h, d);
-  if (scratch) need = round256(need) + accum_scratch_bytes(d);
-  if (need && !ctx_claim(h, need, "vit_gemm")) return VIT_ERR_WORKSPACE;
-  if (scratch) return gemm_accumulate_with_colsum(h, d, st);
-  rc = gemm_launch_core(h, d, st, kr);
-  if (rc == VIT_OK && d->rope_cos && !g_rope_fused)  // the core had no rotating epilogue for this shape: the separate pass
-    rc = vit_rope_qk(h, d->C, d->c_dtype, d->rope_cos, d->rope_sin, d->M, d->rope_T, d->rope_cols / (2 * d->rope_dh), d->rope_dh,
-                     d->ldc, 0, (vit_stream)st);
-  if (rc != VIT_OK || !d->colsum_out || g_colsum_fused) return rc;
-  return vit_colsum(h, d->C, d->c_dtype, d->ldc, d->colsum_out, d->M, d->N, accum, (vit_stream)st);
+  *pl = GemmPlan{};
+  pl->accumulate = e.accumulate;
+  pl->grad_accumulate = accum;
+  pl->scratch = scratch;
+  pl->kr = kr;
+  pl->drop = make_drop_h(h, d->dropout_p, d->seed, d->site);
+  pl->drs = (pl->drop.thr && d->drop_row_stride > 1) ? d->drop_row_stride : 1;
+  const bool f32in = d->ab_dtype == VIT_F32;
+  if (f32in || !pp_plan(h, &e, pl)) {  // tile-aligned bf16 problems go to the LDS-DMA / persistent core
+    pl->core = f32in ? GEMM_X3 : GEMM_BF16;
+    pl->a_t = d->a_trans; pl->b_t = d->b_trans;
+    pl->tiles_m = cdiv(d->M, BM); pl->tiles_n = cdiv(d->N, BN);
+    split_plan(d, f32in ? XBK : BK, &pl->splits, &pl->k_per_split);
+    if (pl->splits > 1)
+      VIT_CHECK(d->c_dtype == VIT_F32 && !d->bias && d->act == VIT_ACT_NONE && d->dropout_p == 0.f && !d->residual &&
+                    d->rows_per_batch == 0,
+                VIT_ERR_ARG, "vit_gemm: split_k supports only alpha and an f32 C");
+    if (e.accumulate && pl->splits == 1)  // C += result through the residual port of the epilogue
+      VIT_CHECK(d->c_dtype == VIT_F32 && !d->residual && d->rows_per_batch == 0, VIT_ERR_ARG,
+                "vit_gemm: accumulate needs an f32 C and no residual");
+    pl->grid = dim3(pl->tiles_m * pl->tiles_n, pl->splits);
+    if (d->colsum_out) pl->colsum = PASS_BEHIND;
+    if (d->rope_cos) pl->rope = PASS_BEHIND;
+    snprintf(pl->symbol, sizeof(pl->symbol), "%s<%d, %d>", f32in ? "gemm_f32x3_kernel" : "gemm_bf16_kernel", d->a_trans,
+             d->b_trans);
+  }
+  if (scratch) pl->colsum = PASS_BEHIND;  // of the scratch matrix
+  if (pl->splits > 1) pl->slab_bytes = (size_t)pl->splits * d->M * d->N * sizeof(float);
+  if (pl->colsum == PASS_BEHIND) pl->colsum_bytes = colsum_ws_bytes(d->M, d->N);  // what vit_colsum claims
+  pl->need = std::max(pl->slab_bytes, pl->colsum_bytes);
+  if (scratch) {
+    pl->scratch_off = round256(pl->need);
+    pl->need = pl->scratch_off + round256((size_t)d->M * d->N * sizeof(float));
+  }
+  return VIT_OK;
 }
 
-static int gemm_launch_core(vit_handle h, const vit_gemm_desc* d, hipStream_t st, KRows kr) {
-  const bool f32in = d->ab_dtype == VIT_F32;
-  if (!f32in) {
-    int rc2 = VIT_OK;  // tile-aligned problems go to the LDS-DMA / persistent core
-    if (gemm2_try_launch(h, d, st, &rc2)) return rc2;
-  }
-
+static int generic_launch(const GemmPlan& pl, const vit_gemm_desc* d, hipStream_t st) {
   GemmArgs a;
-  a.A = (const char*)d->A; a.B = (const char*)d->B; a.C = (char*)d->C;
-  a.lda = d->lda; a.ldb = d->ldb; a.ldc = d->ldc;
+  fill_gemm_args(a, pl, d);
   a.a_bs = a.b_bs = a.c_bs = 0;
-  a.M = d->M; a.N = d->N; a.K = d->K;
-  a.tiles_m = cdiv(d->M, BM); a.tiles_n = cdiv(d->N, BN);
-  int splits, kps;
-  split_plan(d, f32in ? XBK : BK, &splits, &kps);
-  a.splits = splits; a.k_per_split = kps;
-  a.slab = nullptr;
-  if (splits > 1) {
-    VIT_CHECK(d->c_dtype == VIT_F32 && !d->bias && d->act == VIT_ACT_NONE && d->dropout_p == 0.f && !d->residual &&
-                  d->rows_per_batch == 0,
-              VIT_ERR_ARG, "vit_gemm: split_k supports only alpha and an f32 C");
-    if (!(a.slab = (float*)ctx_claim(h, (size_t)splits * d->M * d->N * sizeof(float), "vit_gemm: split-K"))) return VIT_ERR_WORKSPACE;
-  }
-  a.bias = d->bias;
-  a.aux_in = (const short*)d->aux_in; a.aux_out = (short*)d->aux_out; a.ldaux = d->ldaux;
-  a.residual = d->residual; a.ldres = d->ldres;
-  if (d->accumulate && splits == 1) {  // C += result through the residual port of the epilogue
-    VIT_CHECK(d->c_dtype == VIT_F32 && !d->residual && d->rows_per_batch == 0, VIT_ERR_ARG,
-              "vit_gemm: accumulate needs an f32 C and no residual");
-    a.residual = (const float*)d->C; a.ldres = d->ldc;
-  }
-  a.alpha = d->alpha;
-  a.act = d->act; a.c_dtype = d->c_dtype;
-  a.drop = make_drop_h(h, d->dropout_p, d->seed, d->site);
-  a.rpb = d->rows_per_batch; a.orb = d->out_batch_rows; a.roff = d->out_row_offset;
-  a.drs = (a.drop.thr && d->drop_row_stride > 1) ? d->drop_row_stride : 1;
   a.krs = a.krs_rows = 0;
-  if (kr.stride > 1) {
-    a.krs = kr.stride;
-    a.krs_rows = kr.rows;
+  if (pl.kr.stride > 1) {
+    a.krs = pl.kr.stride;
+    a.krs_rows = pl.kr.rows;
   }
-
-  dim3 grid(a.tiles_m * a.tiles_n, splits), block(NTHR);
-  const int v = d->a_trans * 2 + d->b_trans;
-  snprintf(g_last_gemm, sizeof(g_last_gemm), "%s<%d, %d>", f32in ? "gemm_f32x3_kernel" : "gemm_bf16_kernel", d->a_trans,
-           d->b_trans);
-  if (f32in) {
+  const dim3 grid = pl.grid, block(NTHR);
+  const int v = pl.a_t * 2 + pl.b_t;
+  if (pl.core == GEMM_X3) {
     switch (v) {
       case 0: hipLaunchKernelGGL((gemm_f32x3_kernel<0, 0>), grid, block, 0, st, a); break;
       case 1: hipLaunchKernelGGL((gemm_f32x3_kernel<0, 1>), grid, block, 0, st, a); break;
@@ -713,8 +654,38 @@ static int gemm_launch_core(vit_handle h, const vit_gemm_desc* d, hipStream_t st
     default: hipLaunchKernelGGL((gemm_bf16_kernel<1, 1>), grid, block, 0, st, a); break;
   }
   VIT_LAUNCH_CHECK();
-  if (splits > 1)
-    return launch_splitk_reduce(a.slab, (float*)d->C, (long)d->ldc, d->M, d->N, splits, d->alpha, d->accumulate, st);
+  if (pl.splits > 1)
+    return launch_splitk_reduce(a.slab, (float*)d->C, (long)d->ldc, d->M, d->N, pl.splits, d->alpha, pl.accumulate, st);
+  return VIT_OK;
+}
+
+// plan -> one claim of the whole call's workspace before its first launch (a call that returns VIT_ERR_WORKSPACE has written
+// nothing) -> launch by the plan
+int gemm_launch(vit_handle h, const vit_gemm_desc* d, hipStream_t st, int k_row_stride, int k_rows) {
+  GemmPlan pl;
+  int rc = gemm_plan(h, d, KRows{k_row_stride, k_rows}, &pl);
+  if (rc != VIT_OK) return rc;
+  memcpy(g_last_gemm, pl.symbol, sizeof(g_last_gemm));
+  if (pl.need && !(pl.ws = (char*)ctx_claim(h, pl.need, "vit_gemm"))) return VIT_ERR_WORKSPACE;
+  float* const c_out = (float*)d->C;
+  const long ldc_out = d->ldc;
+  vit_gemm_desc t;
+  if (pl.scratch) {  // the product and its column sums from the scratch matrix; the last pass adds it into C
+    t = *d;
+    t.C = pl.ws + pl.scratch_off; t.ldc = d->N;
+    d = &t;
+  }
+  rc = pl.core == GEMM_PP ? pp_launch(pl, d, st) : generic_launch(pl, d, st);
+  if (rc == VIT_OK && pl.rope == PASS_BEHIND)  // the core had no rotating epilogue for this shape: the separate pass
+    rc = vit_rope_qk(h, d->C, d->c_dtype, d->rope_cos, d->rope_sin, d->M, d->rope_T, d->rope_cols / (2 * d->rope_dh), d->rope_dh,
+                     d->ldc, 0, (vit_stream)st);
+  if (rc == VIT_OK && pl.colsum == PASS_BEHIND)
+    rc = vit_colsum(h, d->C, d->c_dtype, d->ldc, d->colsum_out, d->M, d->N, pl.grad_accumulate, (vit_stream)st);
+  if (rc != VIT_OK || !pl.scratch) return rc;
+  const long nvec = (long)d->M * (d->N / 4);
+  hipLaunchKernelGGL(add_into_kernel, dim3((int)std::min<long>((nvec + 255) / 256, 2048)), dim3(256), 0, st, c_out, ldc_out,
+                     (const float*)d->C, d->M, d->N);
+  VIT_LAUNCH_CHECK();
   return VIT_OK;
 }
 

@@ -14,7 +14,7 @@
 //     loads of the next tile's first K-tiles are already in flight during the current tile's epilogue;
 //   * XCD-aware tile order inside each round of concurrently running tiles (neighbours in n share the A panel in L2);
 //   * one launch of just enough workgroups for ceil(tiles / CUs) rounds, a partial last round included: the step is
-//     power-limited, and the idle CUs' budget goes to the busy ones' clock (gemm2_try_launch);
+//     power-limited, and the idle CUs' budget goes to the busy ones' clock (pp_plan);
 //   * epilogue through a per-wave LDS transpose (the 32 KiB the ring leaves free): accumulators go to LDS in MFMA layout and
 //     come back row-major, so every bias / aux / residual load and every output store of a wave-instruction covers whole
 //     128- or 256-byte row segments instead of 16 rows x 32 bytes.
@@ -734,7 +734,6 @@ static int launch_stag_cfg(const Gemm2Args& a, int at, int bt, int epi, dim3 gri
   return launch_stag<1, 1, 0>(a, grid, st);
 }
 
-extern thread_local int g_colsum_fused, g_rope_fused;  // gemm.hip
 int g_gemm2_mode = 1;  // vit_set_option("gemm_core"): 0 = generic 128x128 core only, else the ping-pong kernel where eligible
 
 // K slices of a ping-pong product of `ntile` tiles: how many, and rows per slice (split_k as in vit_gemm_desc)
@@ -752,8 +751,8 @@ static void pp_split_plan(int slots, int ntile, int K, int split_k, int* splits_
   *kps_out = kps;
 }
 
-// Does a bf16 product of this shape run the ping-pong core?  The ONE statement of that rule: gemm2_try_launch asks it, and so
-// does vit_linear_bwd_dw_rows, which must know whether the full-size product it stands in for would have.
+// Does a bf16 product of this shape run the ping-pong core?  The ONE statement of that rule: pp_plan asks it, and so does
+// vit_colsum_rows, which must know whether the product that writes the full-size tensor would have.
 static bool pp_shape_ok(long M, long N, long K, long lda, long ldb) {
   if (g_gemm2_mode == 0) return false;
   if (M % 256 || N % 256 || K % 64) return false;  // other shapes stay on the register-staged 128x128 core
@@ -761,9 +760,10 @@ static bool pp_shape_ok(long M, long N, long K, long lda, long ldb) {
   return true;
 }
 
-// Does the ping-pong core run this (checked, bf16) product -- the generic core does otherwise -- and if so with which generic
-// epilogue and which K slices?  gemm2_try_launch launches by the answer; gemm2_ws_bytes sizes the workspace by it beforehand.
-static bool pp_plan(vit_handle h, const vit_gemm_desc* d, int* epi_out, int* splits_out, int* kps_out) {
+// The ping-pong core's part of gemm_plan (gemm.hip; d is checked, bf16, and carries the effective `accumulate`; pl->drop and
+// pl->drs are set): false = the generic core runs d, and *pl is as it was.  Else the epilogue, the K slices, the walk, who sums
+// the columns and who rotates.
+bool pp_plan(vit_handle h, const vit_gemm_desc* d, GemmPlan* pl) {
   if (!pp_shape_ok(d->M, d->N, d->K, d->lda, d->ldb)) return false;
   int epi = 0;
   if (d->act == VIT_ACT_GELU || d->act == VIT_ACT_GELU_GRAD) {
@@ -773,75 +773,36 @@ static bool pp_plan(vit_handle h, const vit_gemm_desc* d, int* epi_out, int* spl
     if (d->a_trans || !d->b_trans) return false;
     epi = 2;
   }
+  const int slots = ctx_num_cus(h);  // one workgroup per CU
+  const int tiles_m = d->M / 256, tiles_n = d->N / 256, ntile = tiles_m * tiles_n;
   int splits, kps;
-  pp_split_plan(ctx_num_cus(h), (d->M / 256) * (d->N / 256), d->K, d->split_k, &splits, &kps);
+  pp_split_plan(slots, ntile, d->K, d->split_k, &splits, &kps);
   if (splits > 1 && !(d->c_dtype == VIT_F32 && !d->bias && d->act == VIT_ACT_NONE && d->dropout_p == 0.f && !d->residual &&
                       d->rows_per_batch == 0)) return false;
   if (d->accumulate && splits == 1 && !(d->c_dtype == VIT_F32 && !d->residual && d->rows_per_batch == 0)) return false;
-  *epi_out = epi; *splits_out = splits; *kps_out = kps;
-  return true;
-}
-// the column-sum partials of the epilogues that sum their own rows: two rows per tile row (one per 128-row wave block)
-static size_t pp_colsum_bytes(const vit_gemm_desc* d) { return (size_t)(d->M / 256) * 2 * d->N * sizeof(float); }
 
-// false: the generic core runs d.  Else the workspace bytes of the product here: its split-K slabs and, given colsum_out, the
-// partials above (claimed whichever epilogue is then chosen).
-bool gemm2_ws_bytes(vit_handle h, const vit_gemm_desc* d, size_t* bytes) {
-  int epi, splits, kps;
-  if (!pp_plan(h, d, &epi, &splits, &kps)) return false;
-  *bytes = splits > 1 ? (size_t)splits * d->M * d->N * sizeof(float) : 0;
-  if (d->colsum_out) *bytes = std::max(*bytes, pp_colsum_bytes(d));
-  return true;
-}
-
-// returns 1 if handled (rc in *rc), 0 if the shape is not eligible
-int gemm2_try_launch(vit_handle h, const vit_gemm_desc* d, hipStream_t st, int* rc) {
-  int epi, splits, kps;
-  if (!pp_plan(h, d, &epi, &splits, &kps)) return 0;
-  const int slots = ctx_num_cus(h);  // one workgroup per CU
-
-  Gemm2Args a;
-  a.A = (const char*)d->A; a.B = (const char*)d->B; a.C = (char*)d->C;
-  a.lda = d->lda; a.ldb = d->ldb; a.ldc = d->ldc;
-  a.M = d->M; a.N = d->N; a.K = d->K;
-  a.tiles_m = d->M / 256; a.tiles_n = d->N / 256;
-  const int ntile = a.tiles_m * a.tiles_n;
-  a.splits = splits; a.k_per_split = kps;
-  a.slab = nullptr;
-  *rc = VIT_ERR_WORKSPACE;  // what a refused claim below returns (gemm_launch has claimed the whole call's need already)
-  if (splits > 1 && !(a.slab = (float*)ctx_claim(h, (size_t)splits * d->M * d->N * sizeof(float), "vit_gemm: split-K"))) return 1;
-  a.nblk = std::min(ntile, slots);
-  a.bias = d->bias;
-  a.aux_in = (const short*)d->aux_in; a.aux_out = (short*)d->aux_out; a.ldaux = d->ldaux;
-  a.residual = d->residual; a.ldres = d->ldres;
-  if (d->accumulate && splits == 1) { a.residual = (const float*)d->C; a.ldres = d->ldc; }
-  a.alpha = d->alpha;
-  a.rope_cos = d->rope_cos; a.rope_sin = d->rope_sin; a.rope_T = d->rope_T; a.rope_dh = d->rope_dh; a.rope_cols = d->rope_cols;
-  a.act = d->act; a.c_dtype = d->c_dtype;
-  a.drop = make_drop_h(h, d->dropout_p, d->seed, d->site);
-  a.rpb = d->rows_per_batch; a.orb = d->out_batch_rows; a.roff = d->out_row_offset;
-  a.drs = (a.drop.thr && d->drop_row_stride > 1) ? d->drop_row_stride : 1;
-
-  dim3 grid(a.nblk, splits);
-  a.lin_split = 0;
-  a.colsum_part = nullptr;
-  if (splits > 1 && a.nblk == ntile) {
-    a.lin_split = 1;
+  int nblk = std::min(ntile, slots);
+  dim3 grid(nblk, splits);
+  int lin_split = 0;
+  if (splits > 1 && nblk == ntile) {
+    lin_split = 1;
     grid = dim3(ntile * splits, 1);
   }
   // the specialised epilogue when the descriptor is one of the five hot kinds
   int epi5 = epi;
-  const bool plain = !a.residual && a.rpb == 0 && a.drs == 1 && d->alpha == 1.0f;
-  if (epi == 1 && plain && a.bias && d->c_dtype == VIT_BF16 && !a.drop.thr && splits == 1) epi5 = 4;
-  else if (epi == 2 && plain && !a.bias && d->c_dtype == VIT_BF16 && !a.drop.thr && splits == 1) epi5 = 5;
+  const bool residual = d->residual || (d->accumulate && splits == 1);  // the residual port carries old C then
+  const unsigned drop_thr = pl->drop.thr;
+  const bool plain = !residual && d->rows_per_batch == 0 && pl->drs == 1 && d->alpha == 1.0f;
+  if (epi == 1 && plain && d->bias && d->c_dtype == VIT_BF16 && !drop_thr && splits == 1) epi5 = 4;
+  else if (epi == 2 && plain && !d->bias && d->c_dtype == VIT_BF16 && !drop_thr && splits == 1) epi5 = 5;
   else if (epi == 0 && plain && d->c_dtype == VIT_BF16 && !d->a_trans && !d->b_trans && splits == 1) epi5 = 3;
-  else if (epi == 0 && plain && !a.bias && !a.drop.thr && d->c_dtype == VIT_BF16 && !d->a_trans && d->b_trans &&
+  else if (epi == 0 && plain && !d->bias && !drop_thr && d->c_dtype == VIT_BF16 && !d->a_trans && d->b_trans &&
            splits == 1) epi5 = 6;
-  else if (epi == 0 && plain && !a.bias && !a.drop.thr && d->c_dtype == VIT_F32 && d->a_trans && d->b_trans) epi5 = 7;
-  // rotary embedding requested: the rotating epilogue where a wave's 64 columns are whole heads, else the caller (gemm_launch)
-  // runs the separate pass behind this launch
+  else if (epi == 0 && plain && !d->bias && !drop_thr && d->c_dtype == VIT_F32 && d->a_trans && d->b_trans) epi5 = 7;
+  // rotary embedding requested: the rotating epilogue where a wave's 64 columns are whole heads, else gemm_launch runs the
+  // separate pass behind this launch
   if (d->rope_cos) {
-    if (epi5 == 3 && !a.drop.thr && (d->rope_dh == 16 || d->rope_dh == 32 || d->rope_dh == 64) && (d->rope_cols % 64) == 0 &&
+    if (epi5 == 3 && !drop_thr && (d->rope_dh == 16 || d->rope_dh == 32 || d->rope_dh == 64) && (d->rope_cols % 64) == 0 &&
         d->rope_T >= 9)  // the epilogue steps its angles by table row 8
       epi5 = 8;
   }
@@ -858,33 +819,44 @@ int gemm2_try_launch(vit_handle h, const vit_gemm_desc* d, hipStream_t st, int* 
     // half tiles on twice as many workgroups shortened the product itself but cost 5 % more CU-time, and the step is
     // power-limited: with one launch every OTHER kernel of the step ran 1-3 % faster (ViT-B step -0.4 ms, ViT-L with its
     // second stream 53.6 -> 51.7 ms).
-    a.nblk = cdiv(ntile, cdiv(ntile, slots));
-    grid = dim3(a.nblk, splits);
+    nblk = cdiv(ntile, cdiv(ntile, slots));
+    grid = dim3(nblk, splits);
   }
-  a.grp2 = 0;
-  if (splits == 1 && (a.tiles_n % 2) == 0 && (size_t)d->N * d->K * 2 > (size_t)4 << 20 && ntile > slots && (ntile % 2) == 0) {
-    a.grp2 = 1;  // weights larger than an L2: two N-groups of XCDs (see tile_coords)
-    if (a.nblk & 1) {  // each round must split into two equal halves
-      a.nblk += 1;
-      grid = dim3(a.nblk, splits);
+  int grp2 = 0;
+  if (splits == 1 && (tiles_n % 2) == 0 && (size_t)d->N * d->K * 2 > (size_t)4 << 20 && ntile > slots && (ntile % 2) == 0) {
+    grp2 = 1;  // weights larger than an L2: two N-groups of XCDs (see tile_coords)
+    if (nblk & 1) {  // each round must split into two equal halves
+      nblk += 1;
+      grid = dim3(nblk, splits);
     }
   }
-  if (d->colsum_out && (epi5 == 3 || epi5 == 5 || epi5 == 6) &&
-      !(a.colsum_part = (float*)ctx_claim(h, pp_colsum_bytes(d), "vit_gemm: column sums"))) return 1;
-  {
-    const int at = epi ? 0 : d->a_trans, bt = epi == 1 ? 0 : (epi == 2 ? 1 : d->b_trans);
-    snprintf(g_last_gemm, sizeof(g_last_gemm), "gemm3_kernel<%d, %d, %d, %d>", at, bt, epi5, 8);
+  pl->core = GEMM_PP;
+  pl->a_t = d->a_trans; pl->b_t = d->b_trans; pl->epi = epi5;  // (epilogues 1 - 8 fix a_t / b_t: eligible only with those)
+  pl->splits = splits; pl->k_per_split = kps;
+  pl->tiles_m = tiles_m; pl->tiles_n = tiles_n;
+  pl->grid = grid; pl->nblk = nblk; pl->lin_split = lin_split; pl->grp2 = grp2;
+  if (d->colsum_out) {
+    // the epilogues that sum their own rows leave two partial rows per tile row (one per 128-row wave block)
+    pl->colsum = (epi5 == 3 || epi5 == 5 || epi5 == 6) ? PASS_FUSED : PASS_BEHIND;
+    if (pl->colsum == PASS_FUSED) pl->colsum_bytes = (size_t)tiles_m * 2 * d->N * sizeof(float);
   }
-  if (epi5 == 8) g_rope_fused = 1;
-  int r = launch_stag_cfg(a, d->a_trans, d->b_trans, epi5, grid, st);
-  if (r == VIT_OK && a.colsum_part) {
-    r = launch_reduce_partials(a.colsum_part, a.tiles_m * 2, d->N, d->colsum_out, d->N, d->colsum_out, ctx_grad_accumulate(h), st);
-    g_colsum_fused = 1;
-  }
-  if (r == VIT_OK && splits > 1)
-    r = launch_splitk_reduce(a.slab, (float*)d->C, (long)d->ldc, d->M, d->N, splits, d->alpha, d->accumulate, st);
-  *rc = r;
-  return 1;
+  if (d->rope_cos) pl->rope = epi5 == 8 ? PASS_FUSED : PASS_BEHIND;
+  snprintf(pl->symbol, sizeof(pl->symbol), "gemm3_kernel<%d, %d, %d, %d>", pl->a_t, pl->b_t, epi5, 8);
+  return true;
+}
+
+int pp_launch(const GemmPlan& pl, const vit_gemm_desc* d, hipStream_t st) {
+  Gemm2Args a;
+  fill_gemm_args(a, pl, d);
+  a.nblk = pl.nblk; a.lin_split = pl.lin_split; a.grp2 = pl.grp2;
+  a.colsum_part = pl.colsum == PASS_FUSED ? (float*)pl.ws : nullptr;
+  a.rope_cos = d->rope_cos; a.rope_sin = d->rope_sin; a.rope_T = d->rope_T; a.rope_dh = d->rope_dh; a.rope_cols = d->rope_cols;
+  int r = launch_stag_cfg(a, pl.a_t, pl.b_t, pl.epi, pl.grid, st);
+  if (r == VIT_OK && a.colsum_part)
+    r = launch_reduce_partials(a.colsum_part, a.tiles_m * 2, d->N, d->colsum_out, d->N, d->colsum_out, pl.grad_accumulate, st);
+  if (r == VIT_OK && pl.splits > 1)
+    r = launch_splitk_reduce(a.slab, (float*)d->C, (long)d->ldc, d->M, d->N, pl.splits, d->alpha, pl.accumulate, st);
+  return r;
 }
 
 
@@ -999,8 +971,6 @@ __global__ void colsum_rows_part_kernel(const short* __restrict__ a, long lda, f
   part[i] = v;
 }
 
-// gemm.hip; k_row_stride > 1: the K rows of an x3 weight-gradient product are compact (GemmArgs::krs), k_rows of them
-int gemm_launch(vit_handle h, const vit_gemm_desc* d, hipStream_t st, int k_row_stride = 0, int k_rows = 0);
 int colsum_strided(vit_handle h, const void* a, int a_dtype, int64_t lda, float* out, int rows, int cols, int64_t row_stride,
                    int held, int accumulate, hipStream_t st);          // elementwise.hip
 
@@ -1017,30 +987,28 @@ int vit_linear_bwd_dw_rows(vit_handle h, const void* dy, int64_t ldy, const void
             VIT_ERR_ARG, "vit_linear_bwd_dw_rows: rows=%d N=%d K=%d row_stride=%lld full_rows=%lld", rows, N, K,
             (long long)row_stride, (long long)full_rows);
   hipStream_t st = (hipStream_t)stream;
-  // the full product dW[N, K] = dY[full_rows, N]^T X[full_rows, K] (both operands transposed: ld = N and K) on the ping-pong
-  // core is what the order below restates; the kernel itself needs 16-byte rows
-  if (dtype == VIT_BF16 && pp_shape_ok(N, K, full_rows, N, K) && (ldy % 8) == 0 && (ldx % 8) == 0 &&
-      ((uintptr_t)dy % 16) == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)dW % 16) == 0) {
-    int splits, kps;
-    pp_split_plan(ctx_num_cus(h), (N / 256) * (K / 256), (int)full_rows, -1, &splits, &kps);
-    hipLaunchKernelGGL(dw_rows_kernel, dim3(N / 64, K / 64), dim3(256), 0, st, (const short*)dy, (long)ldy, (const short*)x,
-                       (long)ldx, dW, (long)K, rows, (int)row_stride, kps, splits, ctx_grad_accumulate(h));
-    VIT_LAUNCH_CHECK();
-    return VIT_OK;
+  // the full product dW[N, K] = dY[full_rows, N]^T X[full_rows, K] this call stands in for, its operands the compact ones
+  vit_gemm_desc d = {};
+  d.M = N; d.N = K; d.K = (int)full_rows; d.ab_dtype = dtype; d.a_trans = 1; d.b_trans = 1;
+  d.A = dy; d.lda = ldy; d.B = x; d.ldb = ldx; d.C = dW; d.ldc = K; d.c_dtype = VIT_F32; d.alpha = 1.f; d.split_k = -1;
+  if (dtype == VIT_BF16) {
+    GemmPlan pl;
+    const int rc = gemm_plan(h, &d, KRows{0, 0}, &pl);
+    if (rc != VIT_OK) return rc;
+    if (pl.core == GEMM_PP) {  // the ping-pong core would run it: its K slices are the order dw_rows_kernel restates
+      hipLaunchKernelGGL(dw_rows_kernel, dim3(N / 64, K / 64), dim3(256), 0, st, (const short*)dy, (long)ldy, (const short*)x,
+                         (long)ldx, dW, (long)K, rows, (int)row_stride, pl.k_per_split, pl.splits, ctx_grad_accumulate(h));
+      VIT_LAUNCH_CHECK();
+      return VIT_OK;
+    }
   }
   if (dtype == VIT_F32 && row_stride > 1 &&
-      (unsigned long long)rows * (unsigned long long)std::max(ldy, ldx) * 4 < 0x7FFFFFF0ull) {
+      (unsigned long long)rows * (unsigned long long)std::max(ldy, ldx) * 4 < 0x7FFFFFF0ull)
     // precision '32': the full product over full_rows rows on the x3 kernel with its own split-K plan, the K rows read from
     // the compact operands and every other row as zero (GemmArgs::krs): the full path's weight gradient bit for bit, at the
     // full product's MFMA time but none of its operand traffic
-    vit_gemm_desc d = {};
-    d.M = N; d.N = K; d.K = (int)full_rows; d.ab_dtype = VIT_F32; d.a_trans = 1; d.b_trans = 1;
-    d.A = dy; d.lda = ldy; d.B = x; d.ldb = ldx; d.C = dW; d.ldc = K; d.c_dtype = VIT_F32; d.alpha = 1.f; d.split_k = -1;
     return gemm_launch(h, &d, st, (int)row_stride, rows);
-  }
-  vit_gemm_desc d = {};  // any other shape: the compact product (the same sum, the GEMM core's own order)
-  d.M = N; d.N = K; d.K = rows; d.ab_dtype = dtype; d.a_trans = 1; d.b_trans = 1;
-  d.A = dy; d.lda = ldy; d.B = x; d.ldb = ldx; d.C = dW; d.ldc = K; d.c_dtype = VIT_F32; d.alpha = 1.f; d.split_k = 1;
+  d.K = rows; d.split_k = 1;  // any other shape: the compact product (the same sum, the GEMM core's own order)
   return gemm_launch(h, &d, st);
 }
 
