@@ -359,5 +359,8 @@ int vit_adamw_step(vit_handle h, float* p, const float* g, float* m, float* v, v
 /* The optimizer steps beside vit_adamw_step -- Adam with L2 decay and SGD, eager and captured (opt/optimizer.py:14-26,108;
  * `opt.type` in configs/config.yaml) -- are declared in their own header, part of this ABI. */
 #include "vit_amd_optim.h"
+/* The exponential moving average of the weights (`train.ema_decay`): vit_ema_update behind the optimizer step, vit_ema_swap
+ * around an evaluation.  Declared in their own header, part of this ABI. */
+#include "vit_amd_ema.h"
 
 #endif /* VIT_AMD_H_ */

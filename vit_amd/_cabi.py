@@ -106,6 +106,9 @@ _PROTOS = {
     "vit_sgd_step_groups": [_P, _P, _P, _P, _P, _I64, _I64, _P, _P, _I, _P, _I, _I, _P, _F, _P],
     "vit_sgd_step_groups_dyn": [_P, _P, _P, _P, _P, _I64, _I64, _P, _P, _I, _P, _I, _I, _P, _F, _P],
     "vit_optim_groups_write": [_P, _P, _I, C.POINTER(C.c_float), _P],
+    # (h, ema, p, n, weight, weight_dev, stream) / (h, p, ema, p_bf16, n, stream)
+    "vit_ema_update": [_P, _P, _P, _I64, _F, _P, _P],
+    "vit_ema_swap": [_P, _P, _P, _P, _I64, _P],
 }
 _RESTYPES = {"vit_last_error": C.c_char_p, "vit_last_gemm_kernel": C.c_char_p, "vit_workspace_needed": C.c_size_t}
 
@@ -114,7 +117,7 @@ _lock = threading.Lock()
 
 
 def declared_symbols(header_path: str = HEADER_PATH):
-    """Every function the C header declares, the headers it includes from its own directory (vit_amd_cov.h, vit_amd_optim.h) included (used by
+    """Every function the C header declares, the headers it includes from its own directory (vit_amd_cov.h, vit_amd_optim.h, vit_amd_ema.h) included (used by
     the CPU test that checks the library exports them all)."""
     seen, names, todo = set(), set(), [os.path.abspath(header_path)]
     while todo:

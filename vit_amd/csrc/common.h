@@ -53,6 +53,24 @@ __device__ __forceinline__ unsigned pack2bf(float lo, float hi) {
   return __builtin_bit_cast(unsigned, r);
 }
 
+// ---- what the streaming kernels over the flat f32 buffers share (optim.hip, ema.hip) ---------------------------------
+// Those files compile under `#pragma clang fp contract(off)`: a multiply-add that is fused is written as one of these.
+__device__ __forceinline__ float fma_(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+__device__ __forceinline__ f32x4 fma_(f32x4 a, float b, f32x4 c) {
+#pragma unroll
+  for (int k = 0; k < 4; ++k) c[k] = __builtin_fmaf(a[k], b, c[k]);
+  return c;
+}
+// the bf16 shadow of p beside p: one 16-byte vector of p is one 8-byte store (vit_cast_f32_bf16's rounding)
+__device__ __forceinline__ void store_shadow(short* __restrict__ pb, long at, f32x4 pp) {
+  u32x2 pk = {pack2bf(pp[0], pp[1]), pack2bf(pp[2], pp[3])};
+  *(u32x2*)(pb + at) = pk;
+}
+__device__ __forceinline__ void store_shadow(short* __restrict__ pb, long at, float pp) { pb[at] = f2bf(pp); }
+// Lanes per block of the step kernels, a compile-time number: read from blockDim the tile arithmetic of the grouped step starts
+// every wave with a vector load of the dispatch packet, a round trip behind the streaming loads of the waves already running.
+constexpr int STEP_BLOCK = 256;
+
 // ---- dropout: counter-based, stateless, identical in every kernel that needs the same mask -----------
 // Two levels.  Every ROW of a [rows, ncols] tensor has a 32-bit key, a full-strength hash of (seed keys, 64-bit row index):
 // drop_rowkey.  Inside the row, one 32-bit word per PAIR of adjacent columns, drop_bits(rowkey, col / 2): element (row, col)

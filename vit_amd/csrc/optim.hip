@@ -18,24 +18,11 @@
 
 namespace vit {
 
-__device__ __forceinline__ float fma_(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
-__device__ __forceinline__ f32x4 fma_(f32x4 a, float b, f32x4 c) {
-#pragma unroll
-  for (int k = 0; k < 4; ++k) c[k] = __builtin_fmaf(a[k], b, c[k]);
-  return c;
-}
-
 __device__ __forceinline__ float clip_coef(const float* __restrict__ sqnorm, float max_norm) {
   return sqnorm ? fminf(1.f, max_norm / (sqrtf(sqnorm[0]) + 1e-6f)) : 1.f;
 }
 
 // ---- the updates, stated once: T is f32x4 (the 16-byte body) or float (the n & 3 tail) ------------------------------------
-__device__ __forceinline__ void store_shadow(short* __restrict__ pb, long at, f32x4 pp) {
-  u32x2 pk = {pack2bf(pp[0], pp[1]), pack2bf(pp[2], pp[3])};
-  *(u32x2*)(pb + at) = pk;
-}
-__device__ __forceinline__ void store_shadow(short* __restrict__ pb, long at, float pp) { pb[at] = f2bf(pp); }
-
 __device__ __forceinline__ f32x4 adam_descend(f32x4 pp, f32x4 mm, f32x4 vv, float decay, float step, float rsqrt_bc2, float eps) {
 #pragma unroll
   for (int k = 0; k < 4; ++k) pp[k] = fma_(pp[k], decay, -(step * mm[k] / fma_(sqrtf(vv[k]), rsqrt_bc2, eps)));
@@ -99,9 +86,6 @@ __device__ __forceinline__ void sgd_update(float* __restrict__ p, const float* _
 // a boundary lets each lane walk on from the tile's first segment.  Offsets past the last end and group indices past the
 // table are clamped, so a malformed table cannot make the kernel read outside it.
 struct alignas(16) GroupRow { float lr, wd, mu, pad; };
-// Lanes per block of the step kernels, a compile-time number: read from blockDim the tile arithmetic below starts every wave
-// with a vector load of the dispatch packet, a round trip behind the streaming loads of the waves already running.
-constexpr int STEP_BLOCK = 256;
 
 __device__ __forceinline__ int seg_find(const long* __restrict__ seg_end, int n_seg, long off) {
   int lo = 0, hi = n_seg - 1;  // the first s with seg_end[s] > off, or the last segment

@@ -590,3 +590,34 @@ def sgd_step_groups(p, g, buf, p_bf16, tables: GroupTables, *, base=0, nesterov=
     n = p.numel() if n is None else n
     h.call("vit_sgd_step_groups_dyn" if dyn else "vit_sgd_step_groups", p.data_ptr(), g.data_ptr(), _ptr(buf), _ptr(p_bf16), n,
            *_groups_args(tables, base), int(bool(nesterov)), _ptr(sqnorm), max_norm, _stream(p))
+
+
+# ------------------------------------------------------------------------------------------------ weight averaging
+def ema_update(ema, p, weight: float = 0.0, *, weight_dev=None, n: Optional[int] = None):
+    """ema <- torch.lerp(ema, p, weight) over the first `n` elements (include/vit_amd_ema.h); `weight` is 1 - decay, already
+    subtracted (in double: a Python float).  `weight_dev` (inside a captured step): the weight is read from that device cell."""
+    _chk(ema, torch.float32, "ema_update ema")
+    _chk(p, torch.float32, "ema_update p")
+    n = p.numel() if n is None else n
+    if n > min(ema.numel(), p.numel()):
+        raise _cabi.VitError(f"ema_update: n = {n} exceeds a buffer ({ema.numel()}, {p.numel()} elements)")
+    _h(p).call("vit_ema_update", ema.data_ptr(), p.data_ptr(), n, float(weight), _ptr(weight_dev), _stream(p))
+
+
+def ema_swap(p, ema, p_bf16=None, *, n: Optional[int] = None):
+    """Exchange the first `n` elements of p and ema in place; p_bf16 (optional) <- bf16 of the new p in the same pass."""
+    _chk(ema, torch.float32, "ema_swap ema")
+    _chk(p, torch.float32, "ema_swap p")
+    n = p.numel() if n is None else n
+    if n > min(ema.numel(), p.numel()) or (p_bf16 is not None and n > p_bf16.numel()):
+        raise _cabi.VitError(f"ema_swap: n = {n} exceeds a buffer")
+    if p_bf16 is not None:
+        _chk(p_bf16, torch.bfloat16, "ema_swap p_bf16")
+    _h(p).call("vit_ema_swap", p.data_ptr(), ema.data_ptr(), _ptr(p_bf16), n, _stream(p))
+
+
+def ema_weight_write(cell, weight: float):
+    """cell[0, 0] <- weight on the current stream: `cell` is a one-row group table ([1, 4] f32) and the number travels by value
+    in a kernel argument (vit_optim_groups_write), so a captured vit_ema_update that reads the cell sees it in stream order."""
+    arr = (C.c_float * 3)(float(weight), 0.0, 0.0)
+    _h(cell).call("vit_optim_groups_write", cell.data_ptr(), 1, arr, _stream(cell))

@@ -6,7 +6,9 @@ to step cannot live in kernel arguments (they are frozen at capture), so it live
 entry: a 32-byte record (`vit_step_state_bind`, include/vit_amd.h) with the dropout keys of the step and Adam's step count /
 bias corrections, advanced by the first node of the graph (`vit_step_advance`); and the optimizer's group table with the
 learning rates, weight decays and SGD's momenta, which the optimizer rewrites ahead of a replay whenever a scheduler changed
-one (`FusedOptimizer._sync_group_table`).  The host writes nothing into the record but the step counter.
+one (`FusedOptimizer._sync_group_table`).  The host writes nothing into the record but the step counter.  With weight
+averaging (`train.ema_decay`, vit_amd/ema.py) the update of the average is the graph's last node; its lerp weight -- 0 on a step the
+schedule skips, 1 for the first update, 1 - decay otherwise -- lives in a one-float device cell that is rewritten the same way.
 
 Scope: one process, one GPU (the RCCL exchange of N > 1 is not captured), a fused optimizer (vit_amd/optimizer.py:
 FusedAdamW, FusedSGD), no trainable input preprocessor, a fixed batch shape.  The reference's step semantics are unchanged
@@ -36,7 +38,7 @@ class GraphedTrainStep:
     `batch` = (flux, error, labels); tensors whose storage differs from the captured ones are copied into the static input
     buffers first (a device-to-device copy of the batch)."""
 
-    def __init__(self, module, optimizer: FusedOptimizer, batch, warmup: int = 2):
+    def __init__(self, module, optimizer: FusedOptimizer, batch, warmup: int = 2, averager=None):
         model = module.model
         eng = model.engine
         if not isinstance(optimizer, FusedOptimizer):
@@ -46,7 +48,7 @@ class GraphedTrainStep:
         if getattr(module, "noise_level", 0):
             raise ValueError("GraphedTrainStep: on-the-fly noise draws a host seed per step; not captured")
         flux, _, labels = batch
-        self.module, self.opt, self.eng = module, optimizer, eng
+        self.module, self.opt, self.eng, self.averager = module, optimizer, eng, averager
         dev = eng.flat.device
         eng._ensure_device_state()
         self.h = eng.handle()  # the engine's own handle: its calls read the bound per-step record
@@ -68,6 +70,9 @@ class GraphedTrainStep:
         # so that the first replay IS the run's next step
         eng._ensure_device_state()
         keep = (eng.flat.clone(), optimizer.clone_state(), int(eng.step_counter))
+        if averager is not None:
+            averager._ensure()  # the capture holds the addresses of its buffer and of its weight cell
+            keep_ema = averager.clone_state()
         # warm-up on a side stream (torch's capture protocol): sizes the arena / workspace, sets the kernels' LDS attributes
         # one stream inside the graph: two-branch graphs (the weight-gradient GEMMs on their second stream) replayed 0.7 ms per
         # step SLOWER than the same two streams launched eagerly on this stack.  The engine's own setting is put back after
@@ -97,6 +102,8 @@ class GraphedTrainStep:
             eng.flat.copy_(keep[0])
             optimizer.restore_state(keep[1])  # in place: the graph holds the state buffers' addresses
             eng.step_counter = keep[2]
+            if averager is not None:
+                averager.restore_state(keep_ema)  # in place, like the optimizer's
             self.state[5] = int(optimizer._step)
             self._dev_step = int(optimizer._step)  # host mirror of the record's step counter
             if eng.shadow is not None:
@@ -124,11 +131,16 @@ class GraphedTrainStep:
             sq = vf.grad_sqnorm(eng.grads[:n], out=opt._sq)
             opt.last_grad_norm = sq
         opt._launch(0, n, self._tables, eng.shadow if eng.precision == "bf16" else None, sq, dyn=True)
+        if self.averager is not None:
+            self.averager.capture_update()
         return loss
 
-    def step(self, batch) -> torch.Tensor:
+    def step(self, batch, step: Optional[int] = None) -> torch.Tensor:
+        """`step`: the number (1-based) of the optimizer step this replay is, for the averaging schedule."""
         flux, _, labels = batch
         self.opt._graph_validate(self._captured)  # ValueError before anything is touched: the caller falls back to eager steps
+        if self.averager is not None and step is None:
+            raise ValueError("GraphedTrainStep.step: the averaging schedule needs the optimizer step's number (step=)")
         if flux is not self._src[0] or flux._version != self._src[2]:
             self.x.copy_(flux, non_blocking=True)
             self._src = (None, self._src[1], -1, self._src[3])
@@ -136,6 +148,10 @@ class GraphedTrainStep:
             self.labels.copy_(labels, non_blocking=True)
             self._src = (self._src[0], None, self._src[2], -1)
         self.opt._sync_group_table()  # on the current stream, ahead of the replay: a launch only when a scheduler changed a number
+        ema_w = 0.0
+        if self.averager is not None:
+            ema_w = self.averager.weight_for(step)
+            self.averager.set_device_weight(ema_w)  # likewise: a launch only when the weight differs from the last replay's
         if self._dev_step != int(self.opt._step):
             # the record's step counter (Adam's bias corrections, dropout keys) is advanced by THIS graph's replays only: steps
             # taken elsewhere in between -- another captured shape (an epoch's partial last batch), eager steps -- put it back
@@ -152,6 +168,8 @@ class GraphedTrainStep:
         self._dev_step += 1
         self.eng.step_counter += 1
         self.eng.mark_shadow_fresh()
+        if ema_w != 0.0:
+            self.averager.n_averaged += 1
         return self.loss
 
     __call__ = step

@@ -8,6 +8,8 @@
                       (`train.accumulate_grad_batches: K` = Lightning's: zero_grad at the start of a group of K batches,
                       each backward on loss / K adding into the flat gradient buffer in place, exchange + clip + step +
                       per-step scheduler on every K-th batch and on the epoch's last one)
+                      (`train.ema_decay`: after the optimizer step the weights' exponential moving average is updated on the
+                      GPU, vit_amd/ema.py; validation and checkpoints then see the averaged weights)
            validate every epoch (basemodule.py:249)
            scheduler: ReduceLROnPlateau on `val_{monitor}` / per-epoch / per-step (opt/optimizer.py:150-172)
            ModelCheckpoint(save_top_k=1, monitor=val_{mae|acc}, save_last=True) when `train.save` (vit.py:386-414)
@@ -35,6 +37,7 @@ from typing import Any, Dict, Iterable, Optional
 import torch
 
 from . import ddp as ddp_mod
+from .ema import WeightAverager, averaging_config
 from .optimizer import FusedOptimizer
 
 __all__ = ["Trainer", "Checkpointer", "FreezeSchedule", "select_accelerator_and_devices", "get_training_strategy", "seed_everything"]
@@ -215,6 +218,10 @@ class Trainer:
         # train.accumulate_grad_batches (Lightning's semantics): micro-batches per optimizer step
         self.accumulate_grad_batches = _accumulate_grad_batches(config)
         self._micro = 0  # micro-batches of the current group already accumulated
+        # train.ema_decay (+ ema_every, ema_start_step): an exponential moving average of the weights, updated after optimizer
+        # steps, validated and checkpointed in place of the raw weights (vit_amd/ema.py); absent by default
+        self.ema_cfg = averaging_config(config)
+        self.averager: Optional[WeightAverager] = None
         self.verbose = verbose and self.rank == 0
         self.logged: Dict[str, float] = {}
         self.metric_totals: Dict[str, float] = {}
@@ -279,6 +286,11 @@ class Trainer:
         if isinstance(self.optimizer, FusedOptimizer):
             self.optimizer.set_grad_clip(self.gradient_clip_val)
             self.optimizer.attach_reducer(self.reducer)
+        if self.ema_cfg is not None:
+            # what the optimizer steps outside the model's flat buffer (a trainable input preprocessor) is averaged too
+            own = {id(p) for p in module.model._param_list}
+            extras = [p for grp in self.optimizer.param_groups for p in grp["params"] if id(p) not in own]
+            self.averager = WeightAverager(module.model, extras=extras, **self.ema_cfg)
         # freeze schedule of the input preprocessor (src/prepca/callbacks.py): warmup.freeze_epochs > 0 freezes it for
         # that many epochs, -1 for good, 0 never.  (As in the reference, the optimizer was built from the parameters that
         # existed at configure time: a preprocessor unfrozen later becomes trainable for autograd but is only stepped if it
@@ -313,6 +325,8 @@ class Trainer:
         else:
             snap["opt"] = copy.deepcopy(opt.state_dict())
             snap["extra_params"] = [p.detach().clone() for p in module.parameters()]
+        if self.averager is not None:
+            snap["ema"] = self.averager.clone_state()
         return snap
 
     def _restore(self, module, snap):
@@ -335,6 +349,8 @@ class Trainer:
                     p.copy_(q)
         for g, saved in zip(opt.param_groups, snap["groups"]):
             g.update(saved)
+        if self.averager is not None:
+            self.averager.restore_state(snap["ema"])
         opt.zero_grad(set_to_none=True)
         self._micro = 0
 
@@ -413,6 +429,8 @@ class Trainer:
         if self.sched_cfg and self.sched_cfg.get("interval") == "step":
             self.sched_cfg["scheduler"].step()
         self.global_step += 1
+        if self.averager is not None:  # once per optimizer step, behind it (under 'zero1': behind the all-gather)
+            self.averager.update(self.global_step)
 
     def _accumulating_step(self, module, batch, batch_idx, is_last: bool):
         """One micro-batch of a group of K = train.accumulate_grad_batches (Lightning's semantics).  The backward runs on
@@ -458,11 +476,12 @@ class Trainer:
         g = self._graphed.get(key)
         try:
             if g is None:
-                g = GraphedTrainStep(module, self.optimizer, batch)  # capture (runs warm-up steps on this batch)
+                g = GraphedTrainStep(module, self.optimizer, batch, averager=self.averager)  # capture (warm-up steps on this batch)
                 while len(self._graphed) >= 2:
                     self._graphed.pop(next(iter(self._graphed)))
                 self._graphed[key] = g
-            loss = g.step(batch)  # refuses (before it touches anything) what its capture no longer covers
+            # refuses (before it touches anything) what its capture no longer covers
+            loss = g.step(batch, step=self.global_step + 1)
         except (TypeError, ValueError) as e:
             import warnings
 
@@ -520,9 +539,14 @@ class Trainer:
     # ------------------------------------------------------------------ checkpoints
     def make_checkpoint(self, module) -> Dict[str, Any]:
         """Lightning's checkpoint layout (the keys the reference's `trainer.fit(ckpt_path=)` / `test(ckpt_path=)` read)."""
-        sd = {f"model.{k}": v.detach().cpu().clone() for k, v in module.model.state_dict().items()}
+        ema = self.averager if self.averager is not None and self.averager.n_averaged > 0 else None
+        if ema is None:
+            sd = {f"model.{k}": v.detach().cpu().clone() for k, v in module.model.state_dict().items()}
+        else:  # the validated model: test(ckpt_path=), model_state_from_checkpoint and the reference's loader read the average
+            averaged, train_state = ema.named_states()
+            sd = {f"model.{k}": v for k, v in averaged.items()}
         sch = self.sched_cfg["scheduler"].state_dict() if self.sched_cfg else None
-        return {
+        ckpt = {
             "epoch": int(self.current_epoch), "global_step": int(self.global_step), "state_dict": sd,
             # Lightning's loader reads this key to decide on checkpoint migrations; the reference pins lightning 2.5.4 (requirements.txt:23)
             "pytorch-lightning_version": "2.5.4",
@@ -534,10 +558,22 @@ class Trainer:
             "vit_amd": {"version": 2, "dropout_base_seed": int(module.model.engine.base_seed),
                         "dropout_step": int(module.model.engine.step_counter)},
         }
+        if ema is not None:  # only then: without averaging the file is laid out as it always was
+            ckpt["vit_amd"]["ema"] = {"decay": ema.decay, "every": ema.every, "start_step": ema.start_step,
+                                      "n_averaged": int(ema.n_averaged), "train_state": train_state}
+        return ckpt
 
     def _resume(self, module, ckpt_path: str) -> int:
         ckpt = load_checkpoint_file(ckpt_path)
-        module.model.load_state_dict(model_state_from_checkpoint(ckpt))
+        saved_ema = (ckpt.get("vit_amd") or {}).get("ema")
+        if self.averager is not None and saved_ema:
+            # `state_dict` holds the averaged weights, `train_state` the raw ones: both sequences continue exactly
+            module.model.load_state_dict(saved_ema["train_state"])
+            self.averager.load_state_dict({"n_averaged": saved_ema["n_averaged"], "averaged": model_state_from_checkpoint(ckpt)})
+        else:
+            module.model.load_state_dict(model_state_from_checkpoint(ckpt))
+            if self.averager is not None:
+                self.averager.load_state_dict({"n_averaged": 0})
         if ckpt.get("optimizer_states"):
             self.optimizer.load_state_dict(ckpt["optimizer_states"][0])
         if ckpt.get("lr_schedulers") and self.sched_cfg:
@@ -573,6 +609,8 @@ class Trainer:
         self._es_best, self._es_bad = None, 0
         self._setup(module)
         _bind(train_loader, self.device)
+        if self.averager is not None and self.averager.swapped:  # an earlier fit() left the average in the model
+            self.averager.swap(module.model.engine)
         first_epoch = self._resume(module, ckpt_path) if ckpt_path else 0
         peeked = None  # (first batch, the rest) of a ONE-SHOT iterable whose first batch the autotune looked at
         if self.exchanging and str(self.reserve_cus_cfg) not in ("0", "", "None"):
@@ -625,7 +663,7 @@ class Trainer:
                         break
                 logs = self._flush_epoch_logs()
                 if val_loader is not None:
-                    logs.update(self.validate(module, val_loader, "val"))
+                    logs.update(self._validate_averaged(module, val_loader))
                 self._step_epoch_scheduler(logs)
                 logs["lr"] = self.optimizer.param_groups[0]["lr"]
                 logs["epoch_time_s"] = time.time() - t0
@@ -638,11 +676,26 @@ class Trainer:
                 if self._early_stop(logs):
                     self.should_stop = True
                     break
+            if self.averager is not None and self.averager.n_averaged > 0:
+                # a normal end or an early stop: the model keeps the averaged weights, the averager the raw ones
+                self.averager.swap(module.model.engine)
         finally:
             # everything alive at freeze time (models, engines, optimizers of EARLIER fits in this process) sat in
             # the permanent generation for good; hand it back so that cyclic garbage among them can be collected again
             gc.unfreeze()
         return self.history
+
+    def _validate_averaged(self, module, val_loader):
+        """fit()'s validation: on the averaged weights once there are any, so that the monitored metric -- the plateau
+        scheduler, the early stop, the best checkpoint -- is the averaged model's; the raw weights are back afterwards."""
+        ema = self.averager if self.averager is not None and self.averager.n_averaged > 0 else None
+        if ema is None:
+            return self.validate(module, val_loader, "val")
+        ema.swap(module.model.engine)
+        try:
+            return self.validate(module, val_loader, "val")
+        finally:
+            ema.swap(module.model.engine)
 
     def _step_epoch_scheduler(self, logs):
         if not self.sched_cfg or self.sched_cfg.get("interval", "epoch") == "step":
