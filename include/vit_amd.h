@@ -362,5 +362,8 @@ int vit_adamw_step(vit_handle h, float* p, const float* g, float* m, float* v, v
 /* The exponential moving average of the weights (`train.ema_decay`): vit_ema_update behind the optimizer step, vit_ema_swap
  * around an evaluation.  Declared in their own header, part of this ABI. */
 #include "vit_amd_ema.h"
+/* Stochastic depth (`model.drop_path_rate`): the path forms of the two LayerNorm passes that form and differentiate the
+ * residual sums.  Declared in their own header, part of this ABI. */
+#include "vit_amd_droppath.h"
 
 #endif /* VIT_AMD_H_ */

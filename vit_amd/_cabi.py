@@ -109,6 +109,10 @@ _PROTOS = {
     # (h, ema, p, n, weight, weight_dev, stream) / (h, p, ema, p_bf16, n, stream)
     "vit_ema_update": [_P, _P, _P, _I64, _F, _P, _P],
     "vit_ema_swap": [_P, _P, _P, _P, _I64, _P],
+    # the _rows forms' arguments + (path_p, seed, path_site, rows_per_sample, branch) / (path_p, path_site, rows_per_sample, branch)
+    "vit_layernorm_fwd_residual_path": [_P, _P, _I64, _P, _I, _P, _P, _P, _P, _I, _P, _P, _I, _I, _F, _F, _U64, _U64, _I, _I, _P],
+    "vit_layernorm_bwd_path": [_P, _P, _I, _P, _P, _P, _P, _P, _I64, _P, _P, _P, _I, _I, _P, _I, _P, _F, _U64, _U64, _I64, _F,
+                               _U64, _I, _I, _P],
 }
 _RESTYPES = {"vit_last_error": C.c_char_p, "vit_last_gemm_kernel": C.c_char_p, "vit_workspace_needed": C.c_size_t}
 
@@ -117,7 +121,7 @@ _lock = threading.Lock()
 
 
 def declared_symbols(header_path: str = HEADER_PATH):
-    """Every function the C header declares, the headers it includes from its own directory (vit_amd_cov.h, vit_amd_optim.h, vit_amd_ema.h) included (used by
+    """Every function the C header declares, the headers it includes from its own directory (vit_amd_cov.h, vit_amd_optim.h, vit_amd_ema.h, vit_amd_droppath.h) included (used by
     the CPU test that checks the library exports them all)."""
     seen, names, todo = set(), set(), [os.path.abspath(header_path)]
     while todo:

@@ -26,7 +26,7 @@ SOURCES = ["api.hip", "gemm.hip", "gemm2.hip", "layernorm.hip", "attention.hip",
            "attention_pipe.hip", "attention_f32.hip", "elementwise.hip", "covariance.hip", "optim.hip", "ema.hip"]
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "attention.h"), os.path.join(ROOT, "include", "vit_amd.h"),
            os.path.join(ROOT, "include", "vit_amd_cov.h"), os.path.join(ROOT, "include", "vit_amd_optim.h"),
-           os.path.join(ROOT, "include", "vit_amd_ema.h")]
+           os.path.join(ROOT, "include", "vit_amd_ema.h"), os.path.join(ROOT, "include", "vit_amd_droppath.h")]
 
 
 def _hipcc() -> str:

@@ -35,6 +35,9 @@ class ViTConfig:
     pos_encoding_type: Optional[str] = None
     max_position_embeddings: int = 512
     rope_base: float = 10000.0
+    # stochastic depth: layer i of L drops each of its two residual branches per sample with probability
+    # linspace(0, drop_path_rate, L)[i] in training forwards (this build's key; 0 = the reference's arithmetic)
+    drop_path_rate: float = 0.0
     use_return_dict: bool = True
 
     @property
@@ -91,8 +94,8 @@ def get_vit_config(config) -> ViTConfig:
         model["num_labels"] = num_labels
     else:
         num_labels = int(model.get("num_labels", 1) or 1)
-    optional = {k: model[k] for k in ("stride_ratio", "stride_size", "pos_encoding_type", "max_position_embeddings", "rope_base")
-                if k in model}
+    optional = {k: model[k] for k in ("stride_ratio", "stride_size", "pos_encoding_type", "max_position_embeddings", "rope_base",
+                                      "drop_path_rate") if k in model}
     return ViTConfig(
         task_type=model["task_type"], image_size=model["image_size"], patch_size=model["patch_size"],
         hidden_size=model["hidden_size"], num_hidden_layers=model["num_hidden_layers"],

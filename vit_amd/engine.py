@@ -22,6 +22,7 @@ A layer's tail -- out-projection, LN-after, FC1 + GELU, FC2 behind its attention
 from __future__ import annotations
 
 import collections
+import gc
 import math
 import os
 from typing import Callable, Dict, List, Optional, Tuple
@@ -200,6 +201,8 @@ class ViTEngine:
         if cfg.head_dim % 4 or cfg.head_dim > 128 or cfg.hidden_size % 8 or cfg.patch_size % 8:
             raise ValueError(f"vit_amd kernels need head_dim % 4 == 0 and <= 128, hidden_size % 8 == 0, patch_size % 8 == 0 "
                              f"(got head_dim {cfg.head_dim}, hidden_size {cfg.hidden_size}, patch_size {cfg.patch_size})")
+        if not 0.0 <= float(cfg.drop_path_rate) < 1.0:
+            raise ValueError(f"drop_path_rate must lie in [0, 1) (got {cfg.drop_path_rate})")
         self.cfg = cfg
         self.loss_name, self.loss_kind = resolved_loss(cfg.task_type, loss_name)
         self.layout = ParamLayout(cfg)
@@ -380,6 +383,11 @@ class ViTEngine:
             return
         self.act, self.tmp, self._rows = {}, {}, None
         self._arenas.pop(train, None)  # release the slot's old tensors before allocating their replacement
+        # ... and those of models that are no longer referenced: a model and its engine refer to each other, so a dropped model's
+        # arena, gradients and workspaces (17 GB at ViT-B; an earlier trial of a sweep, the model before a rebuild) stay allocated
+        # until the cycle collector happens to run -- at a moment no caller chooses, possibly in the middle of a step.  An arena is
+        # allocated once per batch size, outside the steady state, so this is the place to run it.
+        gc.collect()
         c = self.cfg
         dev = self.flat.device
         T, D, Fd, H, L, N, P = c.seq_len, c.hidden_size, c.intermediate_size, c.num_attention_heads, \
@@ -462,6 +470,25 @@ class ViTEngine:
     def _site(self, layer: int, which: int) -> int:
         return 1 + 4 * layer + which
 
+    def path_rates(self, training: bool = True) -> Optional[List[float]]:
+        """Stochastic depth: the drop probability of layer i's two residual branches, the usual linear schedule
+        torch.linspace(0, drop_path_rate, L) (layer 0 never drops).  None when no branch can drop: not training, or rate 0."""
+        rate, L = float(self.cfg.drop_path_rate), self.cfg.num_hidden_layers
+        if not training or rate <= 0.0 or L == 0:
+            return None
+        if not rate < 1.0:
+            raise ValueError(f"drop_path_rate must lie in [0, 1) (got {rate})")
+        return [float(v) for v in torch.linspace(0, rate, L).tolist()]
+
+    def _path(self, pd: Optional[List[float]], i: int, branch: int, rows_per_sample: Optional[int] = None):
+        """The path arguments of layer i's branch (0: attention, 1: MLP) for the LayerNorm passes: (p_i, site, rows per sample,
+        branch) with the layer's fourth site, the one dropout leaves free -- or None where nothing can drop.  Rows per sample:
+        T in the row space a pass indexes by original row (the backward always; the forward over a stream it reads in place);
+        1 where the forward reads a compact stream of one row per sample (the CLS tail's second sum)."""
+        if pd is None or i < 0 or pd[i] <= 0.0:
+            return None
+        return (pd[i], self._site(i, 3), self.cfg.seq_len if rows_per_sample is None else rows_per_sample, branch)
+
     def forward(self, x: torch.Tensor, labels: Optional[torch.Tensor], training: bool, need_grad: bool,
                 output_hidden_states: bool = False, output_attentions: bool = False, capture_ctx: Optional[list] = None):
         self._ensure_device_state()
@@ -487,6 +514,7 @@ class ViTEngine:
         a = self.act
         ph = c.hidden_dropout_prob if training else 0.0
         pa = c.attention_probs_dropout_prob if training else 0.0
+        pd = self.path_rates(training)  # read on every forward, like the dropout probabilities
         if training:
             self.step_counter += 1
         seed = (self.base_seed + 0x9E3779B97F4A7C15 * self.step_counter) & 0xFFFFFFFFFFFFFFFF
@@ -525,7 +553,7 @@ class ViTEngine:
             else:  # ... or by the final LayerNorm: over the CLS rows alone when only the head consumes it
                 r = cls if tail else full
                 then = (r.xL, "vit.layernorm", r.last2, r.meanF, r.rstdF)
-            self._tail_fwd(r, i, j, a["x"][i].view(M, D), then, ph, seed, need_grad)
+            self._tail_fwd(r, i, j, a["x"][i].view(M, D), then, ph, seed, need_grad, pd)
         hn = self.layout.head
         if labels is not None:
             labels = labels.to(self.flat.device)
@@ -534,12 +562,12 @@ class ViTEngine:
             if labels.numel() != n_expected:
                 raise ValueError(f"labels has {labels.numel()} elements, expected {n_expected}")
         logits, loss = vf.head_loss_fwd(r.last, self.p(hn + ".weight"), self.p(hn + ".bias"), labels, self.loss_kind)
-        self._last = dict(B=B, seed=seed, ph=ph, pa=pa, labels=labels, logits=logits, gen=self._gen, grad=need_grad,
+        self._last = dict(B=B, seed=seed, ph=ph, pa=pa, pd=pd, labels=labels, logits=logits, gen=self._gen, grad=need_grad,
                           tail=tail)
         hs = [t.clone() for t in a["x"]] if output_hidden_states else None
         return loss, logits, hs, atts
 
-    def _tail_fwd(self, r: Rows, i: int, j: int, xin, then, ph: float, seed: int, need_grad: bool):
+    def _tail_fwd(self, r: Rows, i: int, j: int, xin, then, ph: float, seed: int, need_grad: bool, pd=None):
         """Layer i behind its attention, over the rows `r` (activations in layer slot j): out-projection -> LN-after -> FC1 + GELU
         -> FC2 -> `then` = (xsum, name, out, mean, rstd), the LayerNorm that consumes FC2's output (the next layer's LN-before, or
         the final one).
@@ -548,18 +576,22 @@ class ViTEngine:
         f32 stream and y, writes the new stream and its normalised operand (vit_layernorm_fwd_residual).
         Rows of stride T (the CLS rows b*T): ctx and the residual stream `xin` are read in place, everything written is compact,
         and the dropout masks are keyed by the ORIGINAL row b*T so that they are the full path's (and oracle/dropmask.py's)
-        bit for bit."""
+        bit for bit.
+        `pd` (path_rates): with pd[i] > 0 the two sums gate their branch per sample (stochastic depth) inside the same
+        LayerNorm passes; the sample of a row is its original row // T, so the CLS rows draw the full path's decisions."""
         c, a, nm = self.cfg, self.act, self.names[i]
         D, Fd, n = c.hidden_size, c.intermediate_size, r.n
         drs = r.stride if r.stride > 1 else 0
         vf.gemm(a["ctx"][j], self.W(nm.wo), M=n, N=D, K=D, lda=r.stride * D, out=r.y, bias=self.b(nm.wo),
                 dropout=(ph, seed, self._site(i, 1)), drop_row_stride=drs)
-        self._ln_res(xin, r.y, r.x1[j], nm.ln2, r.h2[j], r.mean2[j], r.rstd2[j], x_row_stride=r.stride)
+        self._ln_res(xin, r.y, r.x1[j], nm.ln2, r.h2[j], r.mean2[j], r.rstd2[j], x_row_stride=r.stride,
+                     path=self._path(pd, i, 0), seed=seed)
         vf.gemm(r.h2[j], self.W(nm.fc1), M=n, N=Fd, K=D, out=r.g[j], bias=self.b(nm.fc1), act=vf.ACT_GELU_GRAD if need_grad
                 else ACT_GELU, aux_out=r.u[j] if need_grad else None)  # u holds gelu'(pre-activation) for the backward
         vf.gemm(r.g[j], self.W(nm.fc2), M=n, N=D, K=Fd, out=r.y, bias=self.b(nm.fc2), dropout=(ph, seed, self._site(i, 2)),
                 drop_row_stride=drs)
-        self._ln_res(r.x1[j], r.y, *then)
+        # x1 is compact over the CLS rows (one row per sample, read with stride 1): the sample of its row b is b
+        self._ln_res(r.x1[j], r.y, *then, path=self._path(pd, i, 1, c.seq_len // r.stride), seed=seed)
 
     def saved_attentions(self):
         """Attention probabilities (before dropout) of every layer of the LAST need_grad forward, from its saved qkv."""
@@ -574,9 +606,11 @@ class ViTEngine:
         vf.layernorm_fwd(x, self.p(name + ".weight"), self.p(name + ".bias"), self.cfg.layer_norm_eps, out=out,
                          mean=mean, rstd=rstd)
 
-    def _ln_res(self, x, delta, xsum, name, out, mean, rstd, x_row_stride=1):
+    def _ln_res(self, x, delta, xsum, name, out, mean, rstd, x_row_stride=1, path=None, seed=0):
+        # path: the sum gates delta per sample (stochastic depth, vit_layernorm_fwd_residual_path); None = the plain forms
         vf.layernorm_fwd_residual(x, delta, xsum, self.p(name + ".weight"), self.p(name + ".bias"),
-                                  self.cfg.layer_norm_eps, out=out, mean=mean, rstd=rstd, x_row_stride=x_row_stride)
+                                  self.cfg.layer_norm_eps, out=out, mean=mean, rstd=rstd, x_row_stride=x_row_stride,
+                                  path=path, seed=seed)
 
     # ------------------------------------------------------------------ weight gradients beside the data path
     def _dw(self, r: Rows, dy, x, out, ldx: Optional[int] = None):
@@ -655,22 +689,26 @@ class ViTEngine:
 
     # ------------------------------------------------------------------ backward
     def _ln_bwd(self, r: Rows, name: str, dy, x, mean, rstd, dres, dx, dyn=None, dbias=None, dropout=vf.NO_DROP,
-                dres_row_stride: int = 0):
+                dres_row_stride: int = 0, path=None):
         """The backward of LayerNorm `name` over the rows `r`: dx = dres + its input gradient, and the gradients of its weight
         and bias.  With `dyn` it also emits dyn = dropout_mask * dx (activation dtype) and dbias = its column sums: the gradient
         of the Linear output underneath the next "dropout(.) + residual" going down, and that Linear's bias gradient.
-        `dres_row_stride = T`: dres alone is compact -- the CLS rows' residual gradient rejoining the token stream."""
+        `dres_row_stride = T`: dres alone is compact -- the CLS rows' residual gradient rejoining the token stream.
+        `path` (with dyn): that Linear sits in a branch gated per sample -- dyn carries the gate the forward drew
+        (vit_layernorm_bwd_path)."""
         vf.layernorm_bwd_rows(dy, x, self.p(name + ".weight"), mean, rstd, dres, dx, self.dW(name), self.db(name), dyn=dyn,
-                              dbias=dbias, dropout=dropout, dres_row_stride=dres_row_stride, row_stride=r.stride, full_rows=r.M)
+                              dbias=dbias, dropout=dropout, dres_row_stride=dres_row_stride, row_stride=r.stride, full_rows=r.M,
+                              path=path)
 
-    def _fc2_dy(self, r: Rows, i: int, ph: float, seed: int) -> dict:
+    def _fc2_dy(self, r: Rows, i: int, ph: float, seed: int, pd=None) -> dict:
         """What the LayerNorm backward that consumes layer i's output emits for that layer's FC2 (_ln_bwd's dyn / dbias):
-        r.dy and the FC2 bias gradient.  Nothing for i = -1: under layer 0's LN-before lie the embeddings."""
+        r.dy and the FC2 bias gradient, gated like layer i's MLP branch was in the forward (`pd`).  Nothing for i = -1: under
+        layer 0's LN-before lie the embeddings."""
         if i < 0:
             return {}
-        return dict(dyn=r.dy, dbias=self.db(self.names[i].fc2), dropout=(ph, seed, self._site(i, 2)))
+        return dict(dyn=r.dy, dbias=self.db(self.names[i].fc2), dropout=(ph, seed, self._site(i, 2)), path=self._path(pd, i, 1))
 
-    def _tail_bwd(self, r: Rows, i: int, dx, dx_out, ph: float, seed: int):
+    def _tail_bwd(self, r: Rows, i: int, dx, dx_out, ph: float, seed: int, pd=None):
         """Layer i's backward behind its attention, over the rows `r`: from `dx`, the gradient of the layer's output stream
         (r.dy = mask * dx and the FC2 bias gradient came with the LayerNorm backward above), down to r.dctx; the residual
         gradient at the layer's LN-after input goes to `dx_out`.
@@ -698,7 +736,7 @@ class ViTEngine:
         # this pass writes the OTHER dy buffer: the FC2 weight gradient still reading r.dy keeps running beside it
         self._before_write(r.dy2)
         self._ln_bwd(r, nm.ln2, r.dh, r.x1[i], r.mean2[i], r.rstd2[i], dx, dx_out, dyn=r.dy2, dbias=self.db(nm.wo),
-                     dropout=(ph, seed, self._site(i, 1)))
+                     dropout=(ph, seed, self._site(i, 1)), path=self._path(pd, i, 0))
         self._dw(r, r.dy2, a["ctx"][i], self.dW(nm.wo), ldx=r.stride * D)
         vf.gemm(r.dy2, self.W(nm.wo), M=n, N=D, K=D, b_trans=True, out=r.dctx, ldc=r.stride * D)
 
@@ -736,7 +774,7 @@ class ViTEngine:
                            "between (the engine keeps the activations of ONE forward; run backward before the next forward)")
         c = self.cfg
         a, t = self.act, self.tmp
-        B, seed, ph, pa = st["B"], st["seed"], st["ph"], st["pa"]
+        B, seed, ph, pa, pd = st["B"], st["seed"], st["ph"], st["pa"], st["pd"]  # pd: the forward's path rates
         T, D, H, L, N, P = c.seq_len, c.hidden_size, c.num_attention_heads, c.num_hidden_layers, c.num_patches, c.patch_size
         dh, M = c.head_dim, B * T
         scale = dh ** -0.5
@@ -750,10 +788,10 @@ class ViTEngine:
         self._setup_side()
         dx, spare = r.dx  # the residual gradient and the buffer the next LayerNorm backward writes it to
         self._ln_bwd(r, "vit.layernorm", r.dlast.view(-1, D), r.xL, r.meanF, r.rstdF, None, dx,
-                     **self._fc2_dy(r, L - 1, ph, seed))
+                     **self._fc2_dy(r, L - 1, ph, seed, pd))
         self._notify(self.layout.tail_start, self.layout.n_trainable)
         for i in reversed(range(L)):
-            self._tail_bwd(r, i, dx, spare, ph, seed)
+            self._tail_bwd(r, i, dx, spare, ph, seed, pd)
             dx, spare = spare, dx
             self._before_write(t["dqkv"])
             # the QKV bias gradient = column sums of dqkv: taken by the attention kernels on their way out, unless RoPE
@@ -775,7 +813,7 @@ class ViTEngine:
                 rejoin, r = r.stride, full
                 dx, spare = full.dx
             self._ln_bwd(full, self.names[i].ln1, t["dh"], a["x"][i].view(M, D), a["mean1"][i], a["rstd1"][i], dres, spare,
-                         dres_row_stride=rejoin, **self._fc2_dy(full, i - 1, ph, seed))
+                         dres_row_stride=rejoin, **self._fc2_dy(full, i - 1, ph, seed, pd))
             dx, spare = spare, dx
             self._notify(*self.layout.layer_ranges[i])
         dpos = self.g(EMBED + "position_embeddings").view(T, D) if c.pos_encoding_type == "learned" else None

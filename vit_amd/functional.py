@@ -148,10 +148,14 @@ def layernorm_fwd(x, gamma, beta, eps: float, out_dtype=torch.bfloat16, out=None
     return y, mean, rstd
 
 
+DropPath = Tuple[float, int, int, int]  # (p, site, rows_per_sample, branch); the seed is the step's, shared with dropout
+
+
 def layernorm_fwd_residual(x, delta, xsum, gamma, beta, eps: float, out_dtype=torch.bfloat16, out=None, mean=None,
-                           rstd=None, x_row_stride: int = 1):
+                           rstd=None, x_row_stride: int = 1, path: Optional[DropPath] = None, seed: int = 0):
     """xsum = x + delta (f32 stream + bf16/f32 projection output); y = LayerNorm(xsum).
-    `x_row_stride = s > 1`: the rows are every s-th row of x (delta, xsum, y, mean, rstd compact: x.numel() / (D s) rows)."""
+    `x_row_stride = s > 1`: the rows are every s-th row of x (delta, xsum, y, mean, rstd compact: x.numel() / (D s) rows).
+    `path` (with `seed`): the stochastic-depth form, see layernorm_fwd_residual_path."""
     _chk(x, torch.float32, "layernorm_fwd_residual x")
     _chk(xsum, torch.float32, "layernorm_fwd_residual xsum")
     h = _h(x)
@@ -166,6 +170,12 @@ def layernorm_fwd_residual(x, delta, xsum, gamma, beta, eps: float, out_dtype=to
     rstd = rstd if rstd is not None else torch.empty(rows, dtype=torch.float32, device=x.device)
     if y.numel() != xsum.numel() or mean.numel() < rows or rstd.numel() < rows:
         raise _cabi.VitError("layernorm_fwd_residual: out / mean / rstd do not hold xsum's rows")
+    if path is not None:
+        p, site, rps, branch = path
+        h.call("vit_layernorm_fwd_residual_path", x.data_ptr(), x_row_stride, delta.data_ptr(), _DT[delta.dtype],
+               xsum.data_ptr(), gamma.data_ptr(), beta.data_ptr(), y.data_ptr(), _DT[y.dtype], _ptr(mean), _ptr(rstd), rows,
+               D, eps, p, seed, site, rps, branch, _stream(x))
+        return y, mean, rstd
     if x_row_stride != 1:
         h.call("vit_layernorm_fwd_residual_rows", x.data_ptr(), x_row_stride, delta.data_ptr(), _DT[delta.dtype],
                xsum.data_ptr(), gamma.data_ptr(), beta.data_ptr(), y.data_ptr(), _DT[y.dtype], _ptr(mean), _ptr(rstd), rows,
@@ -203,11 +213,13 @@ def layernorm_bwd_fused(dy, x, gamma, mean, rstd, dres, dx, dgamma, dbeta, dyn, 
 
 
 def layernorm_bwd_rows(dy, x, gamma, mean, rstd, dres, dx, dgamma, dbeta, dyn=None, dbias=None, dropout: Dropout = NO_DROP,
-                       dres_row_stride: int = 0, row_stride: int = 1, full_rows: Optional[int] = None):
+                       dres_row_stride: int = 0, row_stride: int = 1, full_rows: Optional[int] = None,
+                       path: Optional[DropPath] = None):
     """layernorm_bwd (dyn None) / layernorm_bwd_fused at the two ends of a compact run of rows (vit_layernorm_bwd_rows):
     `row_stride = s > 1`: the tensors hold the rows r = j * s of a full tensor of `full_rows` rows compactly (mask keyed by r,
     parameter gradients summed in the full pass's order); `dres_row_stride = s > 0`: dres alone is compact and its row j is the
-    residual gradient of row j * s, every other row has none."""
+    residual gradient of row j * s, every other row has none.  `path` (with dyn): the stochastic-depth form, see
+    layernorm_bwd_path."""
     _chk(x, torch.float32, "layernorm_bwd_rows x")
     _chk(dx, torch.float32, "layernorm_bwd_rows dx")
     h = _h(x)
@@ -227,10 +239,32 @@ def layernorm_bwd_rows(dy, x, gamma, mean, rstd, dres, dx, dgamma, dbeta, dyn=No
         if dres_row_stride or -(-full_rows // row_stride) != rows:
             raise _cabi.VitError("layernorm_bwd_rows: row_stride needs full_rows = the full tensor's rows and a dres like dx")
         rows = full_rows
+    if path is not None:
+        pp, psite, rps, branch = path
+        h.call("vit_layernorm_bwd_path", dy.data_ptr(), _DT[dy.dtype], x.data_ptr(), gamma.data_ptr(), mean.data_ptr(),
+               rstd.data_ptr(), _ptr(dres), dres_row_stride, dx.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), rows, D,
+               _ptr(dyn), _DT[dyn.dtype] if dyn is not None else VIT_BF16, _ptr(dbias), p, seed, site, row_stride, pp, psite,
+               rps, branch, _stream(x))
+        return dx
     h.call("vit_layernorm_bwd_rows", dy.data_ptr(), _DT[dy.dtype], x.data_ptr(), gamma.data_ptr(), mean.data_ptr(),
            rstd.data_ptr(), _ptr(dres), dres_row_stride, dx.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), rows, D,
            _ptr(dyn), _DT[dyn.dtype] if dyn is not None else VIT_BF16, _ptr(dbias), p, seed, site, row_stride, _stream(x))
     return dx
+
+
+def layernorm_fwd_residual_path(x, delta, xsum, gamma, beta, eps: float, path: DropPath, seed: int, **kw):
+    """layernorm_fwd_residual with a per-sample gate on delta (include/vit_amd_droppath.h): xsum = x + m * delta, m = 0 or the
+    kept-branch scale, one draw per (sample, branch); the sample of compact row r is r * x_row_stride // rows_per_sample."""
+    return layernorm_fwd_residual(x, delta, xsum, gamma, beta, eps, path=path, seed=seed, **kw)
+
+
+def layernorm_bwd_path(dy, x, gamma, mean, rstd, dres, dx, dgamma, dbeta, dyn, dbias, path: DropPath, **kw):
+    """layernorm_bwd_rows (its fused form: dyn and dbias are required) for a sum whose branch is gated per sample
+    (include/vit_amd_droppath.h): dyn = dx * dropout mask * (0 or the kept-branch scale); the seed is `dropout`'s, also with
+    dropout off; the sample of full row r is r // rows_per_sample."""
+    if dyn is None or dbias is None:
+        raise _cabi.VitError("layernorm_bwd_path: dyn and dbias are required")
+    return layernorm_bwd_rows(dy, x, gamma, mean, rstd, dres, dx, dgamma, dbeta, dyn=dyn, dbias=dbias, path=path, **kw)
 
 
 def linear_bwd_dw_rows(dy, x, out, *, row_stride: int, full_rows: int, ldx: Optional[int] = None):

@@ -9,6 +9,8 @@ learning rates, weight decays and SGD's momenta, which the optimizer rewrites ah
 one (`FusedOptimizer._sync_group_table`).  The host writes nothing into the record but the step counter.  With weight
 averaging (`train.ema_decay`, vit_amd/ema.py) the update of the average is the graph's last node; its lerp weight -- 0 on a step the
 schedule skips, 1 for the first update, 1 - decay otherwise -- lives in a one-float device cell that is rewritten the same way.
+Stochastic depth (`model.drop_path_rate`) needs no mechanism of its own: the frozen launches carry each layer's rate p_i, and
+the per-sample gate is drawn from the record's keys like every dropout mask, so each replay draws a fresh one.
 
 Scope: one process, one GPU (the RCCL exchange of N > 1 is not captured), a fused optimizer (vit_amd/optimizer.py:
 FusedAdamW, FusedSGD), no trainable input preprocessor, a fixed batch shape.  The reference's step semantics are unchanged
@@ -36,7 +38,10 @@ class GraphedTrainStep:
     """`step(batch) -> loss` replaying a captured forward + backward + clip + optimizer update over `module.model` (a MyViT).
 
     `batch` = (flux, error, labels); tensors whose storage differs from the captured ones are copied into the static input
-    buffers first (a device-to-device copy of the batch)."""
+    buffers first (a device-to-device copy of the batch).
+
+    Stochastic depth (`model.drop_path_rate`) rides along unchanged: the frozen launches carry each layer's rate, the bound
+    record's keys vary the per-sample draw from replay to replay, as they vary the dropout masks."""
 
     def __init__(self, module, optimizer: FusedOptimizer, batch, warmup: int = 2, averager=None):
         model = module.model
