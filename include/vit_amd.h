@@ -365,5 +365,8 @@ int vit_adamw_step(vit_handle h, float* p, const float* g, float* m, float* v, v
 /* Stochastic depth (`model.drop_path_rate`): the path forms of the two LayerNorm passes that form and differentiate the
  * residual sums.  Declared in their own header, part of this ABI. */
 #include "vit_amd_droppath.h"
+/* LayerScale (`model.layer_scale_init`) as a reparametrisation at weight size: the fold of lambda into the out-projection /
+ * FC2 operands and the pass that unfolds their raw gradients.  Declared in their own header, part of this ABI. */
+#include "vit_amd_layerscale.h"
 
 #endif /* VIT_AMD_H_ */

@@ -48,6 +48,17 @@ class GemmDesc(C.Structure):
     ]
 
 
+class LayerScaleEntry(C.Structure):
+    """vit_layer_scale_entry (include/vit_amd_layerscale.h): one matrix of a fold / gradient table, 96 bytes."""
+    _fields_ = [
+        ("W", C.c_void_p), ("b", C.c_void_p), ("lam", C.c_void_p),
+        ("Wf", C.c_void_p), ("bf", C.c_void_p),
+        ("dW_raw", C.c_void_p), ("db_raw", C.c_void_p), ("dW", C.c_void_p), ("db", C.c_void_p), ("dlam", C.c_void_p),
+        ("rows", C.c_int32), ("cols", C.c_int32),
+        ("reserved", C.c_int64),
+    ]
+
+
 _P, _I, _F, _U64, _I64, _SZ = C.c_void_p, C.c_int, C.c_float, C.c_uint64, C.c_int64, C.c_size_t
 
 # name -> argtypes (restype is int unless listed in _RESTYPES)
@@ -113,6 +124,10 @@ _PROTOS = {
     "vit_layernorm_fwd_residual_path": [_P, _P, _I64, _P, _I, _P, _P, _P, _P, _I, _P, _P, _I, _I, _F, _F, _U64, _U64, _I, _I, _P],
     "vit_layernorm_bwd_path": [_P, _P, _I, _P, _P, _P, _P, _P, _I64, _P, _P, _P, _I, _I, _P, _I, _P, _F, _U64, _U64, _I64, _F,
                                _U64, _I, _I, _P],
+    # (h, table, entries, count, stream) / (h, table, n_entries, max_rows, out_dtype | accumulate, stream)
+    "vit_layer_scale_table_write": [_P, _P, C.POINTER(LayerScaleEntry), _I, _P],
+    "vit_layer_scale_fold": [_P, _P, _I, _I, _I, _P],
+    "vit_layer_scale_grad": [_P, _P, _I, _I, _I, _P],
 }
 _RESTYPES = {"vit_last_error": C.c_char_p, "vit_last_gemm_kernel": C.c_char_p, "vit_workspace_needed": C.c_size_t}
 
@@ -121,7 +136,7 @@ _lock = threading.Lock()
 
 
 def declared_symbols(header_path: str = HEADER_PATH):
-    """Every function the C header declares, the headers it includes from its own directory (vit_amd_cov.h, vit_amd_optim.h, vit_amd_ema.h, vit_amd_droppath.h) included (used by
+    """Every function the C header declares, the headers it includes from its own directory (vit_amd_cov.h, vit_amd_optim.h, vit_amd_ema.h, vit_amd_droppath.h, vit_amd_layerscale.h) included (used by
     the CPU test that checks the library exports them all)."""
     seen, names, todo = set(), set(), [os.path.abspath(header_path)]
     while todo:

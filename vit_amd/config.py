@@ -38,6 +38,9 @@ class ViTConfig:
     # stochastic depth: layer i of L drops each of its two residual branches per sample with probability
     # linspace(0, drop_path_rate, L)[i] in training forwards (this build's key; 0 = the reference's arithmetic)
     drop_path_rate: float = 0.0
+    # LayerScale: a learnable per-channel factor on each of a layer's two residual branches, initialised to this value (> 0;
+    # this build's key).  None = off: the reference's model, parameter for parameter
+    layer_scale_init: Optional[float] = None
     use_return_dict: bool = True
 
     @property
@@ -95,7 +98,7 @@ def get_vit_config(config) -> ViTConfig:
     else:
         num_labels = int(model.get("num_labels", 1) or 1)
     optional = {k: model[k] for k in ("stride_ratio", "stride_size", "pos_encoding_type", "max_position_embeddings", "rope_base",
-                                      "drop_path_rate") if k in model}
+                                      "drop_path_rate", "layer_scale_init") if k in model}
     return ViTConfig(
         task_type=model["task_type"], image_size=model["image_size"], patch_size=model["patch_size"],
         hidden_size=model["hidden_size"], num_hidden_layers=model["num_hidden_layers"],

@@ -14,6 +14,8 @@ Data layout in HBM (one MI355X, 288 GB: nothing is recomputed or re-materialised
            lse f32 [B*H,T], x1 f32 [M,D], u/g bf16 [M,4D] (pre/post GELU), LN statistics.  M = B*T token rows.
   CLS tail c_* : compact [B, .] twins of y / x1 / h2 / u / g / x[L] / last and their statistics (and of the backward's
            scratch): what the last layer computes behind its attention when only the head consumes it (see `cls_tail`).
+  LayerScale (cfg.layer_scale_init, off by default): folded [L * 5 D^2] operands of the out-projection / FC2 GEMMs (operand dtype)
+           + f32 [L * 2D] biases, and per layer an f32 [5 D^2 + 2D] slab of their raw gradients (`_ensure_ls`).
 Dropout masks are regenerated from (seed, site) in backward; no mask is stored.
 
 A layer's tail -- out-projection, LN-after, FC1 + GELU, FC2 behind its attention -- is stated once per direction
@@ -42,6 +44,15 @@ PROJ = EMBED + "patch_embeddings.projection"
 LayerNames = collections.namedtuple("LayerNames", "ln1 q wo ln2 fc1 fc2")
 _LAYER_STEMS = LayerNames("layernorm_before", "attention.attention.query", "attention.output.dense", "layernorm_after",
                           "intermediate.dense", "output.dense")
+# LayerScale (cfg.layer_scale_init): the two per-channel factors of a layer and the Linear each one scales, as name stems
+LAMBDA = "lambda1"  # HF DINOv2's parameter name: vit.encoder.layer.{i}.layer_scale{1,2}.lambda1
+_SCALED = (("layer_scale1", "attention.output.dense"), ("layer_scale2", "output.dense"))
+# what a scaled Linear's GEMMs read and write in place of its parameter and gradient slices: the folded operands
+# Wf = diag(lambda) W (operand dtype), bf = lambda * b, and the raw gradients of those two (f32)
+ScaledLinear = collections.namedtuple("ScaledLinear", "Wf bf dW_raw db_raw")
+# ViTEngine._ls; views: name stem -> ScaledLinear, table: vf.LayerScaleTable (entries 2i, 2i + 1 = layer i's two Linears),
+# raw_ptrs: the data_ptr of every dW_raw
+LayerScaleState = collections.namedtuple("LayerScaleState", "views table raw_ptrs held")
 # one slot of ViTEngine._arenas; rows = (the token rows, the CLS rows)
 Arena = collections.namedtuple("Arena", "key act tmp Mp rows")
 
@@ -98,6 +109,9 @@ class ParamLayout:
             add(p + "layernorm_before.bias", (D,))
             add(p + "layernorm_after.weight", (D,))
             add(p + "layernorm_after.bias", (D,))
+            if cfg.layer_scale_init is not None:  # inside the layer's range: its bucket, its lr, its gradient exchange
+                for scale, _ in _SCALED:
+                    add(p + f"{scale}.{LAMBDA}", (D,))
             self.layer_ranges.append((start, off))
         self.tail_start = off
         add("vit.layernorm.weight", (D,))
@@ -121,6 +135,8 @@ class ParamLayout:
                 order += [p + f"attention.attention.{n}.weight", p + f"attention.attention.{n}.bias"]
             for n in ("attention.output.dense", "intermediate.dense", "output.dense", "layernorm_before", "layernorm_after"):
                 order += [p + n + ".weight", p + n + ".bias"]
+            if cfg.layer_scale_init is not None:
+                order += [p + f"{scale}.{LAMBDA}" for scale, _ in _SCALED]
         order += ["vit.layernorm.weight", "vit.layernorm.bias", "vit.pooler.dense.weight", "vit.pooler.dense.bias",
                   head + ".weight", head + ".bias"]
         assert sorted(order) == sorted(self.entries)
@@ -203,6 +219,9 @@ class ViTEngine:
                              f"(got head_dim {cfg.head_dim}, hidden_size {cfg.hidden_size}, patch_size {cfg.patch_size})")
         if not 0.0 <= float(cfg.drop_path_rate) < 1.0:
             raise ValueError(f"drop_path_rate must lie in [0, 1) (got {cfg.drop_path_rate})")
+        ls = cfg.layer_scale_init
+        if ls is not None and (isinstance(ls, bool) or not isinstance(ls, (int, float)) or not math.isfinite(ls) or not ls > 0):
+            raise ValueError(f"layer_scale_init must be a finite number > 0, or None for no LayerScale (got {ls!r})")
         self.cfg = cfg
         self.loss_name, self.loss_kind = resolved_loss(cfg.task_type, loss_name)
         self.layout = ParamLayout(cfg)
@@ -210,6 +229,11 @@ class ViTEngine:
         self.shadow: Optional[torch.Tensor] = None
         self.grads: Optional[torch.Tensor] = None
         self._shadow_version = -1
+        # LayerScale: the folded operands of the scaled Linears, their raw-gradient slabs and the kernels' table (_ensure_ls);
+        # None while the feature is off, or nothing is allocated yet
+        self.layer_scale = ls is not None
+        self._ls: Optional[LayerScaleState] = None
+        self._fold_epoch = -1  # the _shadow_epoch the folded operands were made at
         self.names = [LayerNames(*(f"vit.encoder.layer.{i}.{s}" for s in _LAYER_STEMS)) for i in range(cfg.num_hidden_layers)]
         self._arena_key = None
         self._arenas: Dict[bool, Arena] = {}  # train? -> its slot: one arena for training, one for evaluation
@@ -296,7 +320,13 @@ class ViTEngine:
         if self.grads is None:
             self.grads = torch.zeros(self.layout.n_total, dtype=torch.float32, device=self.flat.device)
         if self.precision != "bf16":
-            return  # the x3 GEMMs read the f32 master weights directly
+            # the x3 GEMMs read the f32 master weights directly; only the folded operands can be stale
+            if self.layer_scale:
+                ver = self.version_fn()
+                if self._shadow_version != ver:
+                    self._shadow_version = ver
+                self._ensure_folded()
+            return
         if self.shadow is None:
             self.shadow = torch.empty(self.layout.n_total, dtype=torch.bfloat16, device=self.flat.device)
             self._shadow_version = -1
@@ -304,6 +334,63 @@ class ViTEngine:
         if self._shadow_version != ver:
             vf.cast_f32_bf16(self.flat, self.shadow)
             self._shadow_version = ver
+        if self.layer_scale:
+            self._ensure_folded()
+
+    # ------------------------------------------------------------------ LayerScale
+    # Every write of _shadow_version -- a cast, mark_shadow_fresh() behind a kernel that rewrote flat and shadow through raw
+    # pointers, the -1 that invalidates -- counts as one epoch: the folded operands are stale exactly when the shadow is stale or
+    # has just been rewritten, so they are refolded when the epoch moved since the last fold.
+    _shadow_epoch = 0
+
+    @property
+    def _shadow_version(self) -> int:
+        return self._shadow_ver
+
+    @_shadow_version.setter
+    def _shadow_version(self, ver: int):
+        self._shadow_ver = ver
+        self._shadow_epoch += 1
+
+    def _ensure_ls(self) -> "LayerScaleState":
+        """The LayerScale side buffers, allocated on first use for the current device and precision: folded weights in the GEMM
+        operand dtype (L * 5 D^2) and folded biases (L * 2D, f32); per layer a slab of raw gradients (5 D^2 + 2D, f32, zeroed:
+        the raw bias gradients must be zero when an accumulating backward begins); the kernels' table, two entries per layer."""
+        if self._ls is None:
+            c, dev = self.cfg, self.flat.device
+            D, Fd, L = c.hidden_size, c.intermediate_size, c.num_hidden_layers
+            nw, per = D * D + D * Fd, D * D + D * Fd + 2 * D
+            wf = torch.empty(L * nw, dtype=self.adt, device=dev)
+            bf = torch.empty(L * 2 * D, dtype=torch.float32, device=dev)
+            raw = torch.zeros(L * per, dtype=torch.float32, device=dev)
+            views, entries = {}, []
+            for i in range(L):
+                p, w0, r0 = f"vit.encoder.layer.{i}.", i * nw, i * per
+                for k, ((scale, stem), K) in enumerate(zip(_SCALED, (D, Fd))):
+                    wo, ro = w0 + k * D * D, r0 + k * D * D  # the out-projection's D x D comes first
+                    v = ScaledLinear(Wf=wf[wo:wo + D * K].view(D, K), bf=bf[(2 * i + k) * D:(2 * i + k + 1) * D],
+                                     dW_raw=raw[ro:ro + D * K].view(D, K), db_raw=raw[r0 + nw + k * D:r0 + nw + (k + 1) * D])
+                    views[p + stem] = v
+                    entries.append(dict(W=self.p(p + stem + ".weight"), b=self.p(p + stem + ".bias"),
+                                        lam=self.p(p + f"{scale}.{LAMBDA}"), dW=self.g(p + stem + ".weight"),
+                                        db=self.g(p + stem + ".bias"), dlam=self.g(p + f"{scale}.{LAMBDA}"), **v._asdict()))
+            with vf.use_handle(self.handle()):
+                table = vf.layer_scale_table(entries, dev)
+            self._ls = LayerScaleState(views, table, frozenset(v.dW_raw.data_ptr() for v in views.values()), (wf, bf, raw))
+            self._fold_epoch = -1
+        return self._ls
+
+    def fold_layer_scale(self):
+        """Wf = diag(lambda) W, bf = lambda * b for every scaled Linear, from the f32 master weights: one launch on the current
+        stream (unconditionally: this is also the first node of a captured step)."""
+        ls = self._ensure_ls()
+        with vf.use_handle(self.handle()):
+            vf.layer_scale_fold(ls.table, self.adt)
+        self._fold_epoch = self._shadow_epoch
+
+    def _ensure_folded(self):
+        if self._ls is None or self._fold_epoch != self._shadow_epoch:
+            self.fold_layer_scale()
 
     def handle(self):
         """This engine's own vit_handle.  Launch geometry (`reserve_cus`) and the split-K / reduction workspace belong to the
@@ -342,18 +429,29 @@ class ViTEngine:
     def g(self, name: str) -> torch.Tensor:
         return self.layout.view(self.grads, name)
 
-    # by name stem (self.names[i].fc1, PROJ, ...): W the GEMM operand, b the f32 bias, dW / db their gradient slices
+    # by name stem (self.names[i].fc1, PROJ, ...): W the GEMM operand, b the f32 bias, dW / db their gradient slices.  With
+    # LayerScale on, the out-projection and FC2 stems name the folded operands and the raw-gradient slabs instead (the true
+    # gradients reach the flat buffer through vit_layer_scale_grad at the end of the layer's backward).
+    def _scaled(self, stem: str) -> Optional[ScaledLinear]:
+        return None if self._ls is None else self._ls.views.get(stem)
+
     def W(self, stem: str) -> torch.Tensor:
+        v = self._scaled(stem)
+        if v is not None:
+            return v.Wf
         return self.layout.view(self.shadow if self.precision == "bf16" else self.flat, stem + ".weight")
 
     def b(self, stem: str) -> torch.Tensor:
-        return self.layout.view(self.flat, stem + ".bias")
+        v = self._scaled(stem)
+        return self.layout.view(self.flat, stem + ".bias") if v is None else v.bf
 
     def dW(self, stem: str) -> torch.Tensor:
-        return self.layout.view(self.grads, stem + ".weight")
+        v = self._scaled(stem)
+        return self.layout.view(self.grads, stem + ".weight") if v is None else v.dW_raw
 
     def db(self, stem: str) -> torch.Tensor:
-        return self.layout.view(self.grads, stem + ".bias")
+        v = self._scaled(stem)
+        return self.layout.view(self.grads, stem + ".bias") if v is None else v.db_raw
 
     def _qkv_w(self, i: int, buf: torch.Tensor):
         """Layer i's adjacent query / key / value weights in `buf` (a flat buffer) as one [3D, D] matrix."""
@@ -452,6 +550,7 @@ class ViTEngine:
         self._arena_key = None
         self._arenas = {}
         self.act, self.tmp, self._rows = {}, {}, None
+        self._ls = None  # the folded operands have the precision's operand dtype and point into flat / grads
 
     def _rope_tables(self, T: int):
         """Half-width cos / sin tables of RotaryPositionEmbedding (rope.py:36-56), computed on the host by the reference's
@@ -627,15 +726,32 @@ class ViTEngine:
         each, which runs before this call on the main stream, and the next step's writers run behind _join_side; a second
         writer of one of them inside a step would need _before_write like the token rows'."""
         N, K = out.shape
+        # a raw-gradient slab of a scaled Linear (LayerScale) is overwritten even inside an accumulating backward: the add into
+        # the flat buffer is vit_layer_scale_grad's.  The handle's option is read on the host when the product is planned.
+        raw = self._accum and self._ls is not None and out.data_ptr() in self._ls.raw_ptrs
         with self._on_side as side:
-            if r.stride > 1:
-                return vf.linear_bwd_dw_rows(dy, x, out, row_stride=r.stride, full_rows=r.Mp, ldx=ldx)
-            vf.gemm(dy, x, M=N, N=K, K=r.n, a_trans=True, b_trans=True, ldb=ldx, out=out, split_k=-1)
+            if raw:
+                vf._h(out).set_option("grad_accumulate", 0)
+            try:
+                if r.stride > 1:
+                    return vf.linear_bwd_dw_rows(dy, x, out, row_stride=r.stride, full_rows=r.Mp, ldx=ldx)
+                vf.gemm(dy, x, M=N, N=K, K=r.n, a_trans=True, b_trans=True, ldb=ldx, out=out, split_k=-1)
+            finally:
+                if raw:
+                    vf._h(out).set_option("grad_accumulate", 1)
             if side is not None:
                 ev = torch.cuda.Event()
                 ev.record(side)
                 self._side_reads[dy.data_ptr()] = ev
         return out
+
+    def _unfold_layer_scale(self, i: int):
+        """The end of layer i's backward with LayerScale on: the raw gradients of its two folded Linears become the gradients of
+        W, b and lambda in the flat buffer (one launch; it leaves the raw bias gradients zeroed for the next backward).  Issued
+        where the layer's weight-gradient GEMMs were, behind them, and in front of the layer's _notify."""
+        if self._ls is not None:
+            with self._on_side:
+                vf.layer_scale_grad(self._ls.table, self._accum, first=2 * i, count=2)
 
     def _before_write(self, buf):
         """The main stream waits for the second stream's last reader of `buf` (see _dw), if there is one."""
@@ -815,6 +931,7 @@ class ViTEngine:
             self._ln_bwd(full, self.names[i].ln1, t["dh"], a["x"][i].view(M, D), a["mean1"][i], a["rstd1"][i], dres, spare,
                          dres_row_stride=rejoin, **self._fc2_dy(full, i - 1, ph, seed, pd))
             dx, spare = spare, dx
+            self._unfold_layer_scale(i)
             self._notify(*self.layout.layer_ranges[i])
         dpos = self.g(EMBED + "position_embeddings").view(T, D) if c.pos_encoding_type == "learned" else None
         vf.embed_finish_bwd(dx.view(B, T, D), self.g(EMBED + "cls_token").view(D), dpos, dropout=(ph, seed, 0),

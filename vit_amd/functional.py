@@ -650,6 +650,69 @@ def ema_swap(p, ema, p_bf16=None, *, n: Optional[int] = None):
     _h(p).call("vit_ema_swap", p.data_ptr(), ema.data_ptr(), _ptr(p_bf16), n, _stream(p))
 
 
+# ------------------------------------------------------------------------------------------------ LayerScale
+class LayerScaleTable:
+    """The device table of `vit_layer_scale_fold` / `vit_layer_scale_grad` (include/vit_amd_layerscale.h): 96 bytes per matrix.
+    `rows[i]` mirrors entry i's row count on the host (the launch geometry); `held` keeps the tensors the entries point to."""
+
+    def __init__(self, table, rows, held):
+        self.table, self.rows, self.held = table, rows, held
+        self.n = len(rows)
+
+
+_LS_FIELDS = ("W", "b", "lam", "Wf", "bf", "dW_raw", "db_raw", "dW", "db", "dlam")
+_LS_DTYPES = (torch.float32, torch.bfloat16)
+
+
+def layer_scale_table(entries, device) -> LayerScaleTable:
+    """Build the table from one dict per matrix: W [rows, cols], b, lam (f32); Wf (bf16 / f32 like W), bf -- the fold's outputs;
+    dW_raw, db_raw, dW, db, dlam (f32) -- what the gradient pass reads and writes.  Either output set may be absent.  The library
+    checks the entries (vit_layer_scale_table_write) and writes them on the current stream."""
+    arr = (_cabi.LayerScaleEntry * len(entries))()
+    rows, held = [], []
+    for i, ent in enumerate(entries):
+        W = ent["W"]
+        if W.dim() != 2:
+            raise _cabi.VitError(f"layer_scale_table: entry {i}: W must be a matrix")
+        r, c = W.shape
+        for k in _LS_FIELDS:
+            t = ent.get(k)
+            if t is None:
+                continue
+            if k != "Wf":
+                _chk(t, torch.float32, f"layer_scale_table entry {i} {k}")
+            elif t.dtype not in _LS_DTYPES or not t.is_contiguous():
+                raise _cabi.VitError(f"layer_scale_table: entry {i}: Wf must be a contiguous bf16 / f32 tensor")
+            if t.device != W.device or t.numel() != (r * c if k in ("W", "Wf", "dW_raw", "dW") else r):
+                raise _cabi.VitError(f"layer_scale_table: entry {i}: {k} does not match W's shape {r} x {c} (or its device)")
+            setattr(arr[i], k, t.data_ptr())
+            held.append(t)
+        arr[i].rows, arr[i].cols = r, c
+        rows.append(r)
+    table = torch.zeros(max(1, len(entries)) * 12, dtype=torch.int64, device=device)
+    _h(table).call("vit_layer_scale_table_write", table.data_ptr(), arr, len(entries), _stream(table))
+    return LayerScaleTable(table, rows, held)
+
+
+def _ls_span(tab: LayerScaleTable, first: int, count: Optional[int]):
+    count = tab.n - first if count is None else count
+    if first < 0 or count <= 0 or first + count > tab.n:
+        raise _cabi.VitError(f"layer scale: entries [{first}, {first + count}) are not inside a table of {tab.n}")
+    return tab.table.data_ptr() + 96 * first, count, max(tab.rows[first:first + count])
+
+
+def layer_scale_fold(tab: LayerScaleTable, out_dtype, first: int = 0, count: Optional[int] = None):
+    """Wf = diag(lam) W (stored as `out_dtype`: what the entries' Wf tensors are), bf = lam * b for `count` entries from `first`."""
+    ptr, count, max_rows = _ls_span(tab, first, count)
+    _h(tab.table).call("vit_layer_scale_fold", ptr, count, max_rows, _DT[out_dtype], _stream(tab.table))
+
+
+def layer_scale_grad(tab: LayerScaleTable, accumulate: bool = False, first: int = 0, count: Optional[int] = None):
+    """dW (+)= diag(lam) dW_raw, db (+)= lam * db_raw, dlam (+)= rowsum(dW_raw * W) + db_raw * b; db_raw is left zeroed."""
+    ptr, count, max_rows = _ls_span(tab, first, count)
+    _h(tab.table).call("vit_layer_scale_grad", ptr, count, max_rows, int(bool(accumulate)), _stream(tab.table))
+
+
 def ema_weight_write(cell, weight: float):
     """cell[0, 0] <- weight on the current stream: `cell` is a one-row group table ([1, 4] f32) and the number travels by value
     in a kernel argument (vit_optim_groups_write), so a captured vit_ema_update that reads the cell sees it in stream order."""

@@ -98,7 +98,7 @@ class GraphedTrainStep:
             # The graph replays RAW POINTERS into the activation arena and the library workspace.  Hold the tensors: whatever
             # the engine or the handle do later (another batch size, a grown workspace), the captured addresses stay valid and
             # are nobody else's.  (The engine also keeps evaluation forwards in their own arena: engine._ensure_arena.)
-            self._held = (eng.act, eng.tmp, self.h._ws)
+            self._held = (eng.act, eng.tmp, self.h._ws, eng._ls)  # _ls: LayerScale's folded operands, slabs and table
         finally:
             # also on a failed warm-up / capture: the warm-up steps were real optimisation steps and must not leak into the run
             _cabi.check(self.h.lib.vit_step_state_bind(self.h.h, None), "vit_step_state_bind")
@@ -128,6 +128,10 @@ class GraphedTrainStep:
         st = torch.cuda.current_stream(eng.flat.device).cuda_stream
         b1, b2 = self._betas
         _cabi.check(lib.vit_step_advance(h, eng.base_seed, b1, b2, st), "vit_step_advance")
+        if eng.layer_scale:
+            # LayerScale: the previous replay's optimizer node rewrote W, b and lambda, so the fold of lambda into the
+            # out-projection / FC2 operands is a node of the graph in front of the forward, launched unconditionally
+            eng.fold_layer_scale()
         loss, _, _, _ = eng.forward(self.x, self.labels, training=True, need_grad=True)
         eng.backward(self.dloss)
         n = eng.layout.n_trainable

@@ -182,6 +182,8 @@ class MyViT(nn.Module):
         for name, p in zip(self._param_names, self._param_list):
             if name.endswith("cls_token") or name.endswith("position_embeddings"):
                 p.copy_(torch.randn(p.shape))
+            elif name.endswith(".lambda1"):  # LayerScale (config.layer_scale_init): present only when the feature is on
+                p.fill_(float(self.config.layer_scale_init))
             elif "layernorm" in name:
                 p.fill_(1.0 if name.endswith("weight") else 0.0)
             elif name.endswith("bias"):
