@@ -90,7 +90,10 @@ int vit_set_option(const char* name, int value);
  * the slice total; every vector output -- the last stage of the partial-row reducer.  A vit_gemm whose C accumulates AND that
  * carries colsum_out (two parameter gradients from one descriptor; no training step issues it) runs the product into a
  * scratch matrix in the workspace, behind what its stages use (part of what the call needs of it), sums its columns and adds it
- * into C. */
+ * into C.
+ * "lamb_passes": 7 (default) | a mask of 1 (moments + partial norms), 2 (ratios), 4 (apply): the launches a vit_lamb_step*
+ * call makes (vit_amd_optim.h).  For measurement only -- tools/lamb_bench.py times each pass alone with it; a pass alone reads
+ * what an earlier full call left in the workspace and in `trust`, so anything but 7 computes no optimizer step. */
 int vit_handle_set_option(vit_handle h, const char* name, int value);
 
 /* Per-step state in device memory, for a training step captured as a hipGraph (HIP streams and graphs instead of a tracing

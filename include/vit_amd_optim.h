@@ -52,7 +52,41 @@
  *   numbers travel by value in kernel arguments (64 rows per launch) and are stored with 16-byte vector stores, so there is no
  *   staging buffer the host could overwrite under a running step.  The caller launches it only when a scheduler changed a
  *   number, ahead of the step -- or ahead of the replay of a captured step -- on the same stream: per-step schedules stay
- *   correct under a hipGraph although kernel arguments are frozen at capture. */
+ *   correct under a hipGraph although kernel arguments are frozen at capture.
+ *
+ * vit_lamb_step*: LAMB as timm's `Lamb` states it (the implementation DeiT-III trains with), the fused clip in the place of timm's
+ *   max_grad_norm.  Here a SEGMENT IS ONE PARAMETER TENSOR together with its alignment pad (zero in every buffer): the trust
+ *   ratio is a norm over exactly that tensor, so the segment table is the per-parameter one
+ *   (vit_amd.functional.optim_param_tables), never the merged runs the other families may be given.  Per segment, with the
+ *   call-wide clip as above:
+ *     g' = g * clip
+ *     m  = beta1 * m + (1 - beta1) * g'          v = beta2 * v + (1 - beta2) * g'^2
+ *     u  = (m / bc1) / (sqrt(v) / sqrt(bc2) + eps)   [+ weight_decay * p   if weight_decay != 0]
+ *     adapt = (weight_decay != 0) or always_adapt
+ *     r  = adapt and ||p|| > 0 and ||u|| > 0 ? ||p|| / ||u|| : 1        (L2 norms over the segment)
+ *     r  = trust_clip ? min(r, 1) : r
+ *     p -= lr * r * u;  p_bf16 = bf16(p)
+ *   lr and weight_decay are the segment's group row's; beta1, beta2, eps, always_adapt, trust_clip and `step` (1-based) are
+ *   call-wide; 1 - beta is 1.f - beta as in vit_adamw_step; g is only read.  Defaults of the Python layer: betas (0.9, 0.999),
+ *   eps 1e-6, always_adapt and trust_clip off.
+ *   Three launches per call, their dependencies kernel boundaries (no atomics, no block waits for another): (1) m and v are
+ *   updated and every TILE writes one (sum p^2, sum u^2) pair into the handle's workspace; (2) one wave per segment sums its
+ *   tiles' pairs in a fixed order and writes trust[s]; (3) u is recomputed from the stored m, v and the untouched p by the same
+ *   device function -- bit for bit what entered the norm -- and p and the shadow are written.  42 B per parameter (24 + 18)
+ *   against AdamW's 30; storing u instead would take 4 B of scratch per parameter.  Tiles are VIT_LAMB_TILE elements cut from
+ *   each segment's start (the last one short; none straddles a segment), a function of the segment table alone -- not of the
+ *   grid, of `base` or of a handle option -- and all sums are f64 in one fixed order: deterministic, and a call over a sub-run
+ *   [base, base + n) of WHOLE segments gives on those segments the bits the whole-buffer call gives, trust[] included.  A run
+ *   that cuts a segment is the caller's error (vit_amd.functional refuses it); the kernels then cut the segment to the run and
+ *   still read nothing outside the run or the tables.  A segment whose group index is negative (a parameter no group owns,
+ *   which the per-parameter table keeps as a segment of its own so that it enters no neighbour's norm) is neither read nor
+ *   written, and neither is its trust entry.
+ *   `trust`: f32, caller-owned, n_segments entries indexed by the table's segment number; the by-value form (one tensor = one
+ *   segment, for parameters outside the flat buffer) takes one entry, or NULL.  Workspace: 16 + 16 B per tile slot,
+ *   n / VIT_LAMB_TILE + n_segments + 1 slots (by value: ceil(n / VIT_LAMB_TILE)), stated through vit_workspace_needed.
+ *   `_dyn`: bc1 and sqrt(bc2) from the bound record, as for the other families.
+ *   VIT_ERR_ARG, before anything is launched: a NULL p, g, m, v or table; a NULL trust with a table; n <= 0; n_segments <= 0;
+ *   n_groups <= 0; base < 0 or not a multiple of 4; step < 1; no record bound (`_dyn`). */
 #ifndef VIT_AMD_OPTIM_H_
 #define VIT_AMD_OPTIM_H_
 
@@ -93,6 +127,20 @@ int vit_sgd_step_groups_dyn(vit_handle h, float* p, const float* g, float* buf, 
                             const int64_t* seg_end, const int32_t* seg_group, int n_segments, const float* groups,
                             int n_groups, int nesterov, const float* sqnorm, float max_norm, vit_stream stream);
 int vit_optim_groups_write(vit_handle h, float* groups, int n_groups, const float* values, vit_stream stream);
+
+#define VIT_LAMB_TILE 4096 /* elements per tile of the LAMB norms, cut from each segment's start */
+
+int vit_lamb_step(vit_handle h, float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, float lr, float beta1,
+                  float beta2, float eps, float weight_decay, int always_adapt, int trust_clip, int step, const float* sqnorm,
+                  float max_norm, float* trust, vit_stream stream);
+int vit_lamb_step_groups(vit_handle h, float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, int64_t base,
+                         const int64_t* seg_end, const int32_t* seg_group, int n_segments, const float* groups, int n_groups,
+                         float beta1, float beta2, float eps, int always_adapt, int trust_clip, int step, const float* sqnorm,
+                         float max_norm, float* trust, vit_stream stream);
+int vit_lamb_step_groups_dyn(vit_handle h, float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, int64_t base,
+                             const int64_t* seg_end, const int32_t* seg_group, int n_segments, const float* groups,
+                             int n_groups, float beta1, float beta2, float eps, int always_adapt, int trust_clip,
+                             const float* sqnorm, float max_norm, float* trust, vit_stream stream);
 
 #ifdef __cplusplus
 }

@@ -117,6 +117,12 @@ _PROTOS = {
     "vit_sgd_step_groups": [_P, _P, _P, _P, _P, _I64, _I64, _P, _P, _I, _P, _I, _I, _P, _F, _P],
     "vit_sgd_step_groups_dyn": [_P, _P, _P, _P, _P, _I64, _I64, _P, _P, _I, _P, _I, _I, _P, _F, _P],
     "vit_optim_groups_write": [_P, _P, _I, C.POINTER(C.c_float), _P],
+    # (h, p, g, m, v, p_bf16, n, lr, beta1, beta2, eps, weight_decay, always_adapt, trust_clip, step, sqnorm, max_norm, trust, stream)
+    "vit_lamb_step": [_P, _P, _P, _P, _P, _P, _I64, _F, _F, _F, _F, _F, _I, _I, _I, _P, _F, _P, _P],
+    # (h, p, g, m, v, p_bf16, n, base, seg_end, seg_group, n_segments, groups, n_groups, beta1, beta2, eps, always_adapt,
+    #  trust_clip, [step,] sqnorm, max_norm, trust, stream)
+    "vit_lamb_step_groups": [_P, _P, _P, _P, _P, _P, _I64, _I64, _P, _P, _I, _P, _I, _F, _F, _F, _I, _I, _I, _P, _F, _P, _P],
+    "vit_lamb_step_groups_dyn": [_P, _P, _P, _P, _P, _P, _I64, _I64, _P, _P, _I, _P, _I, _F, _F, _F, _I, _I, _P, _F, _P, _P],
     # (h, ema, p, n, weight, weight_dev, stream) / (h, p, ema, p_bf16, n, stream)
     "vit_ema_update": [_P, _P, _P, _I64, _F, _P, _P],
     "vit_ema_swap": [_P, _P, _P, _P, _I64, _P],
@@ -215,7 +221,8 @@ class Handle:
 
     def set_option(self, name: str, value: int):
         """Per-handle options (vit_handle_set_option): 'reserve_cus' (launch geometry of the calls made through THIS handle),
-        'grad_accumulate' (parameter-gradient outputs store old + new)."""
+        'grad_accumulate' (parameter-gradient outputs store old + new), 'lamb_passes' (measurement only: which of LAMB's
+        three launches a call makes)."""
         check(self.lib.vit_handle_set_option(self.h, name.encode(), int(value)), f"vit_handle_set_option({name})")
 
     def ensure_workspace(self, nbytes: int):

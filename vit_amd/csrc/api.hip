@@ -15,6 +15,7 @@ struct vit_ctx {
   int num_cus;             // compute units of the device (read once in vit_create): grid size of the persistent kernels
   int reserve_cus;         // vit_handle_set_option("reserve_cus"): -1 = the process default (vit_set_option), else this handle's own
   int grad_accumulate;     // vit_handle_set_option("grad_accumulate"): parameter-gradient outputs store old + new
+  int lamb_passes;         // vit_handle_set_option("lamb_passes"): which of vit_lamb_step*'s three launches are made (bits 1 | 2 | 4)
 };
 
 namespace vit {
@@ -55,6 +56,7 @@ int ctx_num_cus(vit_handle h) {
 }
 
 int ctx_grad_accumulate(vit_handle h) { return h ? h->grad_accumulate : 0; }
+int ctx_lamb_passes(vit_handle h) { return h ? h->lamb_passes : 7; }
 
 static thread_local size_t g_ws_needed = 0;  // vit_workspace_needed()
 void* ctx_claim(vit_handle h, size_t need_bytes, const char* who) {
@@ -92,6 +94,7 @@ int vit_create(vit_handle* out, int device) {
   c->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
   c->reserve_cus = -1;
   c->grad_accumulate = 0;
+  c->lamb_passes = 7;
   *out = c;
   return VIT_OK;
 }
@@ -145,7 +148,12 @@ int vit_handle_set_option(vit_handle h, const char* name, int value) {
     h->grad_accumulate = value;
     return VIT_OK;
   }
-  vit::set_error("vit_handle_set_option: '%s' is not a per-handle option (reserve_cus, grad_accumulate)", name);
+  if (strcmp(name, "lamb_passes") == 0) {
+    VIT_CHECK(value >= 1 && value <= 7, VIT_ERR_ARG, "vit_handle_set_option: lamb_passes takes 1 .. 7 (bits: moments 1, ratios 2, apply 4)");
+    h->lamb_passes = value;
+    return VIT_OK;
+  }
+  vit::set_error("vit_handle_set_option: '%s' is not a per-handle option (reserve_cus, grad_accumulate, lamb_passes)", name);
   return VIT_ERR_ARG;
 }
 

@@ -313,6 +313,8 @@ int ctx_num_cus(vit_handle h);  // compute units of the handle's device (api.hip
 // vit_handle_set_option("grad_accumulate"): non-zero = every parameter-gradient output of a call through this handle stores
 // old + new (new = what overwrite mode stores, bit for bit; one f32 add in the producer's final write or reduce stage)
 int ctx_grad_accumulate(vit_handle h);
+// vit_handle_set_option("lamb_passes"): bits 1 | 2 | 4 = the launches a vit_lamb_step* call makes (7: all three, the default)
+int ctx_lamb_passes(vit_handle h);
 // The handle's workspace, for a caller that needs `need_bytes` (> 0) from its front -- or NULL when it does not hold them (a
 // NULL handle holds none): the need is then recorded for vit_workspace_needed(), the error text is "`who`: needs N workspace
 // bytes, have M", and the caller returns VIT_ERR_WORKSPACE.  An entry point claims its WHOLE need (the maximum over its stages,

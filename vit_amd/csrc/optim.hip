@@ -5,6 +5,8 @@
 // table in device memory (torch.optim's param_groups in one launch); the by-value forms are that kernel without a table, their
 // scalars as its one row.  The `_groups_dyn` forms (a step captured as a hipGraph) read the bias corrections from the handle's
 // bound StepState; what a scheduler changes between replays lives in the group table.
+// LAMB (further down) is the one family that cannot be one pass: its per-tensor trust ratio needs two norms over the whole
+// tensor before p may be written -- three launches, 42 B per parameter, a deterministic segmented reduction in between.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -274,6 +276,234 @@ static int sgd_launch(const char* who, vit_handle h, bool dyn, float* p, const f
   return VIT_OK;
 }
 
+// ---- LAMB: per-tensor trust ratios over the flat buffer (include/vit_amd_optim.h) ---------------------------------------------
+// One segment is one parameter tensor.  Three launches: (1) moments + one (sum p^2, sum u^2) pair per tile, (2) one wave per
+// segment sums its tiles' pairs and writes trust[s], (3) u is recomputed -- lamb_u, the same function on the same stored m, v and
+// the still untouched p, so bit for bit -- and p and the shadow are written.  Tiles: LAMB_TILE elements, cut from each segment's
+// start, the last one short; a tile never straddles a segment, and which block works on it changes nothing it computes.
+// Tile k of segment s owns slot (a_s - lo) / LAMB_TILE + (s - s_first) + k of the partial buffer ([lo, hi) the run, a_s the
+// segment's start, s_first the run's first segment): strictly ascending over (s, k), computable from the table alone, below
+// n / LAMB_TILE + n_segments + 1 -- which the host can size without reading the table.  Slots no tile owns are never read.
+// Sums are f64 throughout (a lane's, a wave's butterfly, the block's four waves in order, a segment's tiles strided over one
+// wave): cheap beside 24 B of traffic per element, and it leaves the norms' error to the f32 elements alone.
+constexpr int LAMB_TILE = VIT_LAMB_TILE;
+
+struct LambShared { float b1, b2, omb1, omb2, eps, bc1, rsqrt_bc2; };
+
+// u = (m / bc1) / (sqrt(v) / sqrt(bc2) + eps) [+ wd * p]: the ONE statement of it, for pass 1's norm and pass 3's update
+__device__ __forceinline__ float lamb_u(float pp, float mm, float vv, float wd, const LambShared a) {
+  const float u = (mm / a.bc1) / fma_(sqrtf(vv), a.rsqrt_bc2, a.eps);
+  return wd != 0.f ? fma_(pp, wd, u) : u;
+}
+__device__ __forceinline__ f32x4 lamb_u(f32x4 pp, f32x4 mm, f32x4 vv, float wd, const LambShared a) {
+  f32x4 u;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) u[k] = lamb_u(pp[k], mm[k], vv[k], wd, a);
+  return u;
+}
+__device__ __forceinline__ void lamb_sq(double& acc, float x) { acc = __builtin_fma((double)x, (double)x, acc); }
+__device__ __forceinline__ void lamb_sq(double& acc, f32x4 x) {
+#pragma unroll
+  for (int k = 0; k < 4; ++k) lamb_sq(acc, x[k]);
+}
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// pass 1 on one vector / element: the moments are stored, p and u enter the tile's sums
+template <typename T>
+__device__ __forceinline__ void lamb_moments(const float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                             float* __restrict__ v, long at, float clip, const LambShared a, float wd,
+                                             double& sp, double& su) {
+  const T pp = *(const T*)(p + at);
+  const T gg = *(const T*)(g + at) * clip;
+  T mm = *(const T*)(m + at);
+  T vv = *(const T*)(v + at);
+  mm = fma_(mm, a.b1, gg * a.omb1);
+  vv = fma_(vv, a.b2, gg * gg * a.omb2);
+  *(T*)(m + at) = mm;
+  *(T*)(v + at) = vv;
+  lamb_sq(sp, pp);
+  lamb_sq(su, lamb_u(pp, mm, vv, wd, a));
+}
+// pass 3: p -= (lr * r) * u
+template <typename T>
+__device__ __forceinline__ void lamb_apply(float* __restrict__ p, const float* __restrict__ m, const float* __restrict__ v,
+                                           short* __restrict__ pb, long at, const LambShared a, float wd, float step) {
+  T pp = *(const T*)(p + at);
+  pp = fma_(lamb_u(pp, *(const T*)(m + at), *(const T*)(v + at), wd, a), -step, pp);
+  *(T*)(p + at) = pp;
+  if (pb) store_shadow(pb, at, pp);
+}
+
+// the run [lo, hi) in the table's coordinates with its first and last segment; without a table one segment, [0, n)
+struct LambRun { long lo, hi; int s_first, s_last; };
+__device__ __forceinline__ LambRun lamb_run(long n, long base, const long* __restrict__ seg_end, int n_seg) {
+  if (n_seg == 0) return {0, n, 0, 0};
+  return {base, base + n, seg_find(seg_end, n_seg, base), seg_find(seg_end, n_seg, base + n - 1)};
+}
+__device__ __forceinline__ long lamb_clamp(const LambRun& r, long x) { return x < r.lo ? r.lo : x > r.hi ? r.hi : x; }
+// segment s of the run, cut to the run (a run of whole segments cuts nothing), and its first slot
+struct LambSeg { long a, b, slot0; };
+__device__ __forceinline__ long lamb_seg_start(const LambRun& r, const long* __restrict__ seg_end, int s) {
+  return s > r.s_first ? lamb_clamp(r, seg_end[s - 1]) : r.lo;
+}
+__device__ __forceinline__ long lamb_slot0(const LambRun& r, long a, int s) { return (a - r.lo) / LAMB_TILE + (s - r.s_first); }
+__device__ __forceinline__ LambSeg lamb_seg(const LambRun& r, const long* __restrict__ seg_end, int s) {
+  const long a = lamb_seg_start(r, seg_end, s);
+  const long b = s < r.s_last ? lamb_clamp(r, seg_end[s]) : r.hi;
+  return {a, b, lamb_slot0(r, a, s)};
+}
+// the tile that owns slot w: its segment and [lo, hi) (hi <= lo: no tile owns the slot)
+struct LambTile { int s; long lo, hi; };
+__device__ __forceinline__ LambTile lamb_tile(const LambRun& r, const long* __restrict__ seg_end, long w) {
+  int lo = r.s_first, hi = r.s_last;  // the last s whose first slot is <= w (slot0 ascends strictly; s_first's is 0)
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (lamb_slot0(r, lamb_seg_start(r, seg_end, mid), mid) <= w) lo = mid; else hi = mid - 1;
+  }
+  const LambSeg sg = lamb_seg(r, seg_end, lo);
+  const long t0 = sg.a + (w - sg.slot0) * LAMB_TILE;
+  return {lo, t0, t0 + LAMB_TILE < sg.b ? t0 + LAMB_TILE : sg.b};
+}
+// the group's row of a tile / segment; false: a segment no group owns (group index < 0), which no pass touches
+__device__ __forceinline__ bool lamb_row(const int* __restrict__ seg_group, const GroupRow* __restrict__ rows, int n_groups,
+                                         int n_seg, int s, GroupRow& row) {
+  if (n_seg == 0) return true;
+  if (seg_group[s] < 0) return false;
+  row = seg_row(seg_group, rows, n_groups, s);
+  return true;
+}
+
+__global__ __launch_bounds__(STEP_BLOCK) void lamb_moments_kernel(const float* __restrict__ p, const float* __restrict__ g,
+                                                           float* __restrict__ m, float* __restrict__ v, long n, long base,
+                                                           const long* __restrict__ seg_end, const int* __restrict__ seg_group,
+                                                           int n_seg, const GroupRow* __restrict__ rows, int n_groups,
+                                                           GroupRow row, LambShared a, const StepState* __restrict__ st,
+                                                           const float* __restrict__ sqnorm, float max_norm,
+                                                           double* __restrict__ part, long n_slots) {
+  __shared__ double red[2 * (STEP_BLOCK / 64)];
+  const float clip = clip_coef(sqnorm, max_norm);
+  if (st) {
+    a.bc1 = st->bc1; a.rsqrt_bc2 = st->rsqrt_bc2;
+  }
+  const LambRun r = lamb_run(n, base, seg_end, n_seg);
+  for (long w = blockIdx.x; w < n_slots; w += gridDim.x) {  // block-uniform
+    const LambTile t = lamb_tile(r, seg_end, w);
+    if (t.hi <= t.lo || !lamb_row(seg_group, rows, n_groups, n_seg, t.s, row)) continue;
+    const long at0 = t.lo - r.lo, len = t.hi - t.lo, nv = len >> 2;
+    double sp = 0.0, su = 0.0;
+    for (long i = threadIdx.x; i < nv; i += STEP_BLOCK) lamb_moments<f32x4>(p, g, m, v, at0 + 4 * i, clip, a, row.wd, sp, su);
+    if (threadIdx.x < (len & 3)) lamb_moments<float>(p, g, m, v, at0 + (nv << 2) + threadIdx.x, clip, a, row.wd, sp, su);
+    sp = wave_sum_f64(sp);
+    su = wave_sum_f64(su);
+    if ((threadIdx.x & 63) == 0) {
+      red[2 * (threadIdx.x >> 6)] = sp;
+      red[2 * (threadIdx.x >> 6) + 1] = su;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      double tp = red[0], tu = red[1];
+      for (int k = 1; k < STEP_BLOCK / 64; ++k) { tp += red[2 * k]; tu += red[2 * k + 1]; }
+      part[2 * w] = tp;
+      part[2 * w + 1] = tu;
+    }
+    __syncthreads();  // `red` is free for the next tile
+  }
+}
+
+// one wave per segment: r = adapt and ||p|| > 0 and ||u|| > 0 ? ||p|| / ||u|| : 1, min(r, 1) under trust_clip
+__global__ __launch_bounds__(64) void lamb_ratio_kernel(long n, long base, const long* __restrict__ seg_end,
+                                                      const int* __restrict__ seg_group, int n_seg,
+                                                      const GroupRow* __restrict__ rows, int n_groups, GroupRow row,
+                                                      int always_adapt, int trust_clip, const double* __restrict__ part,
+                                                      float* __restrict__ trust) {
+  const LambRun r = lamb_run(n, base, seg_end, n_seg);
+  for (long s = (long)r.s_first + blockIdx.x; s <= r.s_last; s += gridDim.x) {
+    if (!lamb_row(seg_group, rows, n_groups, n_seg, (int)s, row)) continue;
+    const LambSeg sg = lamb_seg(r, seg_end, (int)s);
+    if (sg.b <= sg.a) continue;
+    const long tiles = (sg.b - sg.a + LAMB_TILE - 1) / LAMB_TILE;
+    double sp = 0.0, su = 0.0;
+    for (long k = threadIdx.x; k < tiles; k += 64) {
+      sp += part[2 * (sg.slot0 + k)];
+      su += part[2 * (sg.slot0 + k) + 1];
+    }
+    sp = wave_sum_f64(sp);
+    su = wave_sum_f64(su);
+    if (threadIdx.x == 0) {
+      float ratio = 1.f;
+      if ((row.wd != 0.f || always_adapt) && sp > 0.0 && su > 0.0) ratio = (float)(sqrt(sp) / sqrt(su));
+      trust[s] = trust_clip ? fminf(ratio, 1.f) : ratio;
+    }
+  }
+}
+
+__global__ __launch_bounds__(STEP_BLOCK) void lamb_apply_kernel(float* __restrict__ p, const float* __restrict__ m,
+                                                         const float* __restrict__ v, short* __restrict__ pb, long n, long base,
+                                                         const long* __restrict__ seg_end, const int* __restrict__ seg_group,
+                                                         int n_seg, const GroupRow* __restrict__ rows, int n_groups, GroupRow row,
+                                                         LambShared a, const StepState* __restrict__ st,
+                                                         const float* __restrict__ trust, long n_slots) {
+  if (st) {
+    a.bc1 = st->bc1; a.rsqrt_bc2 = st->rsqrt_bc2;
+  }
+  const LambRun r = lamb_run(n, base, seg_end, n_seg);
+  for (long w = blockIdx.x; w < n_slots; w += gridDim.x) {  // block-uniform
+    const LambTile t = lamb_tile(r, seg_end, w);
+    if (t.hi <= t.lo || !lamb_row(seg_group, rows, n_groups, n_seg, t.s, row)) continue;
+    const float step = row.lr * trust[t.s];
+    const long at0 = t.lo - r.lo, len = t.hi - t.lo, nv = len >> 2;
+    for (long i = threadIdx.x; i < nv; i += STEP_BLOCK) lamb_apply<f32x4>(p, m, v, pb, at0 + 4 * i, a, row.wd, step);
+    if (threadIdx.x < (len & 3)) lamb_apply<float>(p, m, v, pb, at0 + (nv << 2) + threadIdx.x, a, row.wd, step);
+  }
+}
+
+static int lamb_launch(const char* who, vit_handle h, bool dyn, float* p, const float* g, float* m, float* v, void* p_bf16,
+                       int64_t n, const GroupTable* table, GroupRow row, float beta1, float beta2, float eps, int always_adapt,
+                       int trust_clip, int step, const float* sqnorm, float max_norm, float* trust, vit_stream stream) {
+  const StepState* st = dyn ? ctx_step_state(h) : nullptr;
+  VIT_CHECK(!dyn || st, VIT_ERR_ARG, "%s: no step state bound (vit_step_state_bind)", who);
+  VIT_CHECK(p && g && m && v && (table || n > 0) && (dyn || step >= 1), VIT_ERR_ARG, "%s: bad arguments", who);
+  if (table) {
+    if (int rc = groups_check(who, n, *table)) return rc;
+    VIT_CHECK(trust, VIT_ERR_ARG, "%s: null trust (one f32 per segment of the table)", who);
+  }
+  const GroupTable t = table ? *table : GroupTable{};
+  // slots of the partial buffer: what the tiles of ANY table of n_segments segments over n elements stay below
+  const long n_slots = table ? (long)(n / LAMB_TILE) + t.n_segments + 1 : (long)((n + LAMB_TILE - 1) / LAMB_TILE);
+  char* ws = (char*)ctx_claim(h, 16 + (size_t)n_slots * 2 * sizeof(double), who);
+  if (!ws) return VIT_ERR_WORKSPACE;
+  if (!trust) trust = (float*)ws;  // by value: the one ratio nobody asked for
+  double* part = (double*)(ws + 16);
+  const double bc1 = dyn ? 1.0 : 1.0 - pow((double)beta1, step), bc2 = dyn ? 1.0 : 1.0 - pow((double)beta2, step);
+  const LambShared a = {beta1, beta2, 1.f - beta1, 1.f - beta2, eps, (float)bc1, (float)(1.0 / sqrt(bc2))};
+  const dim3 grid(grid_for(n_slots, 1, 8192));
+  hipStream_t s = (hipStream_t)stream;
+  const int passes = ctx_lamb_passes(h);  // 7 unless a measurement asked for single passes (vit_handle_set_option)
+  if (passes & 1) {
+    hipLaunchKernelGGL(lamb_moments_kernel, grid, dim3(STEP_BLOCK), 0, s, p, g, m, v, (long)n, (long)t.base,
+                       (const long*)t.seg_end, (const int*)t.seg_group, t.n_segments, (const GroupRow*)t.groups, t.n_groups, row,
+                       a, st, sqnorm, max_norm, part, n_slots);
+    VIT_LAUNCH_CHECK();
+  }
+  if (passes & 2) {
+    hipLaunchKernelGGL(lamb_ratio_kernel, dim3(grid_for(table ? t.n_segments : 1, 1, 4096)), dim3(64), 0, s, (long)n,
+                       (long)t.base, (const long*)t.seg_end, (const int*)t.seg_group, t.n_segments, (const GroupRow*)t.groups,
+                       t.n_groups, row, always_adapt, trust_clip, part, trust);
+    VIT_LAUNCH_CHECK();
+  }
+  if (passes & 4) {
+    hipLaunchKernelGGL(lamb_apply_kernel, grid, dim3(STEP_BLOCK), 0, s, p, m, v, (short*)p_bf16, (long)n, (long)t.base,
+                       (const long*)t.seg_end, (const int*)t.seg_group, t.n_segments, (const GroupRow*)t.groups, t.n_groups, row,
+                       a, st, trust, n_slots);
+    VIT_LAUNCH_CHECK();
+  }
+  return VIT_OK;
+}
+
 }  // namespace vit
 
 using namespace vit;
@@ -341,6 +571,29 @@ int vit_sgd_step_groups_dyn(vit_handle h, float* p, const float* g, float* buf, 
                             int n_groups, int nesterov, const float* sqnorm, float max_norm, vit_stream stream) {
   const GroupTable t = {base, seg_end, seg_group, n_segments, groups, n_groups};
   return sgd_launch("vit_sgd_step_groups_dyn", h, true, p, g, buf, p_bf16, n, &t, {}, nesterov, sqnorm, max_norm, stream);
+}
+
+int vit_lamb_step(vit_handle h, float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, float lr, float beta1,
+                  float beta2, float eps, float weight_decay, int always_adapt, int trust_clip, int step, const float* sqnorm,
+                  float max_norm, float* trust, vit_stream stream) {
+  return lamb_launch("vit_lamb_step", h, false, p, g, m, v, p_bf16, n, nullptr, {lr, weight_decay, 0.f, 0.f}, beta1, beta2, eps,
+                     always_adapt, trust_clip, step, sqnorm, max_norm, trust, stream);
+}
+int vit_lamb_step_groups(vit_handle h, float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, int64_t base,
+                         const int64_t* seg_end, const int32_t* seg_group, int n_segments, const float* groups, int n_groups,
+                         float beta1, float beta2, float eps, int always_adapt, int trust_clip, int step, const float* sqnorm,
+                         float max_norm, float* trust, vit_stream stream) {
+  const GroupTable t = {base, seg_end, seg_group, n_segments, groups, n_groups};
+  return lamb_launch("vit_lamb_step_groups", h, false, p, g, m, v, p_bf16, n, &t, {}, beta1, beta2, eps, always_adapt,
+                     trust_clip, step, sqnorm, max_norm, trust, stream);
+}
+int vit_lamb_step_groups_dyn(vit_handle h, float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, int64_t base,
+                             const int64_t* seg_end, const int32_t* seg_group, int n_segments, const float* groups,
+                             int n_groups, float beta1, float beta2, float eps, int always_adapt, int trust_clip,
+                             const float* sqnorm, float max_norm, float* trust, vit_stream stream) {
+  const GroupTable t = {base, seg_end, seg_group, n_segments, groups, n_groups};
+  return lamb_launch("vit_lamb_step_groups_dyn", h, true, p, g, m, v, p_bf16, n, &t, {}, beta1, beta2, eps, always_adapt,
+                     trust_clip, 0, sqnorm, max_norm, trust, stream);
 }
 
 int vit_optim_groups_write(vit_handle h, float* groups, int n_groups, const float* values, vit_stream stream) {

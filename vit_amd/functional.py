@@ -626,6 +626,72 @@ def sgd_step_groups(p, g, buf, p_bf16, tables: GroupTables, *, base=0, nesterov=
            *_groups_args(tables, base), int(bool(nesterov)), _ptr(sqnorm), max_norm, _stream(p))
 
 
+# ------------------------------------------------------------------------------------------------ optimizer: LAMB
+LAMB_TILE = 4096  # VIT_LAMB_TILE (include/vit_amd_optim.h): elements per tile of the norms, cut from each segment's start
+
+
+class ParamTables(GroupTables):
+    """`GroupTables` with one segment per parameter tensor, as LAMB's per-tensor norms need them (`optim_param_tables`).
+    `starts` / `ends` / `owners` mirror the segment table on the host (owner -1: a gap no group owns, a segment of its own);
+    `segment_of[i]` is the segment number of the i-th triple the table was built from."""
+
+    def __init__(self, seg_end, seg_group, groups, starts, ends, owners, segment_of):
+        super().__init__(seg_end, seg_group, groups)
+        self.starts, self.ends, self.owners, self.segment_of = starts, ends, owners, segment_of
+
+    def check_run(self, base: int, n: int):
+        """A LAMB call covers whole segments: `base` and `base + n` are segment boundaries, else ValueError."""
+        base, n = int(base), int(n)
+        bounds = set(self.starts) | set(self.ends)
+        if n <= 0 or base not in bounds or base + n not in bounds:
+            raise ValueError(f"lamb_step_groups: the run [{base}, {base + n}) cuts a parameter tensor; a trust ratio is a norm "
+                             f"over a whole tensor, so a run starts and ends on segment boundaries")
+
+
+def optim_param_tables(triples, n_groups: int, device, total: Optional[int] = None) -> ParamTables:
+    """`optim_group_tables` without the merging: every (offset, numel, group) triple -- one parameter tensor with its alignment
+    pad -- is a segment of its own, whoever owns its neighbours, and a gap between two triples (or in front of the first) is a
+    segment of its own with group index -1, which the LAMB kernels neither read nor write.  Same validation."""
+    checked = optim_group_tables(triples, n_groups, "cpu", total)  # the validation, stated once (its tables are dropped)
+    del checked
+    starts, ends, owners, segment_of, prev_end = [], [], [], [], 0
+    for off, numel, gi in ((int(o), int(k), int(gi)) for o, k, gi in triples):
+        if off > prev_end:
+            starts.append(prev_end); ends.append(off); owners.append(-1)
+        segment_of.append(len(ends))
+        starts.append(off); ends.append(off + numel); owners.append(gi)
+        prev_end = off + numel
+    return ParamTables(torch.tensor(ends, dtype=torch.int64, device=device), torch.tensor(owners, dtype=torch.int32, device=device),
+                       torch.zeros(n_groups, 4, dtype=torch.float32, device=device), starts, ends, owners, segment_of)
+
+
+def lamb_step(p, g, m, v, p_bf16, *, lr, beta1=0.9, beta2=0.999, eps=1e-6, weight_decay=0.0, always_adapt=False,
+              trust_clip=False, step=1, sqnorm=None, max_norm=0.0, trust=None, n: Optional[int] = None):
+    """LAMB on one tensor, by value (include/vit_amd_optim.h); `trust` (one f32, optional) receives the tensor's trust ratio."""
+    h = _h(p)
+    n = p.numel() if n is None else n
+    h.call("vit_lamb_step", p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), _ptr(p_bf16), n, lr, beta1, beta2, eps,
+           weight_decay, int(bool(always_adapt)), int(bool(trust_clip)), step, _ptr(sqnorm), max_norm, _ptr(trust), _stream(p))
+
+
+def lamb_step_groups(p, g, m, v, p_bf16, tables: ParamTables, trust, *, base=0, beta1=0.9, beta2=0.999, eps=1e-6,
+                     always_adapt=False, trust_clip=False, step=1, sqnorm=None, max_norm=0.0, n: Optional[int] = None,
+                     dyn: bool = False):
+    """LAMB over p = buffer[base : base + n], whole segments of the per-parameter table (a run that cuts one: ValueError), with
+    each tensor's group's lr / weight_decay; `trust` (f32, `tables.n_segments` entries) receives the ratios of the run's
+    segments.  `dyn` (inside a captured step): the bias corrections come from the handle's bound record instead of `step`."""
+    n = p.numel() if n is None else n
+    if not isinstance(tables, ParamTables):
+        raise ValueError("lamb_step_groups needs the per-parameter tables (optim_param_tables): merged runs would merge the norms")
+    tables.check_run(base, n)
+    _chk(trust, torch.float32, "lamb_step_groups trust")
+    if trust.numel() < tables.n_segments:
+        raise ValueError(f"lamb_step_groups: trust holds {trust.numel()} entries for {tables.n_segments} segments")
+    _h(p).call("vit_lamb_step_groups_dyn" if dyn else "vit_lamb_step_groups", p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(),
+           _ptr(p_bf16), n, *_groups_args(tables, base), beta1, beta2, eps, int(bool(always_adapt)), int(bool(trust_clip)),
+           *(() if dyn else (step,)), _ptr(sqnorm), max_norm, trust.data_ptr(), _stream(p))
+
+
 # ------------------------------------------------------------------------------------------------ weight averaging
 def ema_update(ema, p, weight: float = 0.0, *, weight_dev=None, n: Optional[int] = None):
     """ema <- torch.lerp(ema, p, weight) over the first `n` elements (include/vit_amd_ema.h); `weight` is 1 - decay, already

@@ -13,7 +13,7 @@ Stochastic depth (`model.drop_path_rate`) needs no mechanism of its own: the fro
 the per-sample gate is drawn from the record's keys like every dropout mask, so each replay draws a fresh one.
 
 Scope: one process, one GPU (the RCCL exchange of N > 1 is not captured), a fused optimizer (vit_amd/optimizer.py:
-FusedAdamW, FusedSGD), no trainable input preprocessor, a fixed batch shape.  The reference's step semantics are unchanged
+FusedAdamW, FusedLamb, FusedSGD), no trainable input preprocessor, a fixed batch shape.  The reference's step semantics are unchanged
 (zero_grad -> forward, dropout on -> backward -> clip the global norm -> optimizer step: src/basemodule.py:230-251); only the
 seed schedule of the dropout masks differs from the eager path
 (masks are implementation-defined in the reference too).  The eager path stays the default everywhere but bench.py.
@@ -47,7 +47,7 @@ class GraphedTrainStep:
         model = module.model
         eng = model.engine
         if not isinstance(optimizer, FusedOptimizer):
-            raise TypeError("GraphedTrainStep needs a fused optimizer (FusedAdamW, FusedSGD)")
+            raise TypeError("GraphedTrainStep needs a fused optimizer (FusedAdamW, FusedLamb, FusedSGD)")
         if optimizer._extras or model.preprocessor is not None:
             raise ValueError("GraphedTrainStep: a trainable input preprocessor is outside the captured step")
         if getattr(module, "noise_level", 0):

@@ -7,6 +7,8 @@ clip coefficient, the update and the bf16 shadow refresh in a single pass -- `Fu
 `adam_l2` torch.optim.Adam, whose weight decay is L2 in the gradient) and `FusedSGD` (torch.optim.SGD), each verified
 against its torch class in tests/.  Any other optimizer type falls through to torch.optim exactly as in the reference
 (src/opt/optimizer.py:14-26,108; it then works on the `.grad` views the model's backward produces).
+One type beside the reference's: `lamb` -> `FusedLamb` (timm's Lamb; torch.optim has none, so there is nothing to fall
+through to and the type is an error on any other model), verified against a float64 restatement in tests/test_lamb_gpu.py.
 """
 from __future__ import annotations
 
@@ -18,7 +20,7 @@ import torch
 
 from . import functional as vf
 
-__all__ = ["OptModule", "FusedOptimizer", "FusedAdamW", "FusedSGD", "build_param_groups"]
+__all__ = ["OptModule", "FusedOptimizer", "FusedAdamW", "FusedLamb", "FusedSGD", "build_param_groups"]
 
 
 class FusedOptimizer(torch.optim.Optimizer):
@@ -119,12 +121,16 @@ class FusedOptimizer(torch.optim.Optimizer):
             for name, p in zip(self.model._param_names, self.model._param_list):
                 off, _ = lay.entries[name]
                 if off < lay.n_trainable and id(p) in self._group_index:
-                    triples.append((off, (lay.numel(name) + 7) // 8 * 8, self._group_index[id(p)]))
+                    triples.append((off, (lay.numel(name) + 7) // 8 * 8, self._group_index[id(p)], name))
             if not triples:
                 raise ValueError("no parameter group owns a parameter of the model's flat buffer")
             triples.sort()
-            self._part = (sig, flat.device, vf.optim_group_tables(triples, len(self.param_groups), flat.device))
+            self._part = (sig, flat.device, self._build_tables(triples, flat.device))
         return self._part
+
+    def _build_tables(self, triples, device):
+        """The device tables over (offset, padded numel, group, name), sorted by offset: neighbours of one group merge."""
+        return vf.optim_group_tables([t[:3] for t in triples], len(self.param_groups), device)
 
     def _check_shared(self):
         """beta1 / beta2 / eps, or nesterov / dampening, are one kernel argument for the whole launch."""
@@ -425,6 +431,83 @@ class FusedAdamW(FusedOptimizer):
         self._load_groups(sd)
 
 
+class FusedLamb(FusedAdamW):
+    """LAMB over MyViT's flat buffers (see FusedOptimizer): timm's `Lamb`, the optimizer DeiT-III trains ViT-B with at a global
+    batch of 2048, with the fused clip (`set_grad_clip`) in the place of timm's `max_grad_norm`; the formulas stand in
+    include/vit_amd_optim.h.  Adam's moments, then per parameter tensor the trust ratio r = ||p|| / ||u|| scales the update
+    (r = 1 for a tensor whose group has weight_decay 0 unless `always_adapt`; `trust_clip`: min(r, 1)).  The norms are per
+    TENSOR, so the segment table has one segment per parameter (vf.optim_param_tables), not FusedAdamW's merged runs.
+    `state_dict()` / `load_state_dict()` are FusedAdamW's (torch.optim.AdamW's format: LAMB keeps the same two moments), so a
+    FusedAdamW checkpoint loads and `Trainer`'s exact resume works unchanged.
+    `last_trust_ratios`: (names, ratios) of the last step -- `ratios` the device tensor the kernels wrote, one f32 per entry of
+    `names` (the parameters in table order); None before the first step.  Entries of tensors the last step did not update
+    (frozen ones) keep their previous value (1 initially).
+    Under the 'zero1' exchange a rank's shard cuts tensors and a per-tensor norm would need a collective: not supported
+    (`attach_reducer` raises ValueError); the all-reduce exchange needs nothing, every rank computes the same ratios."""
+
+    _SHARED = ("betas", "eps", "always_adapt", "trust_clip")
+
+    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.0, always_adapt: bool = False,
+                 trust_clip: bool = False, param_groups=None):
+        FusedOptimizer.__init__(self, model, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
+                                                  always_adapt=bool(always_adapt), trust_clip=bool(trust_clip)), param_groups)
+        self.adam_l2 = False
+        self._m = None
+        self._v = None
+        self._trust = None        # one f32 per segment of the table, written by the kernels
+        self._trust_extra = {}    # id(p) -> one f32, for a parameter outside the flat buffer
+        self._stepped = False
+
+    def attach_reducer(self, reducer):
+        if getattr(reducer, "mode", "") == "zero1":
+            raise ValueError("FusedLamb does not support the 'zero1' exchange: its shards cut parameter tensors and a trust "
+                             "ratio is a norm over a whole tensor; use the all-reduce exchange")
+        super().attach_reducer(reducer)
+
+    def _build_tables(self, triples, device):
+        """One segment per parameter tensor, and a trust entry per segment (1 until a step writes it)."""
+        tables = vf.optim_param_tables([t[:3] for t in triples], len(self.param_groups), device)
+        self._trust_names = [t[3] for t in triples]
+        self._trust_index = torch.tensor(tables.segment_of, dtype=torch.long, device=device)
+        self._trust = torch.ones(tables.n_segments, dtype=torch.float32, device=device)
+        return tables
+
+    def _launch(self, lo, hi, tables, shadow, sq, dyn=False):
+        eng, g0 = self.model.engine, self.param_groups[0]
+        self._stepped = True
+        vf.lamb_step_groups(eng.flat[lo:hi], eng.grads[lo:hi], self._m[lo:hi], self._v[lo:hi],
+                            None if shadow is None else shadow[lo:hi], tables, self._trust, base=lo, beta1=g0["betas"][0],
+                            beta2=g0["betas"][1], eps=g0["eps"], always_adapt=g0["always_adapt"], trust_clip=g0["trust_clip"],
+                            step=self._step, sqnorm=sq, max_norm=float(self._clip or 0.0), dyn=dyn)
+
+    def _update_extra(self, p, grp, sq):
+        m, v = self._extra_buffers(p)
+        trust = self._trust_extra.get(id(p))
+        if trust is None or trust.device != p.device:
+            trust = self._trust_extra[id(p)] = torch.ones(1, dtype=torch.float32, device=p.device)
+        self._stepped = True
+        vf.lamb_step(p.data.view(-1), p.grad.contiguous().view(-1), m, v, None, lr=float(grp["lr"]), beta1=grp["betas"][0],
+                     beta2=grp["betas"][1], eps=grp["eps"], weight_decay=grp["weight_decay"], always_adapt=grp["always_adapt"],
+                     trust_clip=grp["trust_clip"], step=self._step, sqnorm=sq, max_norm=float(self._clip or 0.0), trust=trust)
+
+    @property
+    def last_trust_ratios(self):
+        """(names, ratios): the last step's trust ratio of every parameter a group owns, the flat buffer's in table order, then
+        the parameters outside it; `ratios` is a device tensor (reading it synchronises).  None before the first step."""
+        if not self._stepped:
+            return None
+        names, parts = [], []
+        if self._trust is not None:
+            names += self._trust_names
+            parts.append(self._trust[self._trust_index])
+        by_id = {id(p): n for n, p in self.model.named_parameters()}
+        for p in self._extras:
+            if id(p) in self._trust_extra:
+                names.append(by_id.get(id(p), "?"))
+                parts.append(self._trust_extra[id(p)])
+        return names, torch.cat(parts)
+
+
 class FusedSGD(FusedOptimizer):
     """SGD over MyViT's flat buffers (see FusedOptimizer).  `step()` == torch.optim.SGD.step() with dampening 0.
     `param_groups[0]` carries torch SGD's keys, and `lr` and `momentum` are read from it on every step: a one-cycle scheduler
@@ -615,7 +698,8 @@ class OptModule:
     a one-cycle scheduler gets the groups' rates as its `max_lr` list (a scalar would flatten them)."""
 
     def __init__(self, lr, monitor_metric="loss", opt_type="adam", weight_decay=0.0, lr_scheduler_name=None,
-                 warmup_ratio=0.0, warmup_epochs=None, no_decay=None, layer_decay=None, **kwargs) -> None:
+                 warmup_ratio=0.0, warmup_epochs=None, no_decay=None, layer_decay=None, lamb_options=None, **kwargs) -> None:
+        self.lamb_options = dict(lamb_options or {})  # eps / always_adapt / trust_clip of `type: lamb`
         self.no_decay = no_decay
         self.layer_decay = None if layer_decay is None else float(layer_decay)
         self.lr = float(lr)
@@ -642,6 +726,8 @@ class OptModule:
         for key in ("no_decay", "layer_decay"):  # absent by default: the reference's call, argument for argument
             if config.get(key) is not None and config.get(key) is not False:
                 common[key] = config[key]
+        if common["opt_type"] == "lamb":  # read only for this type
+            common["lamb_options"] = {k: config[k] for k in ("eps", "always_adapt", "trust_clip") if config.get(k) is not None}
         if "lr_sch" not in config:
             return cls(**common)
         name = config["lr_sch"].lower()
@@ -652,6 +738,11 @@ class OptModule:
 
         groups = build_param_groups(model, self.lr, self.weight_decay, self.no_decay, self.layer_decay)
         fused = {} if groups is None else {"param_groups": groups}
+        if self.opt_type == "lamb":  # ahead of `opt_fns`, which stays the reference's table: torch.optim has no LAMB
+            if not isinstance(model, MyViT):
+                raise ValueError("opt.type 'lamb' is the fused LAMB over a MyViT's flat buffers (FusedLamb); torch has no LAMB "
+                                 f"to fall through to for a {type(model).__name__}")
+            return FusedLamb(model, lr=self.lr, weight_decay=self.weight_decay, **self.lamb_options, **fused)
         if isinstance(model, MyViT) and self.opt_type in ("adam", "adamw"):
             # torch.optim.Adam's weight_decay is L2-in-the-gradient; with the reference's default weight_decay=0
             # (optimizer.py:51) Adam == AdamW, and only with a decay does 'adam' need the L2 form of the kernel
