@@ -39,7 +39,7 @@ typedef enum { VIT_F32 = 0, VIT_BF16 = 1 } vit_dtype;
  * GELU_GRAD: as GELU but aux_out = gelu'(pre-activation) -- the forward already holds Phi and exp(-x^2/2), so saving the
  * derivative costs two FMAs there and the backward GEMM (MUL_AUX: C = acc * aux_in) needs no transcendental at all. */
 typedef enum { VIT_ACT_NONE = 0, VIT_ACT_GELU = 1, VIT_ACT_DGELU = 2, VIT_ACT_GELU_GRAD = 3, VIT_ACT_MUL_AUX = 4 } vit_act;
-typedef enum { VIT_LOSS_MSE = 0, VIT_LOSS_L1 = 1, VIT_LOSS_CE = 2 } vit_loss;
+typedef enum { VIT_LOSS_MSE = 0, VIT_LOSS_L1 = 1, VIT_LOSS_CE = 2, VIT_LOSS_SOFT_CE = 3, VIT_LOSS_BCE = 4 } vit_loss;
 
 int vit_version(void);
 const char* vit_last_error(void);
@@ -330,10 +330,19 @@ int vit_cast_bf16_f32(vit_handle h, const void* src, float* dst, int64_t n, floa
 /* ------------------------------------------------------------------------------------- Head + loss
  * logits[B, C] = cls_rows * W^T + b, cls_rows = last_hidden[:, 0, :] (specvit.py:78-81); loss (specvit.py:83-89):
  * MSE / L1 over logits.view(-1) vs labels.view(-1) (mean), or cross-entropy over int64 labels (mean).
- * last_hidden: f32 [B, T, D]; loss_out: f32 [1]. labels may be NULL (loss_out untouched). */
+ * last_hidden: f32 [B, T, D]; loss_out: f32 [1]. labels may be NULL (loss_out untouched).
+ * The soft-target kinds (the targets vit_mix_targets writes, vit_amd_mix.h; torch's F.cross_entropy with probability targets and
+ * F.binary_cross_entropy_with_logits): labels are f32 [B, C] targets t,
+ *   VIT_LOSS_SOFT_CE: loss = (1/B) sum_b sum_c -t[b,c] log_softmax(z[b])[c];  dz = (softmax(z) * sum_c t - t) * up / B
+ *   VIT_LOSS_BCE:     loss = mean over B*C of max(z, 0) - z t + log1p(exp(-|z|));  dz = (sigmoid(z) - t) * up / (B*C)
+ * C is 10 .. 1000 there, so their forward runs one wave per sample (lanes stride over C, wave max / sum), leaves the row losses
+ * in the workspace (B floats: the call's need, claimed before the first launch) and a second single-block stage forms the
+ * mean in a fixed order: deterministic.  MSE / L1 / CE keep their single-block kernel and need no workspace. */
 int vit_head_loss_fwd(vit_handle h, const float* last_hidden, const float* W, const float* b, const void* labels,
                       float* logits, float* loss_out, int B, int T, int D, int C, int loss_kind, vit_stream stream);
-/* d(last_hidden) (zero except the CLS rows), dW [C,D], db [C] given dloss (f32 [1], the upstream scalar gradient). */
+/* d(last_hidden) (zero except the CLS rows), dW [C,D], db [C] given dloss (f32 [1], the upstream scalar gradient).  The
+ * soft-target kinds form dz with one wave per sample, then d(last_hidden) with one lane per column; dW / db as for every kind
+ * (`accumulate` / "grad_accumulate" included).  Workspace: B*C floats (dz), every kind. */
 int vit_head_loss_bwd(vit_handle h, const float* last_hidden, const float* W, const float* logits, const void* labels,
                       const float* dloss, float* dlast_hidden, float* dW, float* db, int B, int T, int D, int C,
                       int loss_kind, int accumulate, vit_stream stream);
@@ -371,5 +380,8 @@ int vit_adamw_step(vit_handle h, float* p, const float* g, float* m, float* v, v
 /* LayerScale (`model.layer_scale_init`) as a reparametrisation at weight size: the fold of lambda into the out-projection /
  * FC2 operands and the pass that unfolds their raw gradients.  Declared in their own header, part of this ABI. */
 #include "vit_amd_layerscale.h"
+/* Mixup / CutMix of the batch and its labels (`augment:`): vit_mix_plan_write, vit_mix_signal, vit_mix_targets.  Declared in
+ * their own header, part of this ABI. */
+#include "vit_amd_mix.h"
 
 #endif /* VIT_AMD_H_ */

@@ -16,6 +16,8 @@ VIT_OK, VIT_ERR_WORKSPACE = 0, -4
 VIT_F32, VIT_BF16 = 0, 1
 ACT_NONE, ACT_GELU, ACT_DGELU, ACT_GELU_GRAD, ACT_MUL_AUX = 0, 1, 2, 3, 4
 LOSS_MSE, LOSS_L1, LOSS_CE = 0, 1, 2
+LOSS_SOFT_CE, LOSS_BCE = 3, 4  # the soft-target kinds: labels are f32 [B, C] targets
+MIX_LABELS_F32, MIX_LABELS_I64 = 0, 1
 
 
 class VitError(RuntimeError):
@@ -57,6 +59,12 @@ class LayerScaleEntry(C.Structure):
         ("rows", C.c_int32), ("cols", C.c_int32),
         ("reserved", C.c_int64),
     ]
+
+
+class MixRow(C.Structure):
+    """vit_mix_row (include/vit_amd_mix.h): one row of a Mixup / CutMix plan, 32 bytes."""
+    _fields_ = [("w", C.c_float), ("u", C.c_float), ("lo", C.c_int32), ("hi", C.c_int32), ("wy", C.c_float), ("uy", C.c_float),
+                ("reserved", C.c_int32 * 2)]
 
 
 _P, _I, _F, _U64, _I64, _SZ = C.c_void_p, C.c_int, C.c_float, C.c_uint64, C.c_int64, C.c_size_t
@@ -134,6 +142,11 @@ _PROTOS = {
     "vit_layer_scale_table_write": [_P, _P, C.POINTER(LayerScaleEntry), _I, _P],
     "vit_layer_scale_fold": [_P, _P, _I, _I, _I, _P],
     "vit_layer_scale_grad": [_P, _P, _I, _I, _I, _P],
+    # (h, plan_dev, n_rows, host_rows, stream) / (h, x, out, plan_dev, n_rows, B, L, stream) /
+    # (h, labels, label_kind, out, plan_dev, n_rows, B, C, on, off, stream)
+    "vit_mix_plan_write": [_P, _P, _I, C.POINTER(MixRow), _P],
+    "vit_mix_signal": [_P, _P, _P, _P, _I, _I, _I, _P],
+    "vit_mix_targets": [_P, _P, _I, _P, _P, _I, _I, _I, _F, _F, _P],
 }
 _RESTYPES = {"vit_last_error": C.c_char_p, "vit_last_gemm_kernel": C.c_char_p, "vit_workspace_needed": C.c_size_t}
 
@@ -142,7 +155,7 @@ _lock = threading.Lock()
 
 
 def declared_symbols(header_path: str = HEADER_PATH):
-    """Every function the C header declares, the headers it includes from its own directory (vit_amd_cov.h, vit_amd_optim.h, vit_amd_ema.h, vit_amd_droppath.h, vit_amd_layerscale.h) included (used by
+    """Every function the C header declares, the headers it includes from its own directory (vit_amd_cov.h, vit_amd_optim.h, vit_amd_ema.h, vit_amd_droppath.h, vit_amd_layerscale.h, vit_amd_mix.h) included (used by
     the CPU test that checks the library exports them all)."""
     seen, names, todo = set(), set(), [os.path.abspath(header_path)]
     while todo:

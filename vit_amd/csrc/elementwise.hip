@@ -2,6 +2,8 @@
 // backward, dropout-backward cast, deterministic column sums (bias gradients), head + loss, global grad norm (the optimizer
 // steps that consume it: optim.hip).
 // All are vectorised (8-16 B per lane), grid-stride, and free of float atomics (reference: deterministic=True).
+#include <math.h>
+
 #include <algorithm>
 
 #include "common.h"
@@ -384,6 +386,85 @@ __global__ void head_bwd_params_kernel(const float* __restrict__ last, const flo
   }
 }
 
+// ---- the soft-target kinds (VIT_LOSS_SOFT_CE, VIT_LOSS_BCE: labels are f32 [B, C] targets).  C is 10 .. 1000 here, so a sample
+// is a wave's work, not a thread's: lanes stride over C, wave max / sum; 4 samples per block.
+__device__ __forceinline__ void soft_row_stats(const float* __restrict__ z, int C, int lane, float& mx, float& se) {
+  mx = -INFINITY;
+  for (int c = lane; c < C; c += 64) mx = fmaxf(mx, z[c]);
+  mx = wave_max(mx);
+  se = 0.f;
+  for (int c = lane; c < C; c += 64) se += __expf(z[c] - mx);
+  se = wave_sum(se);
+}
+// row_loss[b] = sum_c -t log_softmax(z)_c  |  sum_c max(z, 0) - z t + log1p(exp(-|z|))
+__global__ __launch_bounds__(256) void soft_loss_rows_kernel(const float* __restrict__ logits, const float* __restrict__ tgt,
+                                                             float* __restrict__ row_loss, int B, int C, int kind) {
+  const int b = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (b >= B) return;
+  const float* z = logits + (long)b * C;
+  const float* t = tgt + (long)b * C;
+  float a = 0.f;
+  if (kind == VIT_LOSS_SOFT_CE) {
+    float mx, se;
+    soft_row_stats(z, C, lane, mx, se);
+    const float lse = mx + __logf(se);
+    for (int c = lane; c < C; c += 64) a += t[c] * (lse - z[c]);
+  } else {
+    for (int c = lane; c < C; c += 64) a += (fmaxf(z[c], 0.f) - z[c] * t[c]) + log1pf(__expf(-fabsf(z[c])));
+  }
+  a = wave_sum(a);
+  if (lane == 0) row_loss[b] = a;
+}
+// single block: loss = (sum of the row losses, fixed order) * inv_count
+__global__ __launch_bounds__(256) void soft_loss_mean_kernel(const float* __restrict__ row_loss, int B, float* __restrict__ loss,
+                                                             float inv_count) {
+  __shared__ float red[256];
+  float a = 0.f;
+  for (int b = threadIdx.x; b < B; b += 256) a += row_loss[b];
+  red[threadIdx.x] = a;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) loss[0] = red[0] * inv_count;
+}
+// dlogits (workspace, [B, C]) of the soft-target kinds; one wave per sample
+__global__ __launch_bounds__(256) void soft_dlogits_kernel(const float* __restrict__ logits, const float* __restrict__ tgt,
+                                                           const float* __restrict__ dloss, float* __restrict__ dlogits, int B, int C,
+                                                           int kind) {
+  const int b = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (b >= B) return;
+  const float up = dloss[0];
+  const float* z = logits + (long)b * C;
+  const float* t = tgt + (long)b * C;
+  float* g = dlogits + (long)b * C;
+  if (kind == VIT_LOSS_SOFT_CE) {
+    float mx, se, st = 0.f;
+    soft_row_stats(z, C, lane, mx, se);
+    for (int c = lane; c < C; c += 64) st += t[c];
+    st = wave_sum(st);
+    for (int c = lane; c < C; c += 64) g[c] = (__expf(z[c] - mx) / se * st - t[c]) / (float)B * up;
+  } else {
+    const float n = (float)B * (float)C;
+    for (int c = lane; c < C; c += 64) {
+      const float e = __expf(-fabsf(z[c]));  // sigmoid(z) = 1 / (1 + e^-z) = e^z / (1 + e^z), without overflow
+      const float sg = (z[c] >= 0.f ? 1.f : e) / (1.f + e);
+      g[c] = (sg - t[c]) / n * up;
+    }
+  }
+}
+// the CLS rows of d(last_hidden) from dlogits: dlast[b, 0, d] = sum_c dlogits[b, c] W[c, d], in class order; one lane per column
+__global__ __launch_bounds__(256) void head_bwd_dlast_kernel(const float* __restrict__ W, const float* __restrict__ dlogits,
+                                                             float* __restrict__ dlast, int T, int D, int C) {
+  const int b = blockIdx.y, d = blockIdx.x * 256 + threadIdx.x;
+  if (d >= D) return;
+  const float* g = dlogits + (long)b * C;
+  float a = 0.f;
+  for (int c = 0; c < C; ++c) a += g[c] * W[(long)c * D + d];
+  dlast[(long)b * T * D + d] = a;
+}
+
 // ------------------------------------------------------------------------------------------ grad norm
 __global__ __launch_bounds__(256) void sqnorm_stage1_kernel(const float* __restrict__ g, long n, float* __restrict__ part) {
   __shared__ float red[4];
@@ -670,15 +751,27 @@ int vit_cast_bf16_f32(vit_handle h, const void* src, float* dst, int64_t n, floa
 
 int vit_head_loss_fwd(vit_handle h, const float* last_hidden, const float* W, const float* b, const void* labels,
                       float* logits, float* loss_out, int B, int T, int D, int C, int loss_kind, vit_stream stream) {
-  (void)h;
   VIT_CHECK(last_hidden && W && b && logits, VIT_ERR_ARG, "vit_head_loss_fwd: null pointer");
   VIT_CHECK(B > 0 && T > 0 && D > 0 && C > 0, VIT_ERR_ARG, "vit_head_loss_fwd: B=%d T=%d D=%d C=%d", B, T, D, C);
-  VIT_CHECK(loss_kind >= VIT_LOSS_MSE && loss_kind <= VIT_LOSS_CE, VIT_ERR_ARG, "vit_head_loss_fwd: bad loss_kind");
+  VIT_CHECK(loss_kind >= VIT_LOSS_MSE && loss_kind <= VIT_LOSS_BCE, VIT_ERR_ARG, "vit_head_loss_fwd: bad loss_kind");
+  VIT_CHECK(!labels || loss_out, VIT_ERR_ARG, "vit_head_loss_fwd: labels without loss_out");
+  const bool soft = loss_kind == VIT_LOSS_SOFT_CE || loss_kind == VIT_LOSS_BCE;
+  float* row_loss = nullptr;
+  if (soft && labels) {  // the row losses: claimed before the first launch
+    row_loss = (float*)ctx_claim(h, (size_t)B * sizeof(float), "vit_head_loss_fwd");
+    if (!row_loss) return VIT_ERR_WORKSPACE;
+  }
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(head_logits_kernel, dim3(B), dim3(64), 0, st, last_hidden, W, b, logits, T, D, C);
   VIT_LAUNCH_CHECK();
-  if (labels) {
-    VIT_CHECK(loss_out, VIT_ERR_ARG, "vit_head_loss_fwd: labels without loss_out");
+  if (labels && soft) {
+    hipLaunchKernelGGL(soft_loss_rows_kernel, dim3(cdiv(B, 4)), dim3(256), 0, st, logits, (const float*)labels, row_loss, B, C,
+                       loss_kind);
+    VIT_LAUNCH_CHECK();
+    const float inv = (float)(1.0 / (loss_kind == VIT_LOSS_BCE ? (double)B * C : (double)B));
+    hipLaunchKernelGGL(soft_loss_mean_kernel, dim3(1), dim3(256), 0, st, row_loss, B, loss_out, inv);
+    VIT_LAUNCH_CHECK();
+  } else if (labels) {
     hipLaunchKernelGGL(loss_kernel, dim3(1), dim3(256), 0, st, logits, labels, loss_out, B, C, loss_kind);
     VIT_LAUNCH_CHECK();
   }
@@ -691,6 +784,7 @@ int vit_head_loss_bwd(vit_handle h, const float* last_hidden, const float* W, co
   VIT_CHECK(last_hidden && W && logits && labels && dloss && dlast_hidden && dW && db, VIT_ERR_ARG,
             "vit_head_loss_bwd: null pointer");
   VIT_CHECK(B > 0 && T > 0 && D > 0 && C > 0, VIT_ERR_ARG, "vit_head_loss_bwd: B=%d T=%d D=%d C=%d", B, T, D, C);
+  VIT_CHECK(loss_kind >= VIT_LOSS_MSE && loss_kind <= VIT_LOSS_BCE, VIT_ERR_ARG, "vit_head_loss_bwd: bad loss_kind");
   float* dlog = (float*)ctx_claim(h, (size_t)B * C * 4, "vit_head_loss_bwd");
   if (!dlog) return VIT_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
@@ -698,8 +792,15 @@ int vit_head_loss_bwd(vit_handle h, const float* last_hidden, const float* W, co
   // follow it (replays kept stale rows), and a fill kernel is ordered like every other node
   hipLaunchKernelGGL(zero_f32_kernel, dim3(grid_for((long)B * T * D / 4 + 1)), dim3(256), 0, st, dlast_hidden, (long)B * T * D);
   VIT_LAUNCH_CHECK();
-  hipLaunchKernelGGL(head_bwd_rows_kernel, dim3(B), dim3(64), 0, st, W, logits, labels, dloss, dlog, dlast_hidden, B, T,
-                     D, C, loss_kind);
+  if (loss_kind == VIT_LOSS_SOFT_CE || loss_kind == VIT_LOSS_BCE) {
+    hipLaunchKernelGGL(soft_dlogits_kernel, dim3(cdiv(B, 4)), dim3(256), 0, st, logits, (const float*)labels, dloss, dlog, B, C,
+                       loss_kind);
+    VIT_LAUNCH_CHECK();
+    hipLaunchKernelGGL(head_bwd_dlast_kernel, dim3(cdiv(D, 256), B), dim3(256), 0, st, W, dlog, dlast_hidden, T, D, C);
+  } else {
+    hipLaunchKernelGGL(head_bwd_rows_kernel, dim3(B), dim3(64), 0, st, W, logits, labels, dloss, dlog, dlast_hidden, B, T,
+                       D, C, loss_kind);
+  }
   VIT_LAUNCH_CHECK();
   hipLaunchKernelGGL(head_bwd_params_kernel, dim3(cdiv((long)C * D, 256)), dim3(256), 0, st, last_hidden, dlog, dW, db,
                      B, T, D, C, accumulate || ctx_grad_accumulate(h));

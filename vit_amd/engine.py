@@ -33,7 +33,7 @@ import torch
 
 from . import _cabi
 from . import functional as vf
-from ._cabi import ACT_GELU, LOSS_CE, LOSS_L1, LOSS_MSE, VitError
+from ._cabi import ACT_GELU, LOSS_BCE, LOSS_CE, LOSS_L1, LOSS_MSE, LOSS_SOFT_CE, VitError
 from .config import ViTConfig
 
 ALIGN = 8  # elements; keeps every view 32-byte (f32) / 16-byte (bf16) aligned
@@ -224,6 +224,9 @@ class ViTEngine:
             raise ValueError(f"layer_scale_init must be a finite number > 0, or None for no LayerScale (got {ls!r})")
         self.cfg = cfg
         self.loss_name, self.loss_kind = resolved_loss(cfg.task_type, loss_name)
+        # a classification call whose labels are floating soft targets [B, num_labels] (Mixup / CutMix / label smoothing,
+        # vit_amd/mix.py) runs this kind instead, forward and backward; int64 labels run loss_kind as ever (set_soft_loss)
+        self.soft_loss_kind = LOSS_SOFT_CE
         self.layout = ParamLayout(cfg)
         self.flat = torch.zeros(self.layout.n_total, dtype=torch.float32)
         self.shadow: Optional[torch.Tensor] = None
@@ -267,6 +270,17 @@ class ViTEngine:
         # the base's), so "were the f32 weights modified since the bf16 shadow was made?" is answered by a signature
         # over the parameters' versions, supplied by the owning module.
         self.version_fn: Callable[[], int] = lambda: self.flat._version
+
+    def set_soft_loss(self, name: str) -> int:
+        """`augment.soft_loss`: 'ce' (torch's cross-entropy with probability targets) | 'bce' (binary cross-entropy with logits,
+        DeiT-III's head loss) for classification calls with soft targets."""
+        if self.loss_kind != LOSS_CE:
+            raise ValueError("soft-target losses belong to classification (task_type 'cls')")
+        kinds = {"ce": LOSS_SOFT_CE, "bce": LOSS_BCE}
+        if name not in kinds:
+            raise ValueError(f"soft_loss must be one of {sorted(kinds)}, got {name!r}")
+        self.soft_loss_kind = kinds[name]
+        return self.soft_loss_kind
 
     # ------------------------------------------------------------------ precision
     def set_precision(self, precision) -> str:
@@ -654,15 +668,18 @@ class ViTEngine:
                 then = (r.xL, "vit.layernorm", r.last2, r.meanF, r.rstdF)
             self._tail_fwd(r, i, j, a["x"][i].view(M, D), then, ph, seed, need_grad, pd)
         hn = self.layout.head
+        kind = self.loss_kind
         if labels is not None:
             labels = labels.to(self.flat.device)
-            labels = labels.contiguous().to(torch.int64 if self.loss_kind == LOSS_CE else torch.float32)
-            n_expected = B if self.loss_kind == LOSS_CE else B * c.num_labels
+            if kind == LOSS_CE and labels.is_floating_point() and tuple(labels.shape) == (B, c.num_labels):
+                kind = self.soft_loss_kind  # soft targets: this call's loss, forward and backward
+            labels = labels.contiguous().to(torch.int64 if kind == LOSS_CE else torch.float32)
+            n_expected = B if kind == LOSS_CE else B * c.num_labels
             if labels.numel() != n_expected:
                 raise ValueError(f"labels has {labels.numel()} elements, expected {n_expected}")
-        logits, loss = vf.head_loss_fwd(r.last, self.p(hn + ".weight"), self.p(hn + ".bias"), labels, self.loss_kind)
+        logits, loss = vf.head_loss_fwd(r.last, self.p(hn + ".weight"), self.p(hn + ".bias"), labels, kind)
         self._last = dict(B=B, seed=seed, ph=ph, pa=pa, pd=pd, labels=labels, logits=logits, gen=self._gen, grad=need_grad,
-                          tail=tail)
+                          tail=tail, kind=kind)
         hs = [t.clone() for t in a["x"]] if output_hidden_states else None
         return loss, logits, hs, atts
 
@@ -899,7 +916,7 @@ class ViTEngine:
         dloss = dloss.reshape(1).to(torch.float32).contiguous()
         full, cls = self._rows
         r = cls if st["tail"] else full  # the rows the backward walks until the last layer's LN-before
-        vf.head_loss_bwd(r.last, self.p(hn + ".weight"), st["logits"], st["labels"], dloss, self.loss_kind, dlast=r.dlast,
+        vf.head_loss_bwd(r.last, self.p(hn + ".weight"), st["logits"], st["labels"], dloss, st["kind"], dlast=r.dlast,
                          dW=self.dW(hn), db=self.db(hn))
         self._setup_side()
         dx, spare = r.dx  # the residual gradient and the buffer the next LayerNorm backward writes it to

@@ -8,7 +8,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import _cabi
-from ._cabi import ACT_DGELU, ACT_GELU, ACT_GELU_GRAD, ACT_MUL_AUX, ACT_NONE, LOSS_CE, LOSS_L1, LOSS_MSE, VIT_BF16, VIT_F32, GemmDesc
+from ._cabi import ACT_DGELU, ACT_GELU, ACT_GELU_GRAD, ACT_MUL_AUX, ACT_NONE, LOSS_BCE, LOSS_CE, LOSS_L1, LOSS_MSE, LOSS_SOFT_CE, VIT_BF16, VIT_F32, GemmDesc
 
 _DT = {torch.float32: VIT_F32, torch.bfloat16: VIT_BF16}
 
@@ -714,6 +714,60 @@ def ema_swap(p, ema, p_bf16=None, *, n: Optional[int] = None):
     if p_bf16 is not None:
         _chk(p_bf16, torch.bfloat16, "ema_swap p_bf16")
     _h(p).call("vit_ema_swap", p.data_ptr(), ema.data_ptr(), _ptr(p_bf16), n, _stream(p))
+
+
+# ------------------------------------------------------------------------------------------------ Mixup / CutMix
+MIX_ROW_BYTES = 32  # vit_mix_row (include/vit_amd_mix.h)
+
+
+def mix_plan_write(plan, rows):
+    """Rows [0, len(rows)) of the device plan (uint8, 32 bytes a row, 16-byte aligned) <- `rows`: a sequence of
+    (w, u, lo, hi, wy, uy).  The rows travel in kernel arguments on the current stream (vit_mix_plan_write)."""
+    n = len(rows)
+    if plan.dtype != torch.uint8 or not plan.is_contiguous() or plan.numel() < n * MIX_ROW_BYTES:
+        raise _cabi.VitError(f"mix_plan_write: the plan must be a contiguous uint8 tensor of at least {n * MIX_ROW_BYTES} bytes")
+    arr = (_cabi.MixRow * n)()
+    for r, (w, u, lo, hi, wy, uy) in zip(arr, rows):
+        r.w, r.u, r.lo, r.hi, r.wy, r.uy = float(w), float(u), int(lo), int(hi), float(wy), float(uy)
+    _h(plan).call("vit_mix_plan_write", plan.data_ptr(), n, arr, _stream(plan))
+
+
+def mix_signal(x, plan, n_rows: int, out=None):
+    """Mixup / CutMix of x [B, L] (f32) by the device plan (vit_mix_signal); `out is x`: in place, None: a fresh tensor."""
+    _chk(x, torch.float32, "mix_signal x")
+    if x.dim() != 2:
+        raise _cabi.VitError(f"mix_signal: x must be [B, L], got {tuple(x.shape)}")
+    out = out if out is not None else torch.empty_like(x)
+    _chk(out, torch.float32, "mix_signal out")
+    if out.shape != x.shape:
+        raise _cabi.VitError(f"mix_signal: out {tuple(out.shape)} is not shaped like x {tuple(x.shape)}")
+    B, L = x.shape
+    _h(x).call("vit_mix_signal", x.data_ptr(), out.data_ptr(), plan.data_ptr(), int(n_rows), B, L, _stream(x))
+    return out
+
+
+def mix_targets(labels, plan, n_rows: int, num_classes: Optional[int] = None, on: float = 1.0, off: float = 0.0, out=None):
+    """The mixed labels of a batch (vit_mix_targets).  `num_classes` None: regression labels f32 [B] / [B, k], mixed linearly
+    into a tensor of their shape; else class labels int64 [B] -> soft targets f32 [B, num_classes] over the smoothed one-hot
+    rows (`on` at the label, `off` elsewhere)."""
+    if not labels.is_contiguous():
+        raise _cabi.VitError("mix_targets: labels must be contiguous")
+    B = labels.shape[0]
+    if num_classes is None:
+        _chk(labels, torch.float32, "mix_targets labels")
+        kind, Cn, shape = _cabi.MIX_LABELS_F32, labels.numel() // max(B, 1), labels.shape
+    else:
+        _chk(labels, torch.int64, "mix_targets labels")
+        if labels.dim() != 1:
+            raise _cabi.VitError(f"mix_targets: class labels must be [B], got {tuple(labels.shape)}")
+        kind, Cn, shape = _cabi.MIX_LABELS_I64, int(num_classes), (B, int(num_classes))
+    out = out if out is not None else torch.empty(shape, dtype=torch.float32, device=labels.device)
+    _chk(out, torch.float32, "mix_targets out")
+    if out.numel() != B * Cn:
+        raise _cabi.VitError(f"mix_targets: out has {out.numel()} elements, expected {B * Cn}")
+    _h(labels).call("vit_mix_targets", labels.data_ptr(), kind, out.data_ptr(), plan.data_ptr(), int(n_rows), B, Cn, float(on),
+                    float(off), _stream(labels))
+    return out
 
 
 # ------------------------------------------------------------------------------------------------ LayerScale

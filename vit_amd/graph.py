@@ -38,7 +38,8 @@ class GraphedTrainStep:
     """`step(batch) -> loss` replaying a captured forward + backward + clip + optimizer update over `module.model` (a MyViT).
 
     `batch` = (flux, error, labels); tensors whose storage differs from the captured ones are copied into the static input
-    buffers first (a device-to-device copy of the batch).
+    buffers first (a device-to-device copy of the batch).  With Mixup / CutMix configured (`module.mixer`) that copy is the
+    mix itself: `mixer.apply(flux, labels, out_x=self.x, out_y=self.labels)` ahead of the replay, the same bytes moved.
 
     Stochastic depth (`model.drop_path_rate`) rides along unchanged: the frozen launches carry each layer's rate, the bound
     record's keys vary the per-sample draw from replay to replay, as they vary the dropout masks."""
@@ -61,7 +62,13 @@ class GraphedTrainStep:
         self.state = torch.zeros(8, dtype=torch.int32, device=dev)
         self.state[5] = int(optimizer._step)
         self.x = flux.detach().to(dev, torch.float32).contiguous().clone()
-        self.labels = labels.detach().to(dev).contiguous().clone()
+        # Mixup / CutMix (module.mixer, vit_amd/mix.py): the mix launches ARE the copy into the static buffers, outside the graph
+        # (step()); the label buffer has the shape and dtype of the mixed targets.  The warm-up and the capture draw nothing.
+        self.mixer = getattr(module, "mixer", None)
+        if self.mixer is not None:
+            self.labels = self.mixer.targets_like(labels.detach().to(dev))
+        else:
+            self.labels = labels.detach().to(dev).contiguous().clone()
         # the copy into the static buffers is skipped only for the very tensor OBJECTS captured, unmodified since (holding the
         # references keeps their storage from being recycled for another batch at the same address)
         self._src = (flux, labels, flux._version, labels._version)
@@ -150,12 +157,18 @@ class GraphedTrainStep:
         self.opt._graph_validate(self._captured)  # ValueError before anything is touched: the caller falls back to eager steps
         if self.averager is not None and step is None:
             raise ValueError("GraphedTrainStep.step: the averaging schedule needs the optimizer step's number (step=)")
-        if flux is not self._src[0] or flux._version != self._src[2]:
-            self.x.copy_(flux, non_blocking=True)
-            self._src = (None, self._src[1], -1, self._src[3])
-        if labels is not self._src[1] or labels._version != self._src[3]:
-            self.labels.copy_(labels, non_blocking=True)
-            self._src = (self._src[0], None, self._src[2], -1)
+        if self.mixer is not None:
+            # every step draws its own plan, so the captured tensors are never the step's input as they are
+            dev = self.x.device
+            self.mixer.apply(flux.detach().to(dev), labels.detach().to(dev), out_x=self.x, out_y=self.labels)
+            self._src = (None, None, -1, -1)
+        else:
+            if flux is not self._src[0] or flux._version != self._src[2]:
+                self.x.copy_(flux, non_blocking=True)
+                self._src = (None, self._src[1], -1, self._src[3])
+            if labels is not self._src[1] or labels._version != self._src[3]:
+                self.labels.copy_(labels, non_blocking=True)
+                self._src = (self._src[0], None, self._src[2], -1)
         self.opt._sync_group_table()  # on the current stream, ahead of the replay: a launch only when a scheduler changed a number
         ema_w = 0.0
         if self.averager is not None:

@@ -12,7 +12,8 @@ What is kept from the reference is the SURFACE: method names (`forward`, `traini
   * epoch statistics (median bias, 90th percentile of |residual|, slope of the pred-vs-label line) in torch on the
     collected predictions;
   * metrics from vit_amd.metrics (torchmetrics is not in this image), whose DDP reduction sums states, not values;
-  * training noise through the `vit_add_noise` kernel.
+  * training noise through the `vit_add_noise` kernel, then Mixup / CutMix of the batch and its labels (`augment:`, off by
+    default) through `vit_mix_signal` / `vit_mix_targets`.
 With `lightning` installed the classes subclass `lightning.LightningModule` and run under `L.Trainer`; otherwise a small
 stand-in base provides `log` / `trainer` / `logger` for vit_amd.trainer.
 """
@@ -105,6 +106,14 @@ class ViTLModule(BaseLightningModule):
         self.save_hyperparameters(ignore=["model"])
         self.task_type = _normalize_task(config)
         self.noise_level = (config.get("noise") or {}).get("noise_level", 0.0)
+        # `augment:` -- Mixup / CutMix / label smoothing of the training batches (vit_amd/mix.py); None unless the block switches
+        # something on.  A classification run with a mixer trains on soft targets [B, num_labels] on every step.
+        from .mix import mixup_from_config
+
+        cls = self.task_type == "cls"
+        self.mixer = mixup_from_config(config, num_classes=int(self.model.config.num_labels) if cls else None)
+        if self.mixer is not None and cls:
+            self.model.engine.set_soft_loss(self.mixer.soft_loss)
         if self.task_type == "cls":
             self.accuracy = Accuracy()
             self.monitor_metric = "acc"
@@ -141,7 +150,12 @@ class ViTLModule(BaseLightningModule):
 
     def training_step(self, batch, batch_idx):
         flux, error, labels = batch
-        loss = self(self._augment(flux, error), labels, loss_only=True)
+        x = self._augment(flux, error)
+        if self.mixer is not None:
+            # noise first (each sample with its own error), then mixing -- in place on the fresh tensor the noise pass returned,
+            # into a tensor of the mixer's otherwise (the loader may have handed out a view of its dataset)
+            x, labels = self.mixer.apply(x, labels, out_x=x if x is not flux else None)
+        loss = self(x, labels, loss_only=True)
         self.log(f"{self.loss_name}_loss", loss, on_step=True, on_epoch=True, prog_bar=True)
         return loss
 

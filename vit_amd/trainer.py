@@ -8,6 +8,7 @@
                       (`train.accumulate_grad_batches: K` = Lightning's: zero_grad at the start of a group of K batches,
                       each backward on loss / K adding into the flat gradient buffer in place, exchange + clip + step +
                       per-step scheduler on every K-th batch and on the epoch's last one)
+                      (`augment:`: training_step mixes the batch and its labels first, Mixup / CutMix, vit_amd/mix.py)
                       (`train.ema_decay`: after the optimizer step the weights' exponential moving average is updated on the
                       GPU, vit_amd/ema.py; validation and checkpoints then see the averaged weights)
            validate every epoch (basemodule.py:249)
@@ -327,6 +328,8 @@ class Trainer:
             snap["extra_params"] = [p.detach().clone() for p in module.parameters()]
         if self.averager is not None:
             snap["ema"] = self.averager.clone_state()
+        if getattr(module, "mixer", None) is not None:
+            snap["mix"] = module.mixer.state_dict()  # the draws' counter: the mixer's whole state
         return snap
 
     def _restore(self, module, snap):
@@ -351,6 +354,8 @@ class Trainer:
             g.update(saved)
         if self.averager is not None:
             self.averager.restore_state(snap["ema"])
+        if "mix" in snap:
+            module.mixer.load_state_dict(snap["mix"])
         opt.zero_grad(set_to_none=True)
         self._micro = 0
 
@@ -561,6 +566,8 @@ class Trainer:
         if ema is not None:  # only then: without averaging the file is laid out as it always was
             ckpt["vit_amd"]["ema"] = {"decay": ema.decay, "every": ema.every, "start_step": ema.start_step,
                                       "n_averaged": int(ema.n_averaged), "train_state": train_state}
+        if getattr(module, "mixer", None) is not None:  # likewise only with mixing on: the counter of its draws
+            ckpt["vit_amd"]["mix"] = module.mixer.state_dict()
         return ckpt
 
     def _resume(self, module, ckpt_path: str) -> int:
@@ -587,6 +594,8 @@ class Trainer:
         if "dropout_step" in own:
             module.model.engine.base_seed = int(own["dropout_base_seed"])
             module.model.engine.step_counter = int(own["dropout_step"])
+        if getattr(module, "mixer", None) is not None and own.get("mix"):
+            module.mixer.load_state_dict(own["mix"])  # call n draws from (seed, rank, n): the sequence continues exactly
         self.global_step = int(ckpt.get("global_step", 0))
         return int(ckpt["epoch"]) + 1 if "epoch" in ckpt else 0  # saved at the END of that epoch
 
