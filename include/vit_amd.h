@@ -383,5 +383,8 @@ int vit_adamw_step(vit_handle h, float* p, const float* g, float* m, float* v, v
 /* Mixup / CutMix of the batch and its labels (`augment:`): vit_mix_plan_write, vit_mix_signal, vit_mix_targets.  Declared in
  * their own header, part of this ABI. */
 #include "vit_amd_mix.h"
+/* Patch dropout (`model.patch_drop_rate`): the per-sample token selection and the gather forms of the embedding-side kernels
+ * behind which the encoder runs at 1 + K tokens.  Declared in their own header, part of this ABI. */
+#include "vit_amd_patchdrop.h"
 
 #endif /* VIT_AMD_H_ */

@@ -147,6 +147,17 @@ _PROTOS = {
     "vit_mix_plan_write": [_P, _P, _I, C.POINTER(MixRow), _P],
     "vit_mix_signal": [_P, _P, _P, _P, _I, _I, _I, _P],
     "vit_mix_targets": [_P, _P, _I, _P, _P, _I, _I, _I, _F, _F, _P],
+    # patch dropout (include/vit_amd_patchdrop.h): (h, idx, slot, B, N, K, seed, site, stream) /
+    # (h, x, idx, patches, out_dtype, B, L, P, S, N, K, stream) / (h, tokens, cls, pos, idx, B, Tc, T_full, D, p, seed, site, stream) /
+    # (h, dtokens, slot, dpatch, dpatch_dtype, dcls, dpos, B, Tc, T_full, D, p, seed, site, accumulate, stream) /
+    # (h, table, idx, out, B, Tc, T_full, W, stream) / (h, dpatches, slot, dx, B, L, P, S, N, K, stream)
+    "vit_patch_select": [_P, _P, _P, _I, _I, _I, _U64, _U64, _P],
+    "vit_patch_slot": [_P, _P, _P, _I, _I, _I, _P],
+    "vit_unfold_gather_cast": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
+    "vit_embed_finish_gather": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _U64, _U64, _P],
+    "vit_embed_finish_gather_bwd": [_P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _F, _U64, _U64, _I, _P],
+    "vit_rows_gather": [_P, _P, _P, _P, _I, _I, _I, _I, _P],
+    "vit_fold_add_gather": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
 }
 _RESTYPES = {"vit_last_error": C.c_char_p, "vit_last_gemm_kernel": C.c_char_p, "vit_workspace_needed": C.c_size_t}
 
@@ -155,7 +166,7 @@ _lock = threading.Lock()
 
 
 def declared_symbols(header_path: str = HEADER_PATH):
-    """Every function the C header declares, the headers it includes from its own directory (vit_amd_cov.h, vit_amd_optim.h, vit_amd_ema.h, vit_amd_droppath.h, vit_amd_layerscale.h, vit_amd_mix.h) included (used by
+    """Every function the C header declares, the headers it includes from its own directory (vit_amd_cov.h, vit_amd_optim.h, vit_amd_ema.h, vit_amd_droppath.h, vit_amd_layerscale.h, vit_amd_mix.h, vit_amd_patchdrop.h) included (used by
     the CPU test that checks the library exports them all)."""
     seen, names, todo = set(), set(), [os.path.abspath(header_path)]
     while todo:

@@ -41,7 +41,16 @@ class ViTConfig:
     # LayerScale: a learnable per-channel factor on each of a layer's two residual branches, initialised to this value (> 0;
     # this build's key).  None = off: the reference's model, parameter for parameter
     layer_scale_init: Optional[float] = None
+    # patch dropout (timm's name and rule): a training forward keeps a random num_kept_patches of each sample's patch tokens
+    # (plus CLS) and the encoder runs at that shorter sequence; evaluation sees every token (this build's key; 0 = the
+    # reference's arithmetic)
+    patch_drop_rate: float = 0.0
     use_return_dict: bool = True
+
+    def __post_init__(self):
+        rate = self.patch_drop_rate
+        if isinstance(rate, bool) or not isinstance(rate, (int, float)) or not 0.0 <= float(rate) < 1.0:
+            raise ValueError(f"patch_drop_rate must lie in [0, 1) (got {rate!r})")
 
     @property
     def intermediate_size(self) -> int:  # builder.py:243
@@ -66,8 +75,21 @@ class ViTConfig:
         return self.num_patches + 1
 
     @property
+    def num_kept_patches(self) -> int:
+        """K of patch dropout: max(1, int(N * (1 - patch_drop_rate))) in Python doubles, as timm's PatchDropout computes it."""
+        return kept_patches(self.num_patches, self.patch_drop_rate)
+
+    @property
     def head_dim(self) -> int:
         return self.hidden_size // self.num_attention_heads
+
+
+def kept_patches(num_patches: int, rate: float) -> int:
+    """How many of `num_patches` patch tokens a training forward keeps at patch_drop_rate `rate` (ValueError outside [0, 1))."""
+    rate = float(rate)
+    if not 0.0 <= rate < 1.0:
+        raise ValueError(f"patch_drop_rate must lie in [0, 1) (got {rate})")
+    return max(1, int(num_patches * (1.0 - rate)))
 
 
 def _targets_in(param) -> int:
@@ -98,7 +120,7 @@ def get_vit_config(config) -> ViTConfig:
     else:
         num_labels = int(model.get("num_labels", 1) or 1)
     optional = {k: model[k] for k in ("stride_ratio", "stride_size", "pos_encoding_type", "max_position_embeddings", "rope_base",
-                                      "drop_path_rate", "layer_scale_init") if k in model}
+                                      "drop_path_rate", "layer_scale_init", "patch_drop_rate") if k in model}
     return ViTConfig(
         task_type=model["task_type"], image_size=model["image_size"], patch_size=model["patch_size"],
         hidden_size=model["hidden_size"], num_hidden_layers=model["num_hidden_layers"],

@@ -16,6 +16,10 @@ Data layout in HBM (one MI355X, 288 GB: nothing is recomputed or re-materialised
            scratch): what the last layer computes behind its attention when only the head consumes it (see `cls_tail`).
   LayerScale (cfg.layer_scale_init, off by default): folded [L * 5 D^2] operands of the out-projection / FC2 GEMMs (operand dtype)
            + f32 [L * 2D] biases, and per layer an f32 [5 D^2 + 2D] slab of their raw gradients (`_ensure_ls`).
+  Patch dropout (cfg.patch_drop_rate, off by default): a training forward keeps K of each sample's N patch tokens, and T above is
+           that forward's 1 + K -- the arena is keyed and sized by it, and also holds keep int32 [B, K] (the kept patches,
+           ascending), slot int32 [B, N] (its inverse, -1 = dropped) and, with RoPE, cos / sin tables f32 [M, head_dim / 2]
+           gathered per token row.  Evaluation arenas keep cfg.seq_len.
 Dropout masks are regenerated from (seed, site) in backward; no mask is stored.
 
 A layer's tail -- out-projection, LN-after, FC1 + GELU, FC2 behind its attention -- is stated once per direction
@@ -34,7 +38,7 @@ import torch
 from . import _cabi
 from . import functional as vf
 from ._cabi import ACT_GELU, LOSS_BCE, LOSS_CE, LOSS_L1, LOSS_MSE, LOSS_SOFT_CE, VitError
-from .config import ViTConfig
+from .config import ViTConfig, kept_patches
 
 ALIGN = 8  # elements; keeps every view 32-byte (f32) / 16-byte (bf16) aligned
 
@@ -219,6 +223,7 @@ class ViTEngine:
                              f"(got head_dim {cfg.head_dim}, hidden_size {cfg.hidden_size}, patch_size {cfg.patch_size})")
         if not 0.0 <= float(cfg.drop_path_rate) < 1.0:
             raise ValueError(f"drop_path_rate must lie in [0, 1) (got {cfg.drop_path_rate})")
+        kept_patches(cfg.num_patches, cfg.patch_drop_rate)  # ValueError outside [0, 1)
         ls = cfg.layer_scale_init
         if ls is not None and (isinstance(ls, bool) or not isinstance(ls, (int, float)) or not math.isfinite(ls) or not ls > 0):
             raise ValueError(f"layer_scale_init must be a finite number > 0, or None for no LayerScale (got {ls!r})")
@@ -245,6 +250,10 @@ class ViTEngine:
         self._Mp = 0  # the current arena's GEMM row count
         self._rows: Optional[Tuple[Rows, Rows]] = None  # the current arena's (token rows, CLS rows)
         self._rope, self._rope_key = None, None
+        # patch dropout (cfg.patch_drop_rate): an optional int32 [B, K] device tensor of strictly ascending patch indices per
+        # sample that replaces the drawn selection of the next training forwards (reproducing a run; tests).  None: draw.
+        self.patch_keep: Optional[torch.Tensor] = None
+        self._T = cfg.seq_len  # the sequence length of the forward in hand: 1 + K when it drops patches, cfg.seq_len otherwise
         self.precision = "f32"       # 'f32' (reference default precision='32') | 'bf16' (precision='bf16-mixed')
         self.base_seed = int(torch.initial_seed()) & 0x7FFFFFFFFFFFFFFF
         self.step_counter = 0
@@ -481,12 +490,16 @@ class ViTEngine:
         return buf[off:off + 3 * self.cfg.hidden_size]
 
     # ------------------------------------------------------------------ arena
-    def _ensure_arena(self, B: int, train: bool):
+    def _ensure_arena(self, B: int, train: bool, T: Optional[int] = None):
         """Select (allocating on first use) the activation arena for this batch size.  Training and evaluation forwards keep
         SEPARATE arenas (one slot each): a validation pass between two optimisation steps must not release the training
         arena -- a captured hipGraph (vit_amd/graph.py) replays raw pointers into it, and re-allocating 17 GB per epoch would
-        be waste in any case.  A slot is replaced when its batch size or the precision changes."""
-        key = (B, train, self.precision)
+        be waste in any case.  A slot is replaced when its batch size, its sequence length or the precision changes.
+        `T`: the sequence length the forward runs at -- 1 + K under patch dropout (every buffer is then sized by it, and the arena
+        also holds the selection `keep` [B, K], its inverse `slot` [B, N] and, with RoPE, the gathered tables), cfg.seq_len
+        otherwise (None)."""
+        T = self.cfg.seq_len if T is None else T
+        key = (B, train, self.precision, T)
         if self._arena_key == key:
             return
         slot = self._arenas.get(train)
@@ -502,8 +515,7 @@ class ViTEngine:
         gc.collect()
         c = self.cfg
         dev = self.flat.device
-        T, D, Fd, H, L, N, P = c.seq_len, c.hidden_size, c.intermediate_size, c.num_attention_heads, \
-            c.num_hidden_layers, c.num_patches, c.patch_size
+        D, Fd, H, L, N, P = c.hidden_size, c.intermediate_size, c.num_attention_heads, c.num_hidden_layers, T - 1, c.patch_size
         M = B * T
         # GEMM row count: token rows padded to the 256-row tiles of the ping-pong GEMM core when the widths allow it.
         # Every buffer a GEMM reads or writes is allocated ZEROED with Mp rows and used through its first M rows by
@@ -541,6 +553,11 @@ class ViTEngine:
             c_mean2=C(0, f32), c_rstd2=C(0, f32), c_xL=E((B, D), f32), c_last=E((B, 1, D), f32),
             c_meanF=E((B,), f32), c_rstdF=E((B,), f32),
         )
+        if T != c.seq_len:  # patch dropout: N above is the kept count K
+            i32 = torch.int32
+            act.update(keep=E((B, N), i32), slot=E((B, c.num_patches), i32))
+            if c.pos_encoding_type == "rope":
+                act.update(rope_cos=E((M, c.head_dim // 2), f32), rope_sin=E((M, c.head_dim // 2), f32))
         tmp = {}
         if train:
             tmp = dict(
@@ -581,7 +598,19 @@ class ViTEngine:
 
     # ------------------------------------------------------------------ forward
     def _site(self, layer: int, which: int) -> int:
+        """The (seed, site) slots of a step: 0 the embedding dropout; layer i's four are 1 + 4 i + {0: attention probabilities,
+        1: attention-output projection, 2: FC2, 3: the layer's two stochastic-depth gates}.  _site(L, 0) = 1 + 4 L, the first
+        slot behind the last layer's, belongs to the patch-dropout selection (vit_patch_select; tests/_patchdrop_ref.py)."""
         return 1 + 4 * layer + which
+
+    def kept_count(self, training: bool) -> Optional[int]:
+        """Patch dropout: K, the patch tokens per sample a forward keeps -- or None when it keeps them all: not training, rate 0,
+        or a rate so small that K == N.  Read on every forward, like the dropout probabilities."""
+        c = self.cfg
+        K = kept_patches(c.num_patches, c.patch_drop_rate)
+        if not training or float(c.patch_drop_rate) <= 0.0 or K >= c.num_patches:
+            return None
+        return K
 
     def path_rates(self, training: bool = True) -> Optional[List[float]]:
         """Stochastic depth: the drop probability of layer i's two residual branches, the usual linear schedule
@@ -600,7 +629,7 @@ class ViTEngine:
         1 where the forward reads a compact stream of one row per sample (the CLS tail's second sum)."""
         if pd is None or i < 0 or pd[i] <= 0.0:
             return None
-        return (pd[i], self._site(i, 3), self.cfg.seq_len if rows_per_sample is None else rows_per_sample, branch)
+        return (pd[i], self._site(i, 3), self._T if rows_per_sample is None else rows_per_sample, branch)
 
     def forward(self, x: torch.Tensor, labels: Optional[torch.Tensor], training: bool, need_grad: bool,
                 output_hidden_states: bool = False, output_attentions: bool = False, capture_ctx: Optional[list] = None):
@@ -614,16 +643,23 @@ class ViTEngine:
             raise ValueError(f"pixel_values must be [batch, {c.image_size}], got {tuple(x.shape)}")
         if not x.is_cuda:
             raise VitError("pixel_values must live on the GPU")
-        if self.precision == "f32" and c.seq_len > 4096:
-            raise ValueError(f"precision '32': the fp32 attention kernels take at most 4096 tokens (this model has "
-                             f"{c.seq_len}); use train.precision 'bf16-mixed'")
+        K = self.kept_count(training)  # patch dropout: this forward runs at 1 + K tokens (None: at all of them)
+        T = c.seq_len if K is None else 1 + K
+        if self.precision == "f32" and T > 4096:
+            raise ValueError(f"precision '32': the fp32 attention kernels take at most 4096 tokens (this forward has "
+                             f"{T}); use train.precision 'bf16-mixed'")
         x = x.contiguous().to(torch.float32)
         B = x.shape[0]
+        keep_in = self.patch_keep if K is not None else None
+        if keep_in is not None and (not isinstance(keep_in, torch.Tensor) or keep_in.dtype != torch.int32 or not keep_in.is_cuda
+                                    or tuple(keep_in.shape) != (B, K)):
+            raise ValueError(f"patch_keep must be an int32 [{B}, {K}] device tensor of ascending patch indices per sample, got "
+                             f"{getattr(keep_in, 'dtype', type(keep_in))} {tuple(getattr(keep_in, 'shape', ()))}")
         self._gen += 1
-        T, D, H, L, N, P, S = c.seq_len, c.hidden_size, c.num_attention_heads, c.num_hidden_layers, c.num_patches, \
-            c.patch_size, c.stride
+        self._T = T
+        D, H, L, N, P, S = c.hidden_size, c.num_attention_heads, c.num_hidden_layers, c.num_patches, c.patch_size, c.stride
         dh, M = c.head_dim, B * T
-        self._ensure_arena(B, need_grad)
+        self._ensure_arena(B, need_grad, T)
         a = self.act
         ph = c.hidden_dropout_prob if training else 0.0
         pa = c.attention_probs_dropout_prob if training else 0.0
@@ -634,14 +670,33 @@ class ViTEngine:
         scale = dh ** -0.5
         full, cls = self._rows
         # --- embeddings: unfold -> projection (+bias) into token rows 1..N -> CLS / pos-emb / dropout
-        vf.unfold_cast(x, P, S, N, out=a["patches"])  # bf16 or f32 patches, per the arena dtype
         x0 = a["x"][0]
-        vf.gemm(a["patches"], self.W(PROJ).view(D, P), M=B * N, N=D, K=P, out=x0.view(M, D), bias=self.b(PROJ), row_map=(N, T, 1))
-        pos = self.p(EMBED + "position_embeddings").view(T, D) if c.pos_encoding_type == "learned" else None
-        vf.embed_finish(x0, self.p(EMBED + "cls_token").view(D), pos, dropout=(ph, seed, 0))
+        pos = self.p(EMBED + "position_embeddings").view(c.seq_len, D) if c.pos_encoding_type == "learned" else None
+        rope = self._rope_tables(c.seq_len) if c.pos_encoding_type == "rope" else None
+        if K is None:
+            vf.unfold_cast(x, P, S, N, out=a["patches"])  # bf16 or f32 patches, per the arena dtype
+            vf.gemm(a["patches"], self.W(PROJ).view(D, P), M=B * N, N=D, K=P, out=x0.view(M, D), bias=self.b(PROJ),
+                    row_map=(N, T, 1))
+            vf.embed_finish(x0, self.p(EMBED + "cls_token").view(D), pos, dropout=(ph, seed, 0))
+        else:
+            # patch dropout: select (or take the caller's selection), then the gather forms of the same three steps; everything
+            # behind them is the path below at T = 1 + K.  The selection's site is the first one behind the layers'.
+            keep, slot = a["keep"], a["slot"]
+            if keep_in is None:
+                vf.patch_select(B, N, K, seed, self._site(L, 0), keep, slot)
+            else:
+                keep.copy_(keep_in)
+                vf.patch_slot(keep, slot)
+            vf.unfold_gather_cast(x, keep, P, S, N, out=a["patches"])
+            vf.gemm(a["patches"], self.W(PROJ).view(D, P), M=B * K, N=D, K=P, out=x0.view(M, D), bias=self.b(PROJ),
+                    row_map=(K, T, 1))
+            vf.embed_finish_gather(x0, self.p(EMBED + "cls_token").view(D), keep, c.seq_len, pos, dropout=(ph, seed, 0))
+            if rope is not None:
+                # every token rotates by its ORIGINAL position: per-step tables [B * T, dh / 2], one row per token row, for a
+                # vit_rope_qk pass behind the projection (the rotating epilogue takes linear positions only)
+                rope = (vf.rows_gather(rope[0], keep, out=a["rope_cos"]), vf.rows_gather(rope[1], keep, out=a["rope_sin"]))
 
         atts = [] if output_attentions else None
-        rope = self._rope_tables(T) if c.pos_encoding_type == "rope" else None
         tail = bool(self.cls_tail) and L > 0 and not output_hidden_states
         r = full
         if L == 0:
@@ -653,7 +708,9 @@ class ViTEngine:
             # vit_with_rope.py:58-60: q, k rotated per head before the scores -- inside the projection's epilogue where the
             # kernel has one (f32 values, one rounding), by a vit_rope_qk pass behind it otherwise (the library decides)
             vf.gemm(a["h1"][j], self._qkv16(i), M=full.n, N=3 * D, K=D, out=a["qkv"][j], bias=self._qkv_bias(i, self.flat),
-                    rope=None if rope is None else (rope[0], rope[1], T, dh, 2 * D))
+                    rope=None if rope is None or K is not None else (rope[0], rope[1], T, dh, 2 * D))
+            if rope is not None and K is not None:
+                vf.rope_qk(a["qkv"][j], rope[0], rope[1], M, H, dh)
             vf.attention_fwd(a["qkv"][j], B, H, T, dh, scale, dropout=(pa, seed, self._site(i, 0)), ctx=a["ctx"][j],
                              lse=a["lse"][j], ctx_lo=a["ctx_lo"][j])
             if output_attentions:
@@ -679,7 +736,7 @@ class ViTEngine:
                 raise ValueError(f"labels has {labels.numel()} elements, expected {n_expected}")
         logits, loss = vf.head_loss_fwd(r.last, self.p(hn + ".weight"), self.p(hn + ".bias"), labels, kind)
         self._last = dict(B=B, seed=seed, ph=ph, pa=pa, pd=pd, labels=labels, logits=logits, gen=self._gen, grad=need_grad,
-                          tail=tail, kind=kind)
+                          tail=tail, kind=kind, T=T, keep=a["keep"] if K is not None else None)
         hs = [t.clone() for t in a["x"]] if output_hidden_states else None
         return loss, logits, hs, atts
 
@@ -707,7 +764,7 @@ class ViTEngine:
         vf.gemm(r.g[j], self.W(nm.fc2), M=n, N=D, K=Fd, out=r.y, bias=self.b(nm.fc2), dropout=(ph, seed, self._site(i, 2)),
                 drop_row_stride=drs)
         # x1 is compact over the CLS rows (one row per sample, read with stride 1): the sample of its row b is b
-        self._ln_res(r.x1[j], r.y, *then, path=self._path(pd, i, 1, c.seq_len // r.stride), seed=seed)
+        self._ln_res(r.x1[j], r.y, *then, path=self._path(pd, i, 1, self._T // r.stride), seed=seed)
 
     def saved_attentions(self):
         """Attention probabilities (before dropout) of every layer of the LAST need_grad forward, from its saved qkv."""
@@ -715,7 +772,7 @@ class ViTEngine:
         if st is None or not st["grad"] or st["gen"] != self._gen:
             raise VitError("saved_attentions(): the last forward did not keep per-layer activations")
         with vf.use_handle(self.handle()):
-            return [vf.attention_probs(self.act["qkv"][i], st["B"], c.num_attention_heads, c.seq_len, c.head_dim,
+            return [vf.attention_probs(self.act["qkv"][i], st["B"], c.num_attention_heads, st["T"], c.head_dim,
                                        c.head_dim ** -0.5) for i in range(c.num_hidden_layers)]
 
     def _ln(self, x, name, out, mean, rstd):
@@ -908,10 +965,14 @@ class ViTEngine:
         c = self.cfg
         a, t = self.act, self.tmp
         B, seed, ph, pa, pd = st["B"], st["seed"], st["ph"], st["pa"], st["pd"]  # pd: the forward's path rates
-        T, D, H, L, N, P = c.seq_len, c.hidden_size, c.num_attention_heads, c.num_hidden_layers, c.num_patches, c.patch_size
+        T, keep = st["T"], st["keep"]  # the forward's sequence length and, under patch dropout, its selection [B, T - 1]
+        self._T = T
+        D, H, L, N, P = c.hidden_size, c.num_attention_heads, c.num_hidden_layers, T - 1, c.patch_size  # N: patch rows per sample
         dh, M = c.head_dim, B * T
         scale = dh ** -0.5
-        rope = self._rope_tables(T) if c.pos_encoding_type == "rope" else None
+        rope, rope_T = None, T
+        if c.pos_encoding_type == "rope":  # under patch dropout the forward's gathered tables: one row per token row
+            rope, rope_T = (self._rope_tables(T), T) if keep is None else ((a["rope_cos"], a["rope_sin"]), M)
         hn = self.layout.head
         dloss = dloss.reshape(1).to(torch.float32).contiguous()
         full, cls = self._rows
@@ -933,7 +994,7 @@ class ViTEngine:
                              dropout=(pa, seed, self._site(i, 0)), dqkv=t["dqkv"], delta=t["delta"],
                              colsum_out=None if rope is not None else self._qkv_bias(i, self.grads), ctx_lo=a["ctx_lo"][i])
             if rope is not None:  # gradient wrt the un-rotated q, k: the inverse rotation
-                vf.rope_qk(t["dqkv"], rope[0], rope[1], T, H, dh, inverse=True)
+                vf.rope_qk(t["dqkv"], rope[0], rope[1], rope_T, H, dh, inverse=True)
                 vf.colsum(t["dqkv"], out=self._qkv_bias(i, self.grads), accumulate=self._accum)
             self._dw(full, t["dqkv"], a["h1"][i], self._qkv_w(i, self.grads))
             vf.gemm(t["dqkv"], self._qkv16(i), M=full.n, N=D, K=3 * D, b_trans=True, out=t["dh"])
@@ -950,9 +1011,13 @@ class ViTEngine:
             dx, spare = spare, dx
             self._unfold_layer_scale(i)
             self._notify(*self.layout.layer_ranges[i])
-        dpos = self.g(EMBED + "position_embeddings").view(T, D) if c.pos_encoding_type == "learned" else None
-        vf.embed_finish_bwd(dx.view(B, T, D), self.g(EMBED + "cls_token").view(D), dpos, dropout=(ph, seed, 0),
-                            dpatch=t["dpatch"])  # dtype follows the buffer
+        dpos = self.g(EMBED + "position_embeddings").view(c.seq_len, D) if c.pos_encoding_type == "learned" else None
+        if keep is None:
+            vf.embed_finish_bwd(dx.view(B, T, D), self.g(EMBED + "cls_token").view(D), dpos, dropout=(ph, seed, 0),
+                                dpatch=t["dpatch"])  # dtype follows the buffer
+        else:  # dpos is summed through the inverse map: rows of patches nobody kept come out zero
+            vf.embed_finish_gather_bwd(dx.view(B, T, D), a["slot"], self.g(EMBED + "cls_token").view(D), dpos,
+                                       dropout=(ph, seed, 0), dpatch=t["dpatch"])
         vf.colsum(t["dpatch"], out=self.db(PROJ), accumulate=self._accum)
         vf.gemm(t["dpatch"], a["patches"], M=D, N=P, K=B * N, a_trans=True, b_trans=True, out=self.dW(PROJ).view(D, P),
                 split_k=-1)
@@ -962,5 +1027,7 @@ class ViTEngine:
             # gradient wrt the signal itself (a trainable input preprocessor sits in front): dpatches = dpatch Wp, then the
             # overlap-add that undoes the tokenizer's unfold
             dpat = vf.gemm(t["dpatch"], self.W(PROJ).view(D, P), M=B * N, N=P, K=D, b_trans=True, out_dtype=torch.float32)
+            if keep is not None:
+                return vf.fold_add_gather(dpat, a["slot"], c.image_size, P, c.stride)
             return vf.fold_add(dpat, B, c.image_size, P, c.stride, N)
         return None

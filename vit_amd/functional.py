@@ -400,6 +400,107 @@ def embed_finish_bwd(dtokens, dcls, dpos=None, dropout: Dropout = NO_DROP, dpatc
     return dpatch
 
 
+# ------------------------------------------------------------------------------------------------ patch dropout
+def _chk_index(t: torch.Tensor, B: int, cols: int, name: str):
+    _chk(t, torch.int32, name)
+    if not t.is_cuda or tuple(t.shape) != (B, cols):
+        raise _cabi.VitError(f"{name}: expected an int32 [{B}, {cols}] device tensor, got {tuple(t.shape)} on {t.device}")
+
+
+def patch_select(B: int, N: int, K: int, seed: int, site: int, idx, slot):
+    """The per-sample K-subset of N patches drawn from (seed, site) (vit_patch_select): idx int32 [B, K] ascending, slot int32
+    [B, N] its inverse (-1: dropped).  A step record bound to the handle varies the draw per replay."""
+    _chk_index(idx, B, K, "patch_select idx")
+    _chk_index(slot, B, N, "patch_select slot")
+    _h(idx).call("vit_patch_select", idx.data_ptr(), slot.data_ptr(), B, N, K, int(seed) & 0xFFFFFFFFFFFFFFFF, int(site),
+                 _stream(idx))
+    return idx, slot
+
+
+def patch_slot(idx, slot):
+    """slot [B, N] <- the inverse map of a given idx [B, K] (vit_patch_slot)."""
+    B, N = slot.shape
+    _chk_index(slot, B, N, "patch_slot slot")
+    _chk_index(idx, B, idx.shape[1], "patch_slot idx")
+    _h(idx).call("vit_patch_slot", idx.data_ptr(), slot.data_ptr(), B, N, idx.shape[1], _stream(idx))
+    return slot
+
+
+def unfold_gather_cast(x, idx, P: int, S: int, N: int, out=None, out_dtype=torch.bfloat16):
+    """Rows b * N + idx[b, k] of unfold_cast's output, compact: [B * K, P]."""
+    _chk(x, torch.float32, "unfold_gather_cast x")
+    B, L = x.shape
+    K = idx.shape[1]
+    _chk_index(idx, B, K, "unfold_gather_cast idx")
+    out = out if out is not None else torch.empty((B * K, P), dtype=out_dtype, device=x.device)
+    if out.numel() != B * K * P or not out.is_contiguous():
+        raise _cabi.VitError("unfold_gather_cast: out must be a contiguous [B*K, P] tensor")
+    _h(x).call("vit_unfold_gather_cast", x.data_ptr(), idx.data_ptr(), out.data_ptr(), _DT[out.dtype], B, L, P, S, N, K, _stream(x))
+    return out
+
+
+def embed_finish_gather(tokens, cls, idx, T_full: int, pos=None, dropout: Dropout = NO_DROP):
+    """embed_finish over compact tokens [B, 1 + K, D]: token t > 0 takes position row 1 + idx[b, t - 1] of pos [T_full, D]; the
+    mask is keyed by the compact row."""
+    _chk(tokens, torch.float32, "embed_finish_gather tokens")
+    B, Tc, D = tokens.shape
+    _chk_index(idx, B, Tc - 1, "embed_finish_gather idx")
+    if pos is not None and pos.numel() != T_full * D:
+        raise _cabi.VitError(f"embed_finish_gather: pos must hold [T_full={T_full}, {D}]")
+    p, seed, site = dropout
+    _h(tokens).call("vit_embed_finish_gather", tokens.data_ptr(), cls.data_ptr(), _ptr(pos), idx.data_ptr(), B, Tc, T_full, D, p,
+                    seed, site, _stream(tokens))
+    return tokens
+
+
+def embed_finish_gather_bwd(dtokens, slot, dcls, dpos=None, dropout: Dropout = NO_DROP, dpatch=None, out_dtype=torch.bfloat16,
+                            accumulate: bool = False):
+    """The backward of embed_finish_gather: dpatch [B * K, D]; dcls; dpos [T_full, D] summed through slot [B, T_full - 1]."""
+    _chk(dtokens, torch.float32, "embed_finish_gather_bwd dtokens")
+    B, Tc, D = dtokens.shape
+    N = slot.shape[1]
+    _chk_index(slot, B, N, "embed_finish_gather_bwd slot")
+    if dpos is not None and dpos.numel() != (N + 1) * D:
+        raise _cabi.VitError(f"embed_finish_gather_bwd: dpos must hold [{N + 1}, {D}]")
+    dpatch = dpatch if dpatch is not None else torch.empty((B * (Tc - 1), D), dtype=out_dtype, device=dtokens.device)
+    if dpatch.numel() != B * (Tc - 1) * D:
+        raise _cabi.VitError("embed_finish_gather_bwd: dpatch must hold [B*K, D]")
+    p, seed, site = dropout
+    _h(dtokens).call("vit_embed_finish_gather_bwd", dtokens.data_ptr(), slot.data_ptr(), dpatch.data_ptr(), _DT[dpatch.dtype],
+                     dcls.data_ptr(), _ptr(dpos), B, Tc, N + 1, D, p, seed, site, int(accumulate), _stream(dtokens))
+    return dpatch
+
+
+def rows_gather(table, idx, out=None):
+    """out[b * Tc + t, :] = table[pos(b, t), :] (pos = 0 for t = 0, 1 + idx[b, t - 1] otherwise); table f32 [T_full, W]."""
+    _chk(table, torch.float32, "rows_gather table")
+    if table.dim() != 2:
+        raise _cabi.VitError("rows_gather: table must be [T_full, W]")
+    T_full, W = table.shape
+    B, K = idx.shape
+    _chk_index(idx, B, K, "rows_gather idx")
+    out = out if out is not None else torch.empty((B * (K + 1), W), dtype=torch.float32, device=table.device)
+    _chk(out, torch.float32, "rows_gather out")
+    if out.numel() != B * (K + 1) * W:
+        raise _cabi.VitError("rows_gather: out must hold [B*(K+1), W]")
+    _h(table).call("vit_rows_gather", table.data_ptr(), idx.data_ptr(), out.data_ptr(), B, K + 1, T_full, W, _stream(table))
+    return out
+
+
+def fold_add_gather(dpatches, slot, L: int, P: int, S: int, out=None):
+    """fold_add of compact dpatches [B * K, P] read through slot [B, N]: dropped windows contribute nothing."""
+    _chk(dpatches, torch.float32, "fold_add_gather dpatches")
+    B, N = slot.shape
+    _chk_index(slot, B, N, "fold_add_gather slot")
+    K = dpatches.numel() // (B * P)
+    if dpatches.numel() != B * K * P or not 0 < K <= N:
+        raise _cabi.VitError("fold_add_gather: dpatches must hold B*K*P elements with 1 <= K <= N")
+    out = out if out is not None else torch.empty((B, L), dtype=torch.float32, device=dpatches.device)
+    _h(dpatches).call("vit_fold_add_gather", dpatches.data_ptr(), slot.data_ptr(), out.data_ptr(), B, L, P, S, N, K,
+                      _stream(dpatches))
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ elementwise
 def dropout_bwd_cast(dx, dropout: Dropout = NO_DROP, out=None, out_dtype=torch.bfloat16):
     _chk(dx, torch.float32, "dropout_bwd_cast dx")

@@ -11,6 +11,8 @@ averaging (`train.ema_decay`, vit_amd/ema.py) the update of the average is the g
 schedule skips, 1 for the first update, 1 - decay otherwise -- lives in a one-float device cell that is rewritten the same way.
 Stochastic depth (`model.drop_path_rate`) needs no mechanism of its own: the frozen launches carry each layer's rate p_i, and
 the per-sample gate is drawn from the record's keys like every dropout mask, so each replay draws a fresh one.
+Patch dropout (`model.patch_drop_rate`) needs nothing new either: the kept count K is frozen in the launches' shapes, and the
+subset each sample keeps is drawn by vit_patch_select from the record's keys, so each replay selects afresh.
 
 Scope: one process, one GPU (the RCCL exchange of N > 1 is not captured), a fused optimizer (vit_amd/optimizer.py:
 FusedAdamW, FusedLamb, FusedSGD), no trainable input preprocessor, a fixed batch shape.  The reference's step semantics are unchanged

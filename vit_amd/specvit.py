@@ -221,7 +221,8 @@ class MyViT(nn.Module):
             hs, self._kept_hidden = self._kept_hidden, None  # copies of eng.act["x"], or None when not asked for
             atts = eng.saved_attentions() if output_attentions else None
             if hooked:
-                B, T, D = pixel_values.shape[0], self.config.seq_len, self.config.hidden_size
+                # the forward's own sequence length: 1 + K tokens under patch dropout
+                B, T, D = pixel_values.shape[0], eng._last["T"], self.config.hidden_size
                 ctxs = [c.view(B, T, D) for c in eng.act["ctx"]]
         else:
             with torch.no_grad():

@@ -475,7 +475,9 @@ class Trainer:
         to eager launches for the rest of the run, with one warning."""
         from .graph import GraphedTrainStep
 
-        key = (tuple(batch[0].shape), module.model.engine.precision)
+        eng = module.model.engine
+        # the tokens a training forward keeps (patch dropout) are frozen in a capture's shapes like the batch's: part of the key
+        key = (tuple(batch[0].shape), eng.precision, eng.kept_count(True))
         if self._graphed is None:
             self._graphed = {}
         g = self._graphed.get(key)
