@@ -296,8 +296,9 @@ int vit_add_noise(vit_handle h, const float* flux, const float* error, float* ou
                   uint64_t seed, vit_stream stream);
 
 /* Rotary position embedding of ViTSelfAttentionWithRoPE (src/models/vit_with_rope.py:58-60 -> src/models/rope.py:66-131,
- * model.pos_encoding_type: 'rope'): rotates the query and key thirds of the token-major qkv buffer ([rows, ld >= 3*H*dh],
- * rows = B*T, position = row % T) in place, pairing element i of a head with element i + dh/2 (_rotate_half).
+ * model.pos_encoding_type: 'rope'): rotates the query and key thirds of the token-major qkv buffer ([rows, ld >= 2*H*dh]:
+ * only columns [0, 2*H*dh) are touched, so a q / k-only buffer is legal; rows = B*T, position = row % T) in place, pairing
+ * element i of a head with element i + dh/2 (_rotate_half).
  * cos_half / sin_half: f32 [T, dh/2] -- the first half of the reference's cached tables (rope.py:44-56), built on the
  * host by the reference's own formula.  inverse != 0 rotates by the negative angle: the backward of the rotation,
  * applied to dq / dk before the projection's weight and input gradients. */

@@ -249,6 +249,11 @@ class Handle:
         three launches a call makes)."""
         check(self.lib.vit_handle_set_option(self.h, name.encode(), int(value)), f"vit_handle_set_option({name})")
 
+    def fill_workspace(self, byte: int):
+        """Every byte of the workspace <- `byte`, on the current stream (tests: a call's result must not depend on what the
+        workspace held before it)."""
+        self._ws.fill_(int(byte) & 0xFF)
+
     def ensure_workspace(self, nbytes: int):
         if nbytes > self.workspace_bytes:
             self.set_workspace(int(nbytes * 1.25))

@@ -630,7 +630,7 @@ int vit_rope_qk(vit_handle h, void* qkv, int dtype, const float* cos_half, const
                 int H, int dh, long ld, int inverse, vit_stream stream) {
   (void)h;
   VIT_CHECK(qkv && cos_half && sin_half, VIT_ERR_ARG, "vit_rope_qk: null pointer");
-  VIT_CHECK(rows > 0 && T > 0 && H > 0 && dh > 0 && (dh % 8) == 0 && ld >= 3L * H * dh && (ld % 4) == 0, VIT_ERR_ARG,
+  VIT_CHECK(rows > 0 && T > 0 && H > 0 && dh > 0 && (dh % 8) == 0 && ld >= 2L * H * dh && (ld % 4) == 0, VIT_ERR_ARG,
             "vit_rope_qk: rows=%ld T=%d H=%d dh=%d ld=%ld (head_dim must be a multiple of 8)", rows, T, H, dh, ld);
   VIT_CHECK(dtype == VIT_BF16 || dtype == VIT_F32, VIT_ERR_ARG, "vit_rope_qk: bad dtype");
   const long total = rows * 2L * H * (dh >> 3);

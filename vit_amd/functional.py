@@ -325,9 +325,12 @@ def attention_bwd(qkv, ctx, dctx, lse, B: int, H: int, T: int, dh: int, scale: f
     return dqkv
 
 
-def attention_probs(qkv, B: int, H: int, T: int, dh: int, scale: float):
+def attention_probs(qkv, B: int, H: int, T: int, dh: int, scale: float, out=None):
     h = _h(qkv)
-    probs = torch.empty((B, H, T, T), dtype=torch.float32, device=qkv.device)
+    probs = out if out is not None else torch.empty((B, H, T, T), dtype=torch.float32, device=qkv.device)
+    _chk(probs, torch.float32, "attention_probs out")
+    if probs.numel() != B * H * T * T:
+        raise _cabi.VitError("attention_probs: out must hold [B, H, T, T]")
     h.call("vit_attention_probs", qkv.data_ptr(), probs.data_ptr(), _DT[qkv.dtype], B, H, T, dh, scale, _stream(qkv))
     return probs
 
@@ -577,13 +580,21 @@ def cast_bf16_f32(src, out, scale: float = 1.0):
 
 
 # ------------------------------------------------------------------------------------------------ head + loss
-def head_loss_fwd(last_hidden, W, b, labels, loss_kind: int):
+def head_loss_fwd(last_hidden, W, b, labels, loss_kind: int, logits=None, loss=None):
     _chk(last_hidden, torch.float32, "head_loss_fwd last_hidden")
     h = _h(last_hidden)
     B, T, D = last_hidden.shape
     Cn = W.shape[0]
-    logits = torch.empty((B, Cn), dtype=torch.float32, device=last_hidden.device)
-    loss = torch.zeros((), dtype=torch.float32, device=last_hidden.device) if labels is not None else None
+    logits = logits if logits is not None else torch.empty((B, Cn), dtype=torch.float32, device=last_hidden.device)
+    _chk(logits, torch.float32, "head_loss_fwd logits")
+    if logits.numel() != B * Cn:
+        raise _cabi.VitError("head_loss_fwd: logits must hold [B, C]")
+    if labels is None:
+        loss = None
+    elif loss is None:
+        loss = torch.zeros((), dtype=torch.float32, device=last_hidden.device)
+    else:
+        _chk(loss, torch.float32, "head_loss_fwd loss")
     h.call("vit_head_loss_fwd", last_hidden.data_ptr(), W.data_ptr(), b.data_ptr(), _ptr(labels), logits.data_ptr(),
            _ptr(loss), B, T, D, Cn, loss_kind, _stream(last_hidden))
     return logits, loss
