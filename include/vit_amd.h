@@ -387,5 +387,9 @@ int vit_adamw_step(vit_handle h, float* p, const float* g, float* m, float* v, v
 /* Patch dropout (`model.patch_drop_rate`): the per-sample token selection and the gather forms of the embedding-side kernels
  * behind which the encoder runs at 1 + K tokens.  Declared in their own header, part of this ABI. */
 #include "vit_amd_patchdrop.h"
+/* Masked spectrum modelling (`model.task_type: mim`): the block mask, the embedding finish that substitutes the mask token and
+ * its backward, and the reconstruction loss that reads its target from the signal.  Declared in their own header, part of
+ * this ABI. */
+#include "vit_amd_mim.h"
 
 #endif /* VIT_AMD_H_ */

@@ -158,6 +158,16 @@ _PROTOS = {
     "vit_embed_finish_gather_bwd": [_P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _F, _U64, _U64, _I, _P],
     "vit_rows_gather": [_P, _P, _P, _P, _I, _I, _I, _I, _P],
     "vit_fold_add_gather": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
+    # masked spectrum modelling (include/vit_amd_mim.h): (h, slot_blocks, mask, B, N, Nb, span, stream) /
+    # (h, tokens, cls, pos, mask, mask_token, B, T, D, p, seed, site, stream) /
+    # (h, dtokens, mask, dpatch, dpatch_dtype, dcls, dpos, dmask_token, B, T, D, p, seed, site, accumulate, stream) /
+    # (h, x, pred, pred_dtype, mask, loss, count, B, L, P, S, N, T, kind, norm_target, stream) /
+    # (h, x, pred, pred_dtype, mask, count, dloss, dpred, dpred_dtype, B, L, P, S, N, T, kind, norm_target, stream)
+    "vit_mim_mask": [_P, _P, _P, _I, _I, _I, _I, _P],
+    "vit_embed_finish_masked": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _U64, _U64, _P],
+    "vit_embed_finish_masked_bwd": [_P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _F, _U64, _U64, _I, _P],
+    "vit_mim_loss_fwd": [_P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
+    "vit_mim_loss_bwd": [_P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
 }
 _RESTYPES = {"vit_last_error": C.c_char_p, "vit_last_gemm_kernel": C.c_char_p, "vit_workspace_needed": C.c_size_t}
 
@@ -166,7 +176,7 @@ _lock = threading.Lock()
 
 
 def declared_symbols(header_path: str = HEADER_PATH):
-    """Every function the C header declares, the headers it includes from its own directory (vit_amd_cov.h, vit_amd_optim.h, vit_amd_ema.h, vit_amd_droppath.h, vit_amd_layerscale.h, vit_amd_mix.h, vit_amd_patchdrop.h) included (used by
+    """Every function the C header declares, the headers it includes from its own directory (vit_amd_cov.h, vit_amd_optim.h, vit_amd_ema.h, vit_amd_droppath.h, vit_amd_layerscale.h, vit_amd_mix.h, vit_amd_patchdrop.h, vit_amd_mim.h) included (used by
     the CPU test that checks the library exports them all)."""
     seen, names, todo = set(), set(), [os.path.abspath(header_path)]
     while todo:

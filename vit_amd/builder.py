@@ -19,7 +19,7 @@ from .config import get_vit_config
 from .preprocessor import LinearPreprocessor, PrefilledAttention, compute_pca_matrix, compute_zca_matrix, load_cov_stats
 from .specvit import MyViT
 
-__all__ = ["get_model", "get_vit_config"]
+__all__ = ["get_model", "get_vit_config", "init_from_state"]
 
 
 @dataclass
@@ -85,12 +85,43 @@ def _build_preprocessor(preproc_type: str, warmup_cfg: dict, stats: dict, initia
     return front.module, front.out_dim, front.tag
 
 
+def init_from_state(model, state: Dict[str, torch.Tensor], verbose: bool = True):
+    """The fine-tuning hand-over: copy into `model` every tensor of `state` (a network state_dict, e.g. a masked pre-training
+    run's) whose name and shape match one of the model's, and leave the rest -- the other task's head (`decoder.*` /
+    `classifier.*` / `regressor.*`), `mask_token` -- alone.  Returns (loaded, skipped_in_checkpoint, skipped_in_model), three
+    sorted name lists, and prints the two skipped ones; raises ValueError when nothing matched."""
+    own = model.state_dict()
+    loaded = sorted(k for k, v in state.items() if k in own and tuple(own[k].shape) == tuple(v.shape))
+    skipped_ckpt = sorted(set(state) - set(loaded))
+    skipped_model = sorted(set(own) - set(loaded))
+    if not loaded:
+        raise ValueError(f"model.init_from: no tensor of the checkpoint matches the model by name and shape "
+                         f"(checkpoint: {sorted(state)[:4]} ...; model: {sorted(own)[:4]} ...)")
+    model.load_state_dict({k: state[k] for k in loaded}, strict=False)
+    if verbose:
+        print(f"[init_from] loaded {len(loaded)} tensors; not in the model (skipped): {skipped_ckpt}; "
+              f"not in the checkpoint (kept as initialised): {skipped_model}")
+    return loaded, skipped_ckpt, skipped_model
+
+
+def _init_from(model, config):
+    """`model.init_from: <checkpoint>`: a Lightning-layout checkpoint (or a bare state_dict) read as `launch.sh test` reads
+    one -- a run with weight averaging stored its averaged weights there."""
+    path = (config.get("model") or {}).get("init_from")
+    if path in (None, "", "none", "None"):
+        return model
+    from .trainer import load_checkpoint_file, model_state_from_checkpoint
+
+    init_from_state(model, model_state_from_checkpoint(load_checkpoint_file(path)))
+    return model
+
+
 def get_model(config):
     warm = config.get("warmup") or {}
     loss_name = (config.get("loss") or {}).get("name")
     kind = warm.get("preprocessor")
     if kind is None or str(kind).lower() in ("none", "null"):
-        return MyViT(get_vit_config(config), loss_name=loss_name, model_name="ViT", full_config=config)
+        return _init_from(MyViT(get_vit_config(config), loss_name=loss_name, model_name="ViT", full_config=config), config)
 
     kind = str(kind).lower()
     if warm.get("cov_path") is None:
@@ -103,5 +134,5 @@ def get_model(config):
     module, width_out, tag = _build_preprocessor(kind, warm, stats)
     # the ViT is sized for what the preprocessor emits; the reference writes that back into the config too (:176-178)
     config["model"]["image_size"] = width_out
-    return MyViT(get_vit_config(config), loss_name=loss_name, model_name=f"{tag}_ViT", preprocessor=module,
-                 full_config=config)
+    return _init_from(MyViT(get_vit_config(config), loss_name=loss_name, model_name=f"{tag}_ViT", preprocessor=module,
+                            full_config=config), config)

@@ -45,12 +45,32 @@ class ViTConfig:
     # (plus CLS) and the encoder runs at that shorter sequence; evaluation sees every token (this build's key; 0 = the
     # reference's arithmetic)
     patch_drop_rate: float = 0.0
+    # masked spectrum modelling (task_type 'mim', this build's key; the YAML's `mim:` section): the fraction of patch blocks a
+    # forward masks, the block length in patches, the reconstruction loss ('l1' | 'mse') and MAE's per-window target
+    # normalisation.  Read by a 'mim' model only.
+    mim_mask_ratio: float = 0.6
+    mim_span: int = 1
+    mim_loss: str = "l1"
+    mim_norm_target: bool = False
     use_return_dict: bool = True
 
     def __post_init__(self):
         rate = self.patch_drop_rate
         if isinstance(rate, bool) or not isinstance(rate, (int, float)) or not 0.0 <= float(rate) < 1.0:
             raise ValueError(f"patch_drop_rate must lie in [0, 1) (got {rate!r})")
+        if self.task_type == "mim":
+            ratio, span = self.mim_mask_ratio, self.mim_span
+            if isinstance(ratio, bool) or not isinstance(ratio, (int, float)) or not 0.0 < float(ratio) < 1.0:
+                raise ValueError(f"mim.mask_ratio must lie in (0, 1) (got {ratio!r})")
+            if isinstance(span, bool) or not isinstance(span, int) or span < 1:
+                raise ValueError(f"mim.span must be an integer >= 1 (got {span!r})")
+            if self.mim_loss not in ("l1", "mse"):
+                raise ValueError(f"mim.loss must be 'l1' or 'mse' (got {self.mim_loss!r})")
+            if not isinstance(self.mim_norm_target, bool):
+                raise ValueError(f"mim.norm_target must be true or false (got {self.mim_norm_target!r})")
+            if float(rate) > 0.0:
+                raise ValueError(f"model.patch_drop_rate ({rate}) and model.task_type 'mim' exclude each other: both draw their "
+                                 f"patch selection from the same site, and a masked model runs at every token")
 
     @property
     def intermediate_size(self) -> int:  # builder.py:243
@@ -92,6 +112,13 @@ def kept_patches(num_patches: int, rate: float) -> int:
     return max(1, int(num_patches * (1.0 - rate)))
 
 
+def mim_blocks(num_patches: int, span: int, mask_ratio: float):
+    """(Nb, Kb) of masked spectrum modelling: the patches fall into Nb = ceil(N / span) blocks of `span` consecutive patches (the
+    last one may be short), of which Kb = max(1, int(Nb * (1 - mask_ratio))) stay visible -- kept_patches' expression."""
+    nb = -(-int(num_patches) // int(span))
+    return nb, max(1, int(nb * (1.0 - float(mask_ratio))))
+
+
 def _targets_in(param) -> int:
     """How many regression targets `data.param` names: a comma-separated string or a list; anything else (None, '', []) = 1."""
     if isinstance(param, str):
@@ -121,6 +148,19 @@ def get_vit_config(config) -> ViTConfig:
         num_labels = int(model.get("num_labels", 1) or 1)
     optional = {k: model[k] for k in ("stride_ratio", "stride_size", "pos_encoding_type", "max_position_embeddings", "rope_base",
                                       "drop_path_rate", "layer_scale_init", "patch_drop_rate") if k in model}
+    if task == "mim":
+        # the `mim:` section: {mask_ratio, span, loss, norm_target}; anything else in it is a spelling mistake
+        section = dict(config.get("mim") or {})
+        unknown = sorted(set(section) - {"mask_ratio", "span", "loss", "norm_target"})
+        if unknown:
+            raise ValueError(f"mim: unknown key(s) {unknown}; the section takes mask_ratio, span, loss, norm_target")
+        if "loss" in section:
+            section["loss"] = str(section["loss"]).lower()
+        optional.update({"mim_" + k: v for k, v in section.items()})
+        if (config.get("augment") or {}).get("mixup_alpha") or (config.get("augment") or {}).get("cutmix_alpha"):
+            raise ValueError("augment (Mixup / CutMix) and model.task_type 'mim' exclude each other: a masked model has no "
+                             "labels to mix, and its target is the signal it was given")
+        model["task_type"] = task
     return ViTConfig(
         task_type=model["task_type"], image_size=model["image_size"], patch_size=model["patch_size"],
         hidden_size=model["hidden_size"], num_hidden_layers=model["num_hidden_layers"],

@@ -43,6 +43,8 @@ class SpecDataset:
         elif task == "reg":
             self.labels = params.float()
             self._normalize(eps)
+        elif task == "mim":  # masked spectrum modelling trains on the spectra alone: the batch contract keeps a labels column
+            self.labels = torch.zeros(self.flux.shape[0])
         else:
             raise ValueError(f"Unsupported task_type '{task}'")
         self.noisy = None
@@ -89,7 +91,8 @@ class SpecDataset:
             if k not in raw.files:
                 raise KeyError(f"Requested array '{k}' not found in {path}: {list(raw.files)}")
         cols = [torch.from_numpy(np.asarray(raw[k][:num_samples])).float() for k in param_keys]
-        params = cols[0] if len(cols) == 1 else torch.stack(cols, dim=1)
+        # no parameter named (an unlabelled 'mim' run): an empty column
+        params = torch.zeros(0) if not cols else cols[0] if len(cols) == 1 else torch.stack(cols, dim=1)
         return cls(raw["flux"][:num_samples], raw["error"][:num_samples], params, **kw)
 
     @classmethod
@@ -104,7 +107,7 @@ class SpecDataset:
             error = torch.tensor(f["dataset/arrays/error/value"][:num_samples])
         df = pd.read_hdf(path)[:num_samples]
         cols = [torch.tensor(df[k].values).float() for k in param_keys]
-        return cls(flux, error, cols[0] if len(cols) == 1 else torch.stack(cols, dim=1), **kw)
+        return cls(flux, error, torch.zeros(0) if not cols else cols[0] if len(cols) == 1 else torch.stack(cols, dim=1), **kw)
 
 
 def _step_reads(ds: "SpecDataset") -> Tuple[bool, ...]:
@@ -411,6 +414,8 @@ class SpecDataModule:
         model = config.get("model", {}) or {}
         task = (model.get("task_type") or model.get("task") or "cls").lower()
         self.task = "cls" if task in ("classification", "cls", "class") else "reg"  # vit.py:20-26
+        if task == "mim":  # this build's: spectra without labels (data.param is not read)
+            self.task, data = "mim", dict(data, param=None)
         self.paths = {"train": data.get("file_path") or data.get("train_path"), "val": data.get("val_path"),
                       "test": data.get("test_path")}
         self.num_samples = data.get("num_samples")

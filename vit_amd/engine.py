@@ -20,6 +20,10 @@ Data layout in HBM (one MI355X, 288 GB: nothing is recomputed or re-materialised
            that forward's 1 + K -- the arena is keyed and sized by it, and also holds keep int32 [B, K] (the kept patches,
            ascending), slot int32 [B, N] (its inverse, -1 = dropped) and, with RoPE, cos / sin tables f32 [M, head_dim / 2]
            gathered per token row.  Evaluation arenas keep cfg.seq_len.
+  Masked spectrum modelling (cfg.task_type 'mim'): the arena also holds mim_mask int32 [B, N] (non-zero = masked), the block
+           selection it is expanded from (mim_keep [B, Kb], mim_slot [B, Nb]), the decoder's output mim_pred f32 [M, P], in bf16
+           mode the operand copy mim_last bf16 [M, D] of `last`, and for training mim_dpred [M, P] (operand dtype).  `last` then
+           has the GEMMs' zeroed pad rows, the CLS tail is off, and the head is the Linear `decoder` [P, D].
 Dropout masks are regenerated from (seed, site) in backward; no mask is stored.
 
 A layer's tail -- out-projection, LN-after, FC1 + GELU, FC2 behind its attention -- is stated once per direction
@@ -38,12 +42,13 @@ import torch
 from . import _cabi
 from . import functional as vf
 from ._cabi import ACT_GELU, LOSS_BCE, LOSS_CE, LOSS_L1, LOSS_MSE, LOSS_SOFT_CE, VitError
-from .config import ViTConfig, kept_patches
+from .config import ViTConfig, kept_patches, mim_blocks
 
 ALIGN = 8  # elements; keeps every view 32-byte (f32) / 16-byte (bf16) aligned
 
 EMBED = "vit.embeddings."
 PROJ = EMBED + "patch_embeddings.projection"
+MASK_TOKEN = EMBED + "mask_token"  # task_type 'mim' only (HF ViTForMaskedImageModeling's name)
 # the name stems of one encoder layer's parameters (+ ".weight" / ".bias"): ViTEngine.names[i].fc1 etc.
 LayerNames = collections.namedtuple("LayerNames", "ln1 q wo ln2 fc1 fc2")
 _LAYER_STEMS = LayerNames("layernorm_before", "attention.attention.query", "attention.output.dense", "layernorm_after",
@@ -68,6 +73,8 @@ def resolved_loss(task_type: str, loss_name: str) -> Tuple[str, int]:
     if task_type == "reg":
         ln = loss_name or "l2"
         return ln, (LOSS_L1 if "l1" in ln.lower() else LOSS_MSE)
+    if task_type == "mim":  # the reconstruction loss is the config's (mim.loss), not the trainer's loss_name
+        return "mim", LOSS_MSE
     raise ValueError(f"Unsupported task_type '{task_type}'")
 
 
@@ -95,6 +102,9 @@ class ParamLayout:
             add(e + "position_embeddings", (1, T, D))
         add(e + "patch_embeddings.projection.weight", (D, P) if cfg.proj_fn == "SW" else (D, 1, P))
         add(e + "patch_embeddings.projection.bias", (D,))
+        mim = cfg.task_type == "mim"
+        if mim:  # the last entry of the embedding block: its bucket, its gradient exchange
+            add(e + "mask_token", (1, 1, D))
         self.embed_end = off
         for i in range(cfg.num_hidden_layers):
             p = f"vit.encoder.layer.{i}."
@@ -120,10 +130,11 @@ class ParamLayout:
         self.tail_start = off
         add("vit.layernorm.weight", (D,))
         add("vit.layernorm.bias", (D,))
-        head = "classifier" if cfg.task_type == "cls" else "regressor"
+        head = "decoder" if mim else "classifier" if cfg.task_type == "cls" else "regressor"
         self.head = head
-        add(head + ".weight", (cfg.num_labels, D))
-        add(head + ".bias", (cfg.num_labels,))
+        n_out = P if mim else cfg.num_labels  # the decoder maps a token to the P samples of its window
+        add(head + ".weight", (n_out, D))
+        add(head + ".bias", (n_out,))
         self.n_trainable = off
         add("vit.pooler.dense.weight", (D, D))
         add("vit.pooler.dense.bias", (D,))
@@ -133,6 +144,8 @@ class ParamLayout:
         if cfg.pos_encoding_type == "learned":
             order.append(e + "position_embeddings")
         order += [e + "patch_embeddings.projection.weight", e + "patch_embeddings.projection.bias"]
+        if mim:
+            order.append(e + "mask_token")
         for i in range(cfg.num_hidden_layers):
             p = f"vit.encoder.layer.{i}."
             for n in ("query", "key", "value"):
@@ -229,6 +242,16 @@ class ViTEngine:
             raise ValueError(f"layer_scale_init must be a finite number > 0, or None for no LayerScale (got {ls!r})")
         self.cfg = cfg
         self.loss_name, self.loss_kind = resolved_loss(cfg.task_type, loss_name)
+        # masked spectrum modelling (task_type 'mim'): every forward masks a block selection of the patch
+        # tokens and the loss is the reconstruction of the masked windows; labels are ignored
+        self.mim = cfg.task_type == "mim"
+        if self.mim:
+            self.loss_kind = LOSS_L1 if cfg.mim_loss == "l1" else LOSS_MSE
+        # an optional [B, N] device tensor (bool or integer, non-zero = masked) that replaces the drawn mask of the next
+        # forwards, like patch_keep does for patch dropout.  None: draw.
+        self.mim_mask: Optional[torch.Tensor] = None
+        # evaluation forwards draw their masks from a counter of their own (reset_mim_eval), not from the training step
+        self.mim_eval_counter = 0
         # a classification call whose labels are floating soft targets [B, num_labels] (Mixup / CutMix / label smoothing,
         # vit_amd/mix.py) runs this kind instead, forward and backward; int64 labels run loss_kind as ever (set_soft_loss)
         self.soft_loss_kind = LOSS_SOFT_CE
@@ -546,7 +569,8 @@ class ViTEngine:
             u=[G(Fd, b16) for _ in range(nl)], g=[G(Fd, b16) for _ in range(nl)],
             mean1=[E((M,), f32) for _ in range(nl)], rstd1=[E((M,), f32) for _ in range(nl)],
             mean2=[E((M,), f32) for _ in range(nl)], rstd2=[E((M,), f32) for _ in range(nl)],
-            last=E((B, T, D), f32), meanF=E((M,), f32), rstdF=E((M,), f32),
+            # 'mim': the decoder's products read every row of `last` (zeroed pad rows, like every GEMM operand)
+            last=G(D, f32).view(B, T, D) if self.mim else E((B, T, D), f32), meanF=E((M,), f32), rstdF=E((M,), f32),
             y=G(D, b16),  # dropout(Linear(.)) of the attention-output / FC2 projection, until the next LayerNorm adds it
             # the last layer's CLS tail: one row per image
             c_y=E((B, D), b16), c_x1=C(D, f32), c_h2=C(D, b16), c_u=C(Fd, b16), c_g=C(Fd, b16),
@@ -558,9 +582,18 @@ class ViTEngine:
             act.update(keep=E((B, N), i32), slot=E((B, c.num_patches), i32))
             if c.pos_encoding_type == "rope":
                 act.update(rope_cos=E((M, c.head_dim // 2), f32), rope_sin=E((M, c.head_dim // 2), f32))
+        if self.mim:
+            # the patch mask and the block selection it is expanded from; the decoder's operand copy of `last` in bf16 mode
+            # (in f32 mode the x3 products read `last` itself); its output, f32 in either mode
+            i32 = torch.int32
+            nb, kb = mim_blocks(N, c.mim_span, c.mim_mask_ratio)
+            act.update(mim_mask=E((B, N), i32), mim_keep=E((B, kb), i32), mim_slot=E((B, nb), i32),
+                       mim_last=G(D, b16) if self.precision == "bf16" else act["last"].view(M, D), mim_pred=E((M, P), f32))
         tmp = {}
+        if train and self.mim:
+            tmp["mim_dpred"] = G(P, b16)
         if train:
-            tmp = dict(
+            tmp.update(
                 dxa=E((M, D), f32), dxb=E((M, D), f32), dy=G(D, b16), dy2=G(D, b16), dU=G(Fd, b16), dh=G(D, b16),
                 dqkv=G(3 * D, b16), dctx=G(D, b16), delta=E((B * H, T), f32), dpatch=E((B * N, D), b16),
                 dlast=E((B, T, D), f32),
@@ -611,6 +644,37 @@ class ViTEngine:
         if not training or float(c.patch_drop_rate) <= 0.0 or K >= c.num_patches:
             return None
         return K
+
+    def reset_mim_eval(self):
+        """The next evaluation forward draws the first evaluation mask again (MyViT.eval() calls this)."""
+        self.mim_eval_counter = 0
+
+    def mim_seed(self, training: bool, step_seed: int) -> int:
+        """The seed a 'mim' forward draws its mask from.  Training: the step's seed (the dropout masks' own).  Evaluation: a
+        pure function of (base_seed, k), k = the evaluation forwards since reset_mim_eval():
+            (base_seed ^ 0x6D696D5F6576616C) + 0x9E3779B97F4A7C15 * (k + 1)   (mod 2^64)
+        so every validation epoch sees the masks of the one before, whatever the batches hold."""
+        if training:
+            return step_seed
+        k, self.mim_eval_counter = self.mim_eval_counter, self.mim_eval_counter + 1
+        return ((self.base_seed ^ 0x6D696D5F6576616C) + 0x9E3779B97F4A7C15 * (k + 1)) & 0xFFFFFFFFFFFFFFFF
+
+    def _mim_select(self, B: int, seed: int, training: bool) -> torch.Tensor:
+        """This forward's patch mask, int32 [B, N] in the arena: the caller's (`mim_mask`), or drawn -- vit_patch_select keeps Kb
+        of the Nb blocks of `mim_span` patches visible, at patch dropout's site (the two features exclude each other), and
+        vit_mim_mask expands the selection.  A step record bound to the handle varies the draw per replay of a captured step."""
+        c, a = self.cfg, self.act
+        N = c.num_patches
+        mask, given = a["mim_mask"], self.mim_mask
+        if given is not None:
+            if not isinstance(given, torch.Tensor) or not given.is_cuda or tuple(given.shape) != (B, N) or given.is_floating_point():
+                raise ValueError(f"mim_mask / bool_masked_pos must be a bool or integer [{B}, {N}] device tensor (non-zero = "
+                                 f"masked), got {getattr(given, 'dtype', type(given))} {tuple(getattr(given, 'shape', ()))}")
+            mask.copy_(given != 0)
+            return mask
+        nb, kb = mim_blocks(N, c.mim_span, c.mim_mask_ratio)
+        vf.patch_select(B, nb, kb, self.mim_seed(training, seed), self._site(c.num_hidden_layers, 0), a["mim_keep"], a["mim_slot"])
+        return vf.mim_mask(a["mim_slot"], c.mim_span, mask)
 
     def path_rates(self, training: bool = True) -> Optional[List[float]]:
         """Stochastic depth: the drop probability of layer i's two residual branches, the usual linear schedule
@@ -674,10 +738,15 @@ class ViTEngine:
         pos = self.p(EMBED + "position_embeddings").view(c.seq_len, D) if c.pos_encoding_type == "learned" else None
         rope = self._rope_tables(c.seq_len) if c.pos_encoding_type == "rope" else None
         if K is None:
+            mask = self._mim_select(B, seed, training) if self.mim else None
             vf.unfold_cast(x, P, S, N, out=a["patches"])  # bf16 or f32 patches, per the arena dtype
             vf.gemm(a["patches"], self.W(PROJ).view(D, P), M=B * N, N=D, K=P, out=x0.view(M, D), bias=self.b(PROJ),
                     row_map=(N, T, 1))
-            vf.embed_finish(x0, self.p(EMBED + "cls_token").view(D), pos, dropout=(ph, seed, 0))
+            if mask is None:
+                vf.embed_finish(x0, self.p(EMBED + "cls_token").view(D), pos, dropout=(ph, seed, 0))
+            else:  # a masked patch's projected token gives way to the mask token, in front of pos-emb and dropout
+                vf.embed_finish_masked(x0, self.p(EMBED + "cls_token").view(D), mask, self.p(MASK_TOKEN).view(D), pos,
+                                       dropout=(ph, seed, 0))
         else:
             # patch dropout: select (or take the caller's selection), then the gather forms of the same three steps; everything
             # behind them is the path below at T = 1 + K.  The selection's site is the first one behind the layers'.
@@ -697,7 +766,7 @@ class ViTEngine:
                 rope = (vf.rows_gather(rope[0], keep, out=a["rope_cos"]), vf.rows_gather(rope[1], keep, out=a["rope_sin"]))
 
         atts = [] if output_attentions else None
-        tail = bool(self.cls_tail) and L > 0 and not output_hidden_states
+        tail = bool(self.cls_tail) and L > 0 and not output_hidden_states and not self.mim  # the decoder reads every row
         r = full
         if L == 0:
             self._ln(full.xL, "vit.layernorm", full.last2, full.meanF, full.rstdF)
@@ -726,6 +795,18 @@ class ViTEngine:
             self._tail_fwd(r, i, j, a["x"][i].view(M, D), then, ph, seed, need_grad, pd)
         hn = self.layout.head
         kind = self.loss_kind
+        if self.mim:
+            # pred[b, n, :] = decoder(last[b, 1 + n, :]) over all M rows (the CLS row's output is ignored by the loss), then the
+            # reconstruction loss of the masked windows against the signal this forward was given
+            if self.precision == "bf16":
+                vf.cast_f32_bf16(full.last2[:M], a["mim_last"])
+            pred = vf.gemm(a["mim_last"], self.W(hn), M=M, N=P, K=D, out=a["mim_pred"], bias=self.b(hn))
+            loss, count = vf.mim_loss_fwd(x, pred, mask, P, S, kind, c.mim_norm_target)
+            recon = pred.view(B, T, P)[:, 1:, :]
+            self._last = dict(B=B, seed=seed, ph=ph, pa=pa, pd=pd, labels=None, logits=recon, gen=self._gen, grad=need_grad,
+                              tail=False, kind=kind, T=T, keep=None, mim=True, mask=mask, count=count, x=x, pred=pred)
+            hs = [t.clone() for t in a["x"]] if output_hidden_states else None
+            return loss, recon, hs, atts
         if labels is not None:
             labels = labels.to(self.flat.device)
             if kind == LOSS_CE and labels.is_floating_point() and tuple(labels.shape) == (B, c.num_labels):
@@ -736,7 +817,7 @@ class ViTEngine:
                 raise ValueError(f"labels has {labels.numel()} elements, expected {n_expected}")
         logits, loss = vf.head_loss_fwd(r.last, self.p(hn + ".weight"), self.p(hn + ".bias"), labels, kind)
         self._last = dict(B=B, seed=seed, ph=ph, pa=pa, pd=pd, labels=labels, logits=logits, gen=self._gen, grad=need_grad,
-                          tail=tail, kind=kind, T=T, keep=a["keep"] if K is not None else None)
+                          tail=tail, kind=kind, T=T, keep=a["keep"] if K is not None else None, mim=False)
         hs = [t.clone() for t in a["x"]] if output_hidden_states else None
         return loss, logits, hs, atts
 
@@ -957,7 +1038,7 @@ class ViTEngine:
         backward belongs to (ViTEngine._gen at that time); the arena holds one forward's activations, so a later forward
         (a second loss term, an eval pass, a viz hook) makes them unavailable and that is an error, not a wrong gradient."""
         st = self._last
-        if st is None or st["labels"] is None:
+        if st is None or (st["labels"] is None and not st["mim"]):
             raise VitError("backward without a preceding forward(labels=...)")
         if not st["grad"] or (gen is not None and gen != st["gen"]) or st["gen"] != self._gen:
             raise VitError("backward: the activations of that forward are gone -- another forward ran on this model in "
@@ -977,9 +1058,20 @@ class ViTEngine:
         dloss = dloss.reshape(1).to(torch.float32).contiguous()
         full, cls = self._rows
         r = cls if st["tail"] else full  # the rows the backward walks until the last layer's LN-before
-        vf.head_loss_bwd(r.last, self.p(hn + ".weight"), st["logits"], st["labels"], dloss, st["kind"], dlast=r.dlast,
-                         dW=self.dW(hn), db=self.db(hn))
-        self._setup_side()
+        if st["mim"]:
+            # dpred (operand dtype; CLS and unmasked rows exact zeros), then the decoder Linear's three products:
+            # dlast = dpred W, dW = dpred^T last beside the data path, db = the column sums of dpred
+            self._setup_side()
+            dpred = t["mim_dpred"]
+            vf.mim_loss_bwd(st["x"], st["pred"], st["mask"], st["count"], dloss, P, c.stride, st["kind"], c.mim_norm_target,
+                            dpred=dpred)
+            vf.gemm(dpred, self.W(hn), M=M, N=D, K=P, b_trans=True, out=full.dlast.view(M, D))
+            self._dw(full, dpred, a["mim_last"], self.dW(hn))
+            vf.colsum(dpred, out=self.db(hn), accumulate=self._accum)
+        else:
+            vf.head_loss_bwd(r.last, self.p(hn + ".weight"), st["logits"], st["labels"], dloss, st["kind"], dlast=r.dlast,
+                             dW=self.dW(hn), db=self.db(hn))
+            self._setup_side()
         dx, spare = r.dx  # the residual gradient and the buffer the next LayerNorm backward writes it to
         self._ln_bwd(r, "vit.layernorm", r.dlast.view(-1, D), r.xL, r.meanF, r.rstdF, None, dx,
                      **self._fc2_dy(r, L - 1, ph, seed, pd))
@@ -1012,7 +1104,10 @@ class ViTEngine:
             self._unfold_layer_scale(i)
             self._notify(*self.layout.layer_ranges[i])
         dpos = self.g(EMBED + "position_embeddings").view(c.seq_len, D) if c.pos_encoding_type == "learned" else None
-        if keep is None:
+        if st["mim"]:  # masked rows: a zero dpatch row, their gradient goes to the mask token
+            vf.embed_finish_masked_bwd(dx.view(B, T, D), st["mask"], self.g(EMBED + "cls_token").view(D), self.g(MASK_TOKEN).view(D),
+                                       dpos, dropout=(ph, seed, 0), dpatch=t["dpatch"])
+        elif keep is None:
             vf.embed_finish_bwd(dx.view(B, T, D), self.g(EMBED + "cls_token").view(D), dpos, dropout=(ph, seed, 0),
                                 dpatch=t["dpatch"])  # dtype follows the buffer
         else:  # dpos is summed through the inverse map: rows of patches nobody kept come out zero

@@ -504,6 +504,86 @@ def fold_add_gather(dpatches, slot, L: int, P: int, S: int, out=None):
     return out
 
 
+# ------------------------------------------------------------------------------------------------ masked spectrum modelling
+def mim_mask(slot_blocks, span: int, mask):
+    """mask int32 [B, N] <- slot_blocks[b, n // span] < 0: the block selection [B, ceil(N / span)] expanded to patches."""
+    B, N = mask.shape
+    _chk_index(mask, B, N, "mim_mask mask")
+    _chk_index(slot_blocks, B, slot_blocks.shape[1], "mim_mask slot_blocks")
+    _h(mask).call("vit_mim_mask", slot_blocks.data_ptr(), mask.data_ptr(), B, N, slot_blocks.shape[1], int(span), _stream(mask))
+    return mask
+
+
+def embed_finish_masked(tokens, cls, mask, mask_token, pos=None, dropout: Dropout = NO_DROP):
+    """embed_finish with the projected token of every masked patch (mask int32 [B, T - 1] non-zero) replaced by mask_token [D]."""
+    _chk(tokens, torch.float32, "embed_finish_masked tokens")
+    B, T, D = tokens.shape
+    _chk_index(mask, B, T - 1, "embed_finish_masked mask")
+    _chk(mask_token, torch.float32, "embed_finish_masked mask_token")
+    if mask_token.numel() != D or cls.numel() != D or (pos is not None and pos.numel() != T * D):
+        raise _cabi.VitError(f"embed_finish_masked: cls and mask_token must hold [{D}], pos [{T}, {D}]")
+    p, seed, site = dropout
+    _h(tokens).call("vit_embed_finish_masked", tokens.data_ptr(), cls.data_ptr(), _ptr(pos), mask.data_ptr(), mask_token.data_ptr(),
+                    B, T, D, p, seed, site, _stream(tokens))
+    return tokens
+
+
+def embed_finish_masked_bwd(dtokens, mask, dcls, dmask_token, dpos=None, dropout: Dropout = NO_DROP, dpatch=None,
+                            out_dtype=torch.bfloat16, accumulate: bool = False):
+    """The backward of embed_finish_masked: dpatch [B * N, D] with exact zeros in the masked rows; dcls, dpos as
+    embed_finish_bwd's; dmask_token [D] the sum over the masked rows."""
+    _chk(dtokens, torch.float32, "embed_finish_masked_bwd dtokens")
+    B, T, D = dtokens.shape
+    _chk_index(mask, B, T - 1, "embed_finish_masked_bwd mask")
+    _chk(dmask_token, torch.float32, "embed_finish_masked_bwd dmask_token")
+    if dmask_token.numel() != D or dcls.numel() != D or (dpos is not None and dpos.numel() != T * D):
+        raise _cabi.VitError(f"embed_finish_masked_bwd: dcls and dmask_token must hold [{D}], dpos [{T}, {D}]")
+    dpatch = dpatch if dpatch is not None else torch.empty((B * (T - 1), D), dtype=out_dtype, device=dtokens.device)
+    if dpatch.numel() != B * (T - 1) * D:
+        raise _cabi.VitError("embed_finish_masked_bwd: dpatch must hold [B*N, D]")
+    p, seed, site = dropout
+    _h(dtokens).call("vit_embed_finish_masked_bwd", dtokens.data_ptr(), mask.data_ptr(), dpatch.data_ptr(), _DT[dpatch.dtype],
+                     dcls.data_ptr(), _ptr(dpos), dmask_token.data_ptr(), B, T, D, p, seed, site, int(accumulate), _stream(dtokens))
+    return dpatch
+
+
+def _chk_mim(x, pred, mask, P: int, who: str):
+    _chk(x, torch.float32, who + " x")
+    B, L = x.shape
+    N = mask.shape[1]
+    _chk_index(mask, B, N, who + " mask")
+    if pred.dtype not in _DT or not pred.is_contiguous() or pred.numel() != B * (N + 1) * P:
+        raise _cabi.VitError(f"{who}: pred must be a contiguous f32 / bf16 tensor holding [B*(N+1)={B * (N + 1)}, P={P}]")
+    return B, L, N
+
+
+def mim_loss_fwd(x, pred, mask, P: int, S: int, kind: int, norm_target: bool = False, loss=None, count=None):
+    """(loss f32 [], count int32 []): the masked reconstruction loss of pred [B * (N + 1), P] against the windows of x [B, L]
+    (vit_mim_loss_fwd); count = the number of masked windows, the loss's denominator / P."""
+    B, L, N = _chk_mim(x, pred, mask, P, "mim_loss_fwd")
+    loss = loss if loss is not None else torch.empty((), dtype=torch.float32, device=x.device)
+    count = count if count is not None else torch.empty((), dtype=torch.int32, device=x.device)
+    _chk(loss, torch.float32, "mim_loss_fwd loss")
+    _chk(count, torch.int32, "mim_loss_fwd count")
+    _h(x).call("vit_mim_loss_fwd", x.data_ptr(), pred.data_ptr(), _DT[pred.dtype], mask.data_ptr(), loss.data_ptr(),
+               count.data_ptr(), B, L, P, S, N, N + 1, kind, int(bool(norm_target)), _stream(x))
+    return loss, count
+
+
+def mim_loss_bwd(x, pred, mask, count, dloss, P: int, S: int, kind: int, norm_target: bool = False, dpred=None,
+                 out_dtype=torch.float32):
+    """dpred [B * (N + 1), P] (dtype of the buffer): zeros in CLS and unmasked rows (vit_mim_loss_bwd)."""
+    B, L, N = _chk_mim(x, pred, mask, P, "mim_loss_bwd")
+    _chk(count, torch.int32, "mim_loss_bwd count")
+    _chk(dloss, torch.float32, "mim_loss_bwd dloss")
+    dpred = dpred if dpred is not None else torch.empty((B * (N + 1), P), dtype=out_dtype, device=x.device)
+    if dpred.dtype not in _DT or not dpred.is_contiguous() or dpred.numel() != B * (N + 1) * P:
+        raise _cabi.VitError("mim_loss_bwd: dpred must be a contiguous f32 / bf16 tensor holding [B*(N+1), P]")
+    _h(x).call("vit_mim_loss_bwd", x.data_ptr(), pred.data_ptr(), _DT[pred.dtype], mask.data_ptr(), count.data_ptr(),
+               dloss.data_ptr(), dpred.data_ptr(), _DT[dpred.dtype], B, L, P, S, N, N + 1, kind, int(bool(norm_target)), _stream(x))
+    return dpred
+
+
 # ------------------------------------------------------------------------------------------------ elementwise
 def dropout_bwd_cast(dx, dropout: Dropout = NO_DROP, out=None, out_dtype=torch.bfloat16):
     _chk(dx, torch.float32, "dropout_bwd_cast dx")

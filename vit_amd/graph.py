@@ -13,6 +13,9 @@ Stochastic depth (`model.drop_path_rate`) needs no mechanism of its own: the fro
 the per-sample gate is drawn from the record's keys like every dropout mask, so each replay draws a fresh one.
 Patch dropout (`model.patch_drop_rate`) needs nothing new either: the kept count K is frozen in the launches' shapes, and the
 subset each sample keeps is drawn by vit_patch_select from the record's keys, so each replay selects afresh.
+Masked spectrum modelling (`model.task_type: mim`) rides on the same selection: each replay draws a fresh block mask, and the
+loss's denominator -- the number of masked windows, which varies with the mask -- is counted on the device, so nothing on the
+host changes from replay to replay.
 
 Scope: one process, one GPU (the RCCL exchange of N > 1 is not captured), a fused optimizer (vit_amd/optimizer.py:
 FusedAdamW, FusedLamb, FusedSGD), no trainable input preprocessor, a fixed batch shape.  The reference's step semantics are unchanged

@@ -61,10 +61,12 @@ _CLS_ALIASES = frozenset({"classification", "cls", "class"})
 
 
 def _normalize_task(config) -> str:
-    """'cls' or 'reg' from model.task_type (legacy key model.task; default 'cls'): vit.py:20-27."""
+    """'cls' or 'reg' from model.task_type (legacy key model.task; default 'cls'): vit.py:20-27 -- or this build's 'mim'."""
     model_cfg = config.get("model") or {}
-    raw = model_cfg.get("task_type") or model_cfg.get("task") or "cls"
-    return "cls" if str(raw).lower() in _CLS_ALIASES else "reg"
+    raw = str(model_cfg.get("task_type") or model_cfg.get("task") or "cls").lower()
+    if raw == "mim":
+        return "mim"
+    return "cls" if raw in _CLS_ALIASES else "reg"
 
 
 class BaseLightningModule(_Base):
@@ -114,7 +116,14 @@ class ViTLModule(BaseLightningModule):
         self.mixer = mixup_from_config(config, num_classes=int(self.model.config.num_labels) if cls else None)
         if self.mixer is not None and cls:
             self.model.engine.set_soft_loss(self.mixer.soft_loss)
-        if self.task_type == "cls":
+        if self.task_type == "mim":
+            # masked spectrum modelling: the reconstruction loss is the one number there is (logged as `mim_loss` /
+            # `val_mim_loss`; monitored, mode min); Mixup / CutMix have no labels to mix
+            if self.mixer is not None:
+                raise ValueError("augment (Mixup / CutMix) and model.task_type 'mim' exclude each other")
+            self.monitor_metric = "mim_loss"
+            self._metrics = {}
+        elif self.task_type == "cls":
             self.accuracy = Accuracy()
             self.monitor_metric = "acc"
             self._metrics = {"acc": self.accuracy}
@@ -173,6 +182,8 @@ class ViTLModule(BaseLightningModule):
         x, labels = self._eval_inputs(batch)
         outputs = self.forward(x, labels, loss_only=False)
         self.log(f"{prefix}_{self.loss_name}_loss", outputs.loss, on_step=False, on_epoch=True)
+        if self.task_type == "mim":
+            return outputs.loss
         scored = outputs.logits if self.task_type == "cls" else outputs.logits.squeeze()
         for name, metric in self._metrics.items():
             self.log(f"{prefix}_{name}", metric(scored, labels), on_step=False, on_epoch=True, prog_bar=(name == "acc"))

@@ -646,7 +646,7 @@ def _scheduler_kwargs(fam: str, cfg: dict, lr: float) -> dict:
     return kw
 
 
-_NO_DECAY_NAMES = ("vit.embeddings.cls_token", "vit.embeddings.position_embeddings")
+_NO_DECAY_NAMES = ("vit.embeddings.cls_token", "vit.embeddings.position_embeddings", "vit.embeddings.mask_token")  # mask_token: 'mim' models
 _LAYER = re.compile(r"(?:^|\.)encoder\.layer\.(\d+)\.")
 
 

@@ -44,10 +44,22 @@ class SequenceClassifierOutput:
         return [f.name for f in fields(self) if getattr(self, f.name) is not None]
 
 
+@dataclass
+class MaskedModelingOutput(SequenceClassifierOutput):
+    """What a 'mim' model returns: HF MaskedImageModelingOutput's `loss` / `reconstruction` [B, N, P] / `hidden_states` /
+    `attentions`, plus the `mask` [B, N] (int32, non-zero = masked) the forward used.  `logits` is the reconstruction too, so
+    code written against the other tasks' output keeps reading a prediction.  `reconstruction` and `mask` are views of the
+    engine's activation arena: the next forward of the same mode overwrites them (clone what has to outlive it)."""
+
+    reconstruction: Optional[torch.Tensor] = None
+    mask: Optional[torch.Tensor] = None
+
+
 def build_model_name(config, model_prefix: str = "ViT", full_config: dict = None) -> str:
-    """Run name `{prefix}_p{patch}_h{hidden}_l{layers}_a{heads}_s{stride}_p{proj_fn}[_nz{noise digits}]` -- the rule of
+    """Run name `{prefix}_p{patch}_h{hidden}_l{layers}_a{heads}_s{stride}_p{proj_fn}[_nz{noise digits}][_mim]` -- the rule of
     src/models/model_utils.py:9-45 (pinned by tests/golden/names.json).  The stride tag is the explicit `stride_size` when
-    one is set (truthy), else the `stride_ratio`; a positive noise level is appended with its decimal point removed."""
+    one is set (truthy), else the `stride_ratio`; a positive noise level is appended with its decimal point removed; a masked
+    spectrum model (task_type 'mim', this build's) appends `_mim`."""
     explicit = getattr(config, "stride_size", None)
     fields = [
         ("p", config.patch_size), ("h", config.hidden_size), ("l", config.num_hidden_layers),
@@ -57,6 +69,8 @@ def build_model_name(config, model_prefix: str = "ViT", full_config: dict = None
     level = ((full_config or {}).get("noise") or {}).get("noise_level", 0)
     if level and level > 0:
         name += "_nz" + str(level).replace(".", "")
+    if getattr(config, "task_type", None) == "mim":
+        name += "_mim"
     return name
 
 
@@ -121,7 +135,7 @@ class MyViT(nn.Module):
         super().__init__()
         self.config = config
         self.task_type = config.task_type
-        if self.task_type not in ("cls", "reg"):
+        if self.task_type not in ("cls", "reg", "mim"):
             raise ValueError(f"Unsupported task_type '{self.task_type}'")  # specvit.py:55
         self.preprocessor = preprocessor  # specvit.py:43, 72-73: applied to pixel_values before the ViT
         self.engine = ViTEngine(config, loss_name=loss_name)
@@ -182,6 +196,8 @@ class MyViT(nn.Module):
         for name, p in zip(self._param_names, self._param_list):
             if name.endswith("cls_token") or name.endswith("position_embeddings"):
                 p.copy_(torch.randn(p.shape))
+            elif name.endswith("mask_token"):  # task_type 'mim': HF ViTEmbeddings starts it at zero
+                p.zero_()
             elif name.endswith(".lambda1"):  # LayerScale (config.layer_scale_init): present only when the feature is on
                 p.fill_(float(self.config.layer_scale_init))
             elif "layernorm" in name:
@@ -200,18 +216,48 @@ class MyViT(nn.Module):
     def loss_name(self):
         return self._loss_name
 
-    def forward(self, pixel_values, labels=None, output_attentions=None, output_hidden_states=None, return_dict=None):
+    def train(self, mode: bool = True):
+        """eval() (= train(False)) also restarts a 'mim' model's evaluation-mask counter (see forward)."""
+        if not mode:
+            self.engine.reset_mim_eval()
+        return super().train(mode)
+
+    def forward(self, pixel_values, labels=None, output_attentions=None, output_hidden_states=None, return_dict=None,
+                bool_masked_pos=None):
+        """A 'mim' model (masked spectrum modelling) ignores `labels` and returns a MaskedModelingOutput: `.loss`, the
+        reconstruction loss over the masked windows; `.reconstruction` [B, N, P]; `.mask` [B, N]; `.hidden_states`;
+        `.attentions`.  `bool_masked_pos` (HF's name): a bool / integer [B, N] device tensor, non-zero = masked, used as given.
+        None draws the mask on the device: in training mode from the step's seed (a fresh mask per step); in eval mode from
+            seed_k = ((base_seed ^ 0x6D696D5F6576616C) + 0x9E3779B97F4A7C15 * (k + 1)) mod 2^64,
+        k = the number of mask-drawing eval forwards since the last eval() / train(False) call -- a function of the engine's
+        base_seed and that counter alone, never of the batch contents, so every validation epoch that starts with eval() sees
+        the same masks in the same order.  The other tasks take no `bool_masked_pos`."""
         eng = self.engine
         training = self.training
         if self.preprocessor is not None:
             pixel_values = self.preprocessor(pixel_values)
+        mim = self.task_type == "mim"
+        if bool_masked_pos is not None and not mim:
+            raise ValueError("bool_masked_pos belongs to masked spectrum modelling (model.task_type 'mim')")
+        if mim:
+            labels = None
+            held, eng.mim_mask = eng.mim_mask, bool_masked_pos if bool_masked_pos is not None else eng.mim_mask
+            try:
+                return self._forward(pixel_values, labels, training, output_attentions, output_hidden_states, return_dict)
+            finally:
+                eng.mim_mask = held
+        return self._forward(pixel_values, labels, training, output_attentions, output_hidden_states, return_dict)
+
+    def _forward(self, pixel_values, labels, training, output_attentions, output_hidden_states, return_dict):
+        eng = self.engine
+        mim = self.task_type == "mim"
         # forward hooks on `vit.encoder.layer.N.attention.attention` (what the reference's viz callback registers to read
         # attention maps, src/viz/viz_callback.py:183-214, 231-235): the kernels have no per-layer Python forward to hook,
         # so when such hooks exist the maps are produced anyway and the hooks are called with HF's (context, probs) output
         hooked = self._hooked_attention_layers()
         if hooked:
             output_attentions_user, output_attentions = output_attentions, True
-        want_grad = torch.is_grad_enabled() and labels is not None and any(p.requires_grad for p in self._param_list)
+        want_grad = torch.is_grad_enabled() and (labels is not None or mim) and any(p.requires_grad for p in self._param_list)
         ctxs = [] if hooked else None
         if want_grad:
             # the loss stays differentiable whatever else is asked for (as in the reference); hidden states / attention maps
@@ -236,9 +282,12 @@ class MyViT(nn.Module):
                     hook(node, (), (ctxs[i].detach(), atts[i]))
             if not output_attentions_user:
                 atts = None
-        out = SequenceClassifierOutput(loss=loss, logits=logits,
-                                       hidden_states=tuple(hs) if hs is not None else None,
-                                       attentions=tuple(atts) if atts is not None else None)
+        hs, atts = tuple(hs) if hs is not None else None, tuple(atts) if atts is not None else None
+        if mim:
+            out = MaskedModelingOutput(loss=loss, logits=logits, hidden_states=hs, attentions=atts, reconstruction=logits,
+                                       mask=eng._last["mask"])
+        else:
+            out = SequenceClassifierOutput(loss=loss, logits=logits, hidden_states=hs, attentions=atts)
         if return_dict is False:
             return out.to_tuple()
         return out
