@@ -391,5 +391,8 @@ int vit_adamw_step(vit_handle h, float* p, const float* g, float* m, float* v, v
  * its backward, and the reconstruction loss that reads its target from the signal.  Declared in their own header, part of
  * this ABI. */
 #include "vit_amd_mim.h"
+/* Global average pooling (`model.global_pool: avg`): the mean of the patch rows of the final LayerNorm's output, which the
+ * head then reads in place of the CLS row, and its backward.  Declared in their own header, part of this ABI. */
+#include "vit_amd_pool.h"
 
 #endif /* VIT_AMD_H_ */

@@ -52,9 +52,19 @@ class ViTConfig:
     mim_span: int = 1
     mim_loss: str = "l1"
     mim_norm_target: bool = False
+    # what the head reads of the final LayerNorm's output (timm's name; this build's key): 'token' = the CLS row, the
+    # reference's model; 'avg' = the mean of the patch rows, CLS excluded (timm's global_pool='avg', fc_norm=False) -- how
+    # SimMIM / MAE / BEiT fine-tune, since a masked objective never trains the CLS token.  No parameter is added or renamed.
+    global_pool: str = "token"
     use_return_dict: bool = True
 
     def __post_init__(self):
+        pool = self.global_pool
+        if not isinstance(pool, str) or pool not in ("token", "avg"):
+            raise ValueError(f"model.global_pool must be 'token' or 'avg' (got {pool!r})")
+        if pool == "avg" and self.task_type == "mim":
+            raise ValueError("model.global_pool 'avg' and model.task_type 'mim' exclude each other: a masked model decodes "
+                             "every token and has no pooled head")
         rate = self.patch_drop_rate
         if isinstance(rate, bool) or not isinstance(rate, (int, float)) or not 0.0 <= float(rate) < 1.0:
             raise ValueError(f"patch_drop_rate must lie in [0, 1) (got {rate!r})")
@@ -147,7 +157,7 @@ def get_vit_config(config) -> ViTConfig:
     else:
         num_labels = int(model.get("num_labels", 1) or 1)
     optional = {k: model[k] for k in ("stride_ratio", "stride_size", "pos_encoding_type", "max_position_embeddings", "rope_base",
-                                      "drop_path_rate", "layer_scale_init", "patch_drop_rate") if k in model}
+                                      "drop_path_rate", "layer_scale_init", "patch_drop_rate", "global_pool") if k in model}
     if task == "mim":
         # the `mim:` section: {mask_ratio, span, loss, norm_target}; anything else in it is a spelling mistake
         section = dict(config.get("mim") or {})

@@ -24,6 +24,9 @@ Data layout in HBM (one MI355X, 288 GB: nothing is recomputed or re-materialised
            selection it is expanded from (mim_keep [B, Kb], mim_slot [B, Nb]), the decoder's output mim_pred f32 [M, P], in bf16
            mode the operand copy mim_last bf16 [M, D] of `last`, and for training mim_dpred [M, P] (operand dtype).  `last` then
            has the GEMMs' zeroed pad rows, the CLS tail is off, and the head is the Linear `decoder` [P, D].
+  Global average pooling (cfg.global_pool 'avg'): the CLS tail is off; c_last [B, 1, D] holds the mean of the patch rows of
+           `last` (vit_token_pool_fwd) and is what the head reads; c_dlast [B, 1, D] takes the head's gradient, which
+           vit_token_pool_bwd spreads over every row of dlast.  No other buffer, no parameter, no workspace.
 Dropout masks are regenerated from (seed, site) in backward; no mask is stored.
 
 A layer's tail -- out-projection, LN-after, FC1 + GELU, FC2 behind its attention -- is stated once per direction
@@ -247,6 +250,9 @@ class ViTEngine:
         self.mim = cfg.task_type == "mim"
         if self.mim:
             self.loss_kind = LOSS_L1 if cfg.mim_loss == "l1" else LOSS_MSE
+        # global average pooling (cfg.global_pool 'avg'): the head reads the mean of the patch rows of the
+        # final LayerNorm's output (c_last) instead of its CLS row, so the last layer runs over every row: no CLS tail
+        self.set_global_pool(getattr(cfg, "global_pool", "token"))
         # an optional [B, N] device tensor (bool or integer, non-zero = masked) that replaces the drawn mask of the next
         # forwards, like patch_keep does for patch dropout.  None: draw.
         self.mim_mask: Optional[torch.Tensor] = None
@@ -302,6 +308,18 @@ class ViTEngine:
         # the base's), so "were the f32 weights modified since the bf16 shadow was made?" is answered by a signature
         # over the parameters' versions, supplied by the owning module.
         self.version_fn: Callable[[], int] = lambda: self.flat._version
+
+    def set_global_pool(self, mode: str) -> str:
+        """`model.global_pool`: 'token' | 'avg'.  Read by every forward; no buffer and no parameter depends on it."""
+        if not isinstance(mode, str) or mode not in ("token", "avg") or (mode == "avg" and self.cfg.task_type == "mim"):
+            raise ValueError(f"global_pool must be 'token' or 'avg', and 'avg' needs a pooled head (got {mode!r}, task_type "
+                             f"{self.cfg.task_type!r})")
+        self.cfg.global_pool = mode
+        return mode
+
+    @property
+    def avg_pool(self) -> bool:
+        return getattr(self.cfg, "global_pool", "token") == "avg"
 
     def set_soft_loss(self, name: str) -> int:
         """`augment.soft_loss`: 'ce' (torch's cross-entropy with probability targets) | 'bce' (binary cross-entropy with logits,
@@ -766,7 +784,8 @@ class ViTEngine:
                 rope = (vf.rows_gather(rope[0], keep, out=a["rope_cos"]), vf.rows_gather(rope[1], keep, out=a["rope_sin"]))
 
         atts = [] if output_attentions else None
-        tail = bool(self.cls_tail) and L > 0 and not output_hidden_states and not self.mim  # the decoder reads every row
+        # the decoder ('mim') and the average pool read every row
+        tail = bool(self.cls_tail) and L > 0 and not output_hidden_states and not self.mim and not self.avg_pool
         r = full
         if L == 0:
             self._ln(full.xL, "vit.layernorm", full.last2, full.meanF, full.rstdF)
@@ -804,7 +823,8 @@ class ViTEngine:
             loss, count = vf.mim_loss_fwd(x, pred, mask, P, S, kind, c.mim_norm_target)
             recon = pred.view(B, T, P)[:, 1:, :]
             self._last = dict(B=B, seed=seed, ph=ph, pa=pa, pd=pd, labels=None, logits=recon, gen=self._gen, grad=need_grad,
-                              tail=False, kind=kind, T=T, keep=None, mim=True, mask=mask, count=count, x=x, pred=pred)
+                              tail=False, kind=kind, T=T, keep=None, mim=True, mask=mask, count=count, x=x, pred=pred,
+                              pool="token")
             hs = [t.clone() for t in a["x"]] if output_hidden_states else None
             return loss, recon, hs, atts
         if labels is not None:
@@ -815,9 +835,14 @@ class ViTEngine:
             n_expected = B if kind == LOSS_CE else B * c.num_labels
             if labels.numel() != n_expected:
                 raise ValueError(f"labels has {labels.numel()} elements, expected {n_expected}")
-        logits, loss = vf.head_loss_fwd(r.last, self.p(hn + ".weight"), self.p(hn + ".bias"), labels, kind)
+        pooled = r.last
+        if self.avg_pool:  # the mean of this forward's patch rows (under patch dropout: of the K kept ones), read as [B, 1, D]
+            pooled = a["c_last"]
+            vf.token_pool_fwd(full.last, 1, out=pooled)
+        logits, loss = vf.head_loss_fwd(pooled, self.p(hn + ".weight"), self.p(hn + ".bias"), labels, kind)
         self._last = dict(B=B, seed=seed, ph=ph, pa=pa, pd=pd, labels=labels, logits=logits, gen=self._gen, grad=need_grad,
-                          tail=tail, kind=kind, T=T, keep=a["keep"] if K is not None else None, mim=False)
+                          tail=tail, kind=kind, T=T, keep=a["keep"] if K is not None else None, mim=False,
+                          pool="avg" if self.avg_pool else "token")
         hs = [t.clone() for t in a["x"]] if output_hidden_states else None
         return loss, logits, hs, atts
 
@@ -1068,6 +1093,12 @@ class ViTEngine:
             vf.gemm(dpred, self.W(hn), M=M, N=D, K=P, b_trans=True, out=full.dlast.view(M, D))
             self._dw(full, dpred, a["mim_last"], self.dW(hn))
             vf.colsum(dpred, out=self.db(hn), accumulate=self._accum)
+        elif st["pool"] == "avg":
+            # the head's backward over the pooled rows, then every patch row of dlast takes its sample's share (CLS rows: zeros)
+            vf.head_loss_bwd(a["c_last"], self.p(hn + ".weight"), st["logits"], st["labels"], dloss, st["kind"],
+                             dlast=t["c_dlast"], dW=self.dW(hn), db=self.db(hn))
+            vf.token_pool_bwd(t["c_dlast"], full.dlast, 1)
+            self._setup_side()
         else:
             vf.head_loss_bwd(r.last, self.p(hn + ".weight"), st["logits"], st["labels"], dloss, st["kind"], dlast=r.dlast,
                              dW=self.dW(hn), db=self.db(hn))

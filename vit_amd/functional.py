@@ -584,6 +584,35 @@ def mim_loss_bwd(x, pred, mask, count, dloss, P: int, S: int, kind: int, norm_ta
     return dpred
 
 
+# ------------------------------------------------------------------------------------------------ global average pooling
+def _chk_pool(x, pooled, first: int, who: str):
+    _chk(x, torch.float32, who + " x")
+    _chk(pooled, torch.float32, who + " pooled")
+    if x.dim() != 3 or not x.is_cuda or not pooled.is_cuda:
+        raise _cabi.VitError(f"{who}: x must be an f32 [B, T, D] device tensor, got {tuple(x.shape)} on {x.device}")
+    B, T, D = x.shape
+    if pooled.numel() != B * D:
+        raise _cabi.VitError(f"{who}: pooled must hold [B={B}, D={D}], got {tuple(pooled.shape)}")
+    return B, T, D, int(first)
+
+
+def token_pool_fwd(x, first: int = 1, out=None):
+    """out f32 [B, D] <- the mean of rows first .. T-1 of x f32 [B, T, D], in the fixed order of include/vit_amd_pool.h
+    (vit_token_pool_fwd)."""
+    out = out if out is not None else torch.empty((x.shape[0], x.shape[2]), dtype=torch.float32, device=x.device)
+    B, T, D, first = _chk_pool(x, out, first, "token_pool_fwd")
+    _h(x).call("vit_token_pool_fwd", x.data_ptr(), out.data_ptr(), B, T, D, first, _stream(x))
+    return out
+
+
+def token_pool_bwd(dpooled, dx, first: int = 1):
+    """dx f32 [B, T, D] <- dpooled [B, D] / (T - first) in rows first .. T-1, exact zeros in front: every element is written
+    (vit_token_pool_bwd)."""
+    B, T, D, first = _chk_pool(dx, dpooled, first, "token_pool_bwd")
+    _h(dx).call("vit_token_pool_bwd", dpooled.data_ptr(), dx.data_ptr(), B, T, D, first, _stream(dx))
+    return dx
+
+
 # ------------------------------------------------------------------------------------------------ elementwise
 def dropout_bwd_cast(dx, dropout: Dropout = NO_DROP, out=None, out_dtype=torch.bfloat16):
     _chk(dx, torch.float32, "dropout_bwd_cast dx")

@@ -16,6 +16,7 @@ subset each sample keeps is drawn by vit_patch_select from the record's keys, so
 Masked spectrum modelling (`model.task_type: mim`) rides on the same selection: each replay draws a fresh block mask, and the
 loss's denominator -- the number of masked windows, which varies with the mask -- is counted on the device, so nothing on the
 host changes from replay to replay.
+Global average pooling (`model.global_pool: avg`) adds two nodes, vit_token_pool_fwd / _bwd, whose arguments are shapes alone.
 
 Scope: one process, one GPU (the RCCL exchange of N > 1 is not captured), a fused optimizer (vit_amd/optimizer.py:
 FusedAdamW, FusedLamb, FusedSGD), no trainable input preprocessor, a fixed batch shape.  The reference's step semantics are unchanged

@@ -56,10 +56,11 @@ class MaskedModelingOutput(SequenceClassifierOutput):
 
 
 def build_model_name(config, model_prefix: str = "ViT", full_config: dict = None) -> str:
-    """Run name `{prefix}_p{patch}_h{hidden}_l{layers}_a{heads}_s{stride}_p{proj_fn}[_nz{noise digits}][_mim]` -- the rule of
+    """Run name `{prefix}_p{patch}_h{hidden}_l{layers}_a{heads}_s{stride}_p{proj_fn}[_nz{noise digits}][_mim][_gap]` -- the rule of
     src/models/model_utils.py:9-45 (pinned by tests/golden/names.json).  The stride tag is the explicit `stride_size` when
     one is set (truthy), else the `stride_ratio`; a positive noise level is appended with its decimal point removed; a masked
-    spectrum model (task_type 'mim', this build's) appends `_mim`."""
+    spectrum model (task_type 'mim', this build's) appends `_mim`, a model whose head reads the mean of the patch tokens
+    (global_pool 'avg', this build's) `_gap` -- two runs that differ in pooling alone do not share a checkpoint directory."""
     explicit = getattr(config, "stride_size", None)
     fields = [
         ("p", config.patch_size), ("h", config.hidden_size), ("l", config.num_hidden_layers),
@@ -71,6 +72,8 @@ def build_model_name(config, model_prefix: str = "ViT", full_config: dict = None
         name += "_nz" + str(level).replace(".", "")
     if getattr(config, "task_type", None) == "mim":
         name += "_mim"
+    if getattr(config, "global_pool", "token") == "avg":
+        name += "_gap"
     return name
 
 
@@ -141,6 +144,7 @@ class MyViT(nn.Module):
         self.engine = ViTEngine(config, loss_name=loss_name)
         self._kept_hidden = None
         self._loss_name = self.engine.loss_name
+        self._name_args = (model_name, full_config)
         self._model_name = build_model_name(config, model_name, full_config=full_config)
         self._build_tree()
         self.init_weights()
@@ -215,6 +219,12 @@ class MyViT(nn.Module):
     @property
     def loss_name(self):
         return self._loss_name
+
+    def set_global_pool(self, mode: str):
+        """Switch what the head reads, 'token' (the CLS row) or 'avg' (the mean of the patch rows): no tensor changes its name
+        or shape, so this is all it takes to evaluate a checkpoint under the pooling it was trained with.  The run name follows."""
+        self.engine.set_global_pool(mode)
+        self._model_name = build_model_name(self.config, self._name_args[0], full_config=self._name_args[1])
 
     def train(self, mode: bool = True):
         """eval() (= train(False)) also restarts a 'mim' model's evaluation-mask counter (see forward)."""

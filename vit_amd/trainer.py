@@ -166,6 +166,15 @@ def model_state_from_checkpoint(ckpt: Dict[str, Any]) -> Dict[str, torch.Tensor]
     return {(k[len("model."):] if k.startswith("model.") else k): v for k, v in sd.items()}
 
 
+def saved_global_pool(ckpt: Dict[str, Any]) -> Optional[str]:
+    """`model.global_pool` of the run that wrote `ckpt` ('token' when its config has no such key), or None for a file without
+    a stored config (a bare state_dict)."""
+    cfg = (ckpt.get("hyper_parameters") or {}).get("config")
+    if not isinstance(cfg, dict) or not isinstance(cfg.get("model"), dict):
+        return None
+    return str(cfg["model"].get("global_pool") or "token")
+
+
 class FreezeSchedule:
     """When the input preprocessor is trainable (reference: PreprocessorFreezeCallback, src/prepca/callbacks.py; pinned on
     it by tests/golden/freeze.json): `freeze_epochs` > 0 = frozen at the start of training and released once, at the first
@@ -539,7 +548,14 @@ class Trainer:
         """Evaluation only (scripts/test.py:26-48): no optimizer is built, no parameter changes."""
         if ckpt_path not in (None, "", "none", "None"):
             path = self.checkpointer.resolve(ckpt_path) if self.checkpointer else ckpt_path
-            module.model.load_state_dict(model_state_from_checkpoint(load_checkpoint_file(path)))
+            ckpt = load_checkpoint_file(path)
+            module.model.load_state_dict(model_state_from_checkpoint(ckpt))
+            # the pooling mode changes no tensor's name or shape, so the state_dict cannot tell: the checkpoint's own config does
+            pool = saved_global_pool(ckpt)
+            if pool is not None and pool != getattr(module.model.config, "global_pool", "token"):
+                print(f"[test] the checkpoint was trained with model.global_pool '{pool}': evaluating with it "
+                      f"(the config says '{module.model.config.global_pool}')")
+                module.model.set_global_pool(pool)
         self._setup(module, for_training=False)
         return self.validate(module, loader, "test")
 
@@ -574,6 +590,10 @@ class Trainer:
 
     def _resume(self, module, ckpt_path: str) -> int:
         ckpt = load_checkpoint_file(ckpt_path)
+        pool = saved_global_pool(ckpt)
+        if pool is not None and pool != getattr(module.model.config, "global_pool", "token"):
+            raise ValueError(f"--ckpt resumes a run trained with model.global_pool '{pool}', the config says "
+                             f"'{module.model.config.global_pool}': the two models share every tensor but not their arithmetic")
         saved_ema = (ckpt.get("vit_amd") or {}).get("ema")
         if self.averager is not None and saved_ema:
             # `state_dict` holds the averaged weights, `train_state` the raw ones: both sequences continue exactly
