@@ -394,5 +394,8 @@ int vit_adamw_step(vit_handle h, float* p, const float* g, float* m, float* v, v
 /* Global average pooling (`model.global_pool: avg`): the mean of the patch rows of the final LayerNorm's output, which the
  * head then reads in place of the CLS row, and its backward.  Declared in their own header, part of this ABI. */
 #include "vit_amd_pool.h"
+/* Sharpness-aware minimisation (`train.sam_rho`): the norm of the first gradient, the ascent that perturbs the flat parameter
+ * buffer and keeps a backup, and the descent that restores it.  Declared in their own header, part of this ABI. */
+#include "vit_amd_sam.h"
 
 #endif /* VIT_AMD_H_ */

@@ -171,6 +171,11 @@ _PROTOS = {
     # global average pooling (include/vit_amd_pool.h): (h, x, pooled, B, T, D, first, stream) / (h, dpooled, dx, B, T, D, first, stream)
     "vit_token_pool_fwd": [_P, _P, _P, _I, _I, _I, _I, _P],
     "vit_token_pool_bwd": [_P, _P, _P, _I, _I, _I, _I, _P],
+    # sharpness-aware minimisation (include/vit_amd_sam.h): (h, p, g, n, adaptive, accumulate, out, stream) /
+    # (h, p, g, backup, p_bf16, n, rho, adaptive, sqnorm_dev, stream) / (h, p, backup, p_bf16, n, stream)
+    "vit_sam_sqnorm": [_P, _P, _P, _I64, _I, _I, _P, _P],
+    "vit_sam_ascend": [_P, _P, _P, _P, _P, _I64, _F, _I, _P, _P],
+    "vit_sam_descend": [_P, _P, _P, _P, _I64, _P],
 }
 _RESTYPES = {"vit_last_error": C.c_char_p, "vit_last_gemm_kernel": C.c_char_p, "vit_workspace_needed": C.c_size_t}
 
@@ -179,7 +184,7 @@ _lock = threading.Lock()
 
 
 def declared_symbols(header_path: str = HEADER_PATH):
-    """Every function the C header declares, the headers it includes from its own directory (vit_amd_cov.h, vit_amd_optim.h, vit_amd_ema.h, vit_amd_droppath.h, vit_amd_layerscale.h, vit_amd_mix.h, vit_amd_patchdrop.h, vit_amd_mim.h, vit_amd_pool.h) included (used by
+    """Every function the C header declares, the headers it includes from its own directory (vit_amd_cov.h, vit_amd_optim.h, vit_amd_ema.h, vit_amd_droppath.h, vit_amd_layerscale.h, vit_amd_mix.h, vit_amd_patchdrop.h, vit_amd_mim.h, vit_amd_pool.h, vit_amd_sam.h) included (used by
     the CPU test that checks the library exports them all)."""
     seen, names, todo = set(), set(), [os.path.abspath(header_path)]
     while todo:

@@ -320,6 +320,10 @@ int ctx_lamb_passes(vit_handle h);
 // bytes, have M", and the caller returns VIT_ERR_WORKSPACE.  An entry point claims its WHOLE need (the maximum over its stages,
 // which use the workspace one after another on one stream) before its first launch; a stage's own claim then cannot fail.
 void* ctx_claim(vit_handle h, size_t need_bytes, const char* who);
+// out[0] (+)= sum (a_i g_i)^2 with a_i = |p_i| (p != NULL) or 1: the deterministic two-stage reduction of vit_grad_sqnorm
+// (elementwise.hip), shared with vit_sam_sqnorm (sam.hip)
+int sqnorm_launch(const char* who, vit_handle h, const float* p, const float* g, int64_t n, float* out, int accumulate,
+                  vit_stream stream);
 // what colsum_strided / vit_colsum claim for a [rows, cols] tensor (elementwise.hip)
 size_t colsum_ws_bytes(int rows, int cols);
 static inline DropCfg make_drop_h(vit_handle h, float p, uint64_t seed, uint64_t site) {

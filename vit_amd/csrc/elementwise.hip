@@ -466,16 +466,25 @@ __global__ __launch_bounds__(256) void head_bwd_dlast_kernel(const float* __rest
 }
 
 // ------------------------------------------------------------------------------------------ grad norm
-__global__ __launch_bounds__(256) void sqnorm_stage1_kernel(const float* __restrict__ g, long n, float* __restrict__ part) {
+// SCALED (vit_sam_sqnorm's adaptive form, include/vit_amd_sam.h): the summand is (|p_i| g_i)^2; the plain form never reads p
+template <bool SCALED>
+__global__ __launch_bounds__(256) void sqnorm_stage1_kernel(const float* __restrict__ p, const float* __restrict__ g, long n,
+                                                            float* __restrict__ part) {
   __shared__ float red[4];
   const long nv = n >> 2;
   float a = 0.f;
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < nv; i += (long)gridDim.x * blockDim.x) {
-    const f32x4 v = *(const f32x4*)(g + 4 * i);
+    f32x4 v = *(const f32x4*)(g + 4 * i);
+    if (SCALED) {
+      const f32x4 w = *(const f32x4*)(p + 4 * i);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) v[k] *= fabsf(w[k]);
+    }
     a += (v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]);
   }
   if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
-    const float v = g[(nv << 2) + threadIdx.x];
+    float v = g[(nv << 2) + threadIdx.x];
+    if (SCALED) v *= fabsf(p[(nv << 2) + threadIdx.x]);
     a += v * v;
   }
   a = wave_sum(a);
@@ -808,23 +817,35 @@ int vit_head_loss_bwd(vit_handle h, const float* last_hidden, const float* W, co
   return VIT_OK;
 }
 
-static int grad_sqnorm_impl(vit_handle h, const float* g, int64_t n, float* out, int accumulate, vit_stream stream) {
-  VIT_CHECK(g && out && n > 0, VIT_ERR_ARG, "vit_grad_sqnorm: bad arguments");
+}  // extern "C"
+
+namespace vit {
+// out[0] (+)= sum (a_i g_i)^2, a_i = |p_i| with p, 1 without: the two launches behind vit_grad_sqnorm, vit_grad_sqnorm_acc and
+// vit_sam_sqnorm (sam.hip), whose plain form therefore has their bits
+int sqnorm_launch(const char* who, vit_handle h, const float* p, const float* g, int64_t n, float* out, int accumulate,
+                  vit_stream stream) {
+  VIT_CHECK(g && out && n > 0, VIT_ERR_ARG, "%s: bad arguments", who);
   const int blocks = grid_for(n / 4 + 1, 256, 1024);
-  float* part = (float*)ctx_claim(h, (size_t)blocks * 4, "vit_grad_sqnorm");
+  float* part = (float*)ctx_claim(h, (size_t)blocks * 4, who);
   if (!part) return VIT_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(sqnorm_stage1_kernel, dim3(blocks), dim3(256), 0, st, g, (long)n, part);
+  if (p)
+    hipLaunchKernelGGL(sqnorm_stage1_kernel<true>, dim3(blocks), dim3(256), 0, st, p, g, (long)n, part);
+  else
+    hipLaunchKernelGGL(sqnorm_stage1_kernel<false>, dim3(blocks), dim3(256), 0, st, p, g, (long)n, part);
   VIT_LAUNCH_CHECK();
   hipLaunchKernelGGL(sqnorm_stage2_kernel, dim3(1), dim3(256), 0, st, part, blocks, out, accumulate);
   VIT_LAUNCH_CHECK();
   return VIT_OK;
 }
+}  // namespace vit
+
+extern "C" {
 int vit_grad_sqnorm(vit_handle h, const float* g, int64_t n, float* out, vit_stream stream) {
-  return grad_sqnorm_impl(h, g, n, out, 0, stream);
+  return sqnorm_launch("vit_grad_sqnorm", h, nullptr, g, n, out, 0, stream);
 }
 int vit_grad_sqnorm_acc(vit_handle h, const float* g, int64_t n, float* out, vit_stream stream) {
-  return grad_sqnorm_impl(h, g, n, out, 1, stream);
+  return sqnorm_launch("vit_grad_sqnorm", h, nullptr, g, n, out, 1, stream);
 }
 
 // ---- per-step state in device memory (hipGraph replays): one thread advances the step counter and derives from it the

@@ -258,6 +258,7 @@ class ViTEngine:
         self.mim_mask: Optional[torch.Tensor] = None
         # evaluation forwards draw their masks from a counter of their own (reset_mim_eval), not from the training step
         self.mim_eval_counter = 0
+        self._mim_eval_seed, self._reuse_mim_seed = 0, False  # forward(reuse_step=True) repeats the last evaluation-mode draw
         # a classification call whose labels are floating soft targets [B, num_labels] (Mixup / CutMix / label smoothing,
         # vit_amd/mix.py) runs this kind instead, forward and backward; int64 labels run loss_kind as ever (set_soft_loss)
         self.soft_loss_kind = LOSS_SOFT_CE
@@ -674,8 +675,11 @@ class ViTEngine:
         so every validation epoch sees the masks of the one before, whatever the batches hold."""
         if training:
             return step_seed
+        if self._reuse_mim_seed:  # forward(reuse_step=True): the previous evaluation-mode draw, the counter stays
+            return self._mim_eval_seed
         k, self.mim_eval_counter = self.mim_eval_counter, self.mim_eval_counter + 1
-        return ((self.base_seed ^ 0x6D696D5F6576616C) + 0x9E3779B97F4A7C15 * (k + 1)) & 0xFFFFFFFFFFFFFFFF
+        self._mim_eval_seed = ((self.base_seed ^ 0x6D696D5F6576616C) + 0x9E3779B97F4A7C15 * (k + 1)) & 0xFFFFFFFFFFFFFFFF
+        return self._mim_eval_seed
 
     def _mim_select(self, B: int, seed: int, training: bool) -> torch.Tensor:
         """This forward's patch mask, int32 [B, N] in the arena: the caller's (`mim_mask`), or drawn -- vit_patch_select keeps Kb
@@ -714,12 +718,16 @@ class ViTEngine:
         return (pd[i], self._site(i, 3), self._T if rows_per_sample is None else rows_per_sample, branch)
 
     def forward(self, x: torch.Tensor, labels: Optional[torch.Tensor], training: bool, need_grad: bool,
-                output_hidden_states: bool = False, output_attentions: bool = False, capture_ctx: Optional[list] = None):
+                output_hidden_states: bool = False, output_attentions: bool = False, capture_ctx: Optional[list] = None,
+                reuse_step: bool = False):
+        """`reuse_step` (the second pass of a sharpness-aware step, vit_amd/sam.py): this forward reads the step seed the
+        previous forward used and does not advance `step_counter`, so it draws that forward's dropout masks, drop-path gates,
+        patch-dropout selection and `mim` mask again -- the same function of the weights, evaluated at other weights."""
         self._ensure_device_state()
         with vf.use_handle(self.handle()):
-            return self._forward(x, labels, training, need_grad, output_hidden_states, output_attentions, capture_ctx)
+            return self._forward(x, labels, training, need_grad, output_hidden_states, output_attentions, capture_ctx, reuse_step)
 
-    def _forward(self, x, labels, training, need_grad, output_hidden_states, output_attentions, capture_ctx):
+    def _forward(self, x, labels, training, need_grad, output_hidden_states, output_attentions, capture_ctx, reuse_step=False):
         c = self.cfg
         if x.dim() != 2 or x.shape[1] != c.image_size:
             raise ValueError(f"pixel_values must be [batch, {c.image_size}], got {tuple(x.shape)}")
@@ -746,9 +754,15 @@ class ViTEngine:
         ph = c.hidden_dropout_prob if training else 0.0
         pa = c.attention_probs_dropout_prob if training else 0.0
         pd = self.path_rates(training)  # read on every forward, like the dropout probabilities
-        if training:
-            self.step_counter += 1
-        seed = (self.base_seed + 0x9E3779B97F4A7C15 * self.step_counter) & 0xFFFFFFFFFFFFFFFF
+        if reuse_step:
+            if self._last is None:
+                raise VitError("forward(reuse_step=True) without a preceding forward")
+            seed = self._last["seed"]
+        else:
+            if training:
+                self.step_counter += 1
+            seed = (self.base_seed + 0x9E3779B97F4A7C15 * self.step_counter) & 0xFFFFFFFFFFFFFFFF
+        self._reuse_mim_seed = reuse_step
         scale = dh ** -0.5
         full, cls = self._rows
         # --- embeddings: unfold -> projection (+bias) into token rows 1..N -> CLS / pos-emb / dropout

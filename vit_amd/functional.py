@@ -937,6 +937,51 @@ def ema_swap(p, ema, p_bf16=None, *, n: Optional[int] = None):
     _h(p).call("vit_ema_swap", p.data_ptr(), ema.data_ptr(), _ptr(p_bf16), n, _stream(p))
 
 
+# ------------------------------------------------------------------------------------------------ sharpness-aware minimisation
+def sam_sqnorm(g, p=None, *, adaptive: bool = False, accumulate: bool = False, out=None, n: Optional[int] = None):
+    """out[0] (+)= sum (a_i g_i)^2 over the first `n` elements, a_i = |p_i| if adaptive else 1 (include/vit_amd_sam.h); the plain
+    form does not read p and has grad_sqnorm's bits."""
+    _chk(g, torch.float32, "sam_sqnorm g")
+    n = g.numel() if n is None else n
+    if adaptive:
+        if p is None:
+            raise _cabi.VitError("sam_sqnorm: the adaptive form needs p")
+        _chk(p, torch.float32, "sam_sqnorm p")
+    if n > g.numel() or (adaptive and n > p.numel()):
+        raise _cabi.VitError(f"sam_sqnorm: n = {n} exceeds a buffer")
+    out = out if out is not None else torch.empty(1, dtype=torch.float32, device=g.device)
+    _chk(out, torch.float32, "sam_sqnorm out")
+    _h(g).call("vit_sam_sqnorm", _ptr(p) if adaptive else None, g.data_ptr(), n, int(bool(adaptive)), int(bool(accumulate)),
+               out.data_ptr(), _stream(g))
+    return out
+
+
+def sam_ascend(p, g, backup, p_bf16, rho: float, sqnorm, *, adaptive: bool = False, n: Optional[int] = None):
+    """backup <- p; p <- p + c * g * rho / (sqrt(sqnorm[0]) + 1e-12), c = p^2 if adaptive else 1, over the first `n` elements;
+    p_bf16 (optional) <- bf16 of the new p in the same pass.  `sqnorm` is a device scalar: nothing is synchronised."""
+    for t, name in ((p, "p"), (g, "g"), (backup, "backup"), (sqnorm, "sqnorm")):
+        _chk(t, torch.float32, f"sam_ascend {name}")
+    n = p.numel() if n is None else n
+    if n > min(p.numel(), g.numel(), backup.numel()) or (p_bf16 is not None and n > p_bf16.numel()) or sqnorm.numel() < 1:
+        raise _cabi.VitError(f"sam_ascend: n = {n} exceeds a buffer")
+    if p_bf16 is not None:
+        _chk(p_bf16, torch.bfloat16, "sam_ascend p_bf16")
+    _h(p).call("vit_sam_ascend", p.data_ptr(), g.data_ptr(), backup.data_ptr(), _ptr(p_bf16), n, float(rho), int(bool(adaptive)),
+               sqnorm.data_ptr(), _stream(p))
+
+
+def sam_descend(p, backup, p_bf16=None, *, n: Optional[int] = None):
+    """p <- backup over the first `n` elements, bit for bit; p_bf16 (optional) <- bf16 of it in the same pass."""
+    _chk(p, torch.float32, "sam_descend p")
+    _chk(backup, torch.float32, "sam_descend backup")
+    n = p.numel() if n is None else n
+    if n > min(p.numel(), backup.numel()) or (p_bf16 is not None and n > p_bf16.numel()):
+        raise _cabi.VitError(f"sam_descend: n = {n} exceeds a buffer")
+    if p_bf16 is not None:
+        _chk(p_bf16, torch.bfloat16, "sam_descend p_bf16")
+    _h(p).call("vit_sam_descend", p.data_ptr(), backup.data_ptr(), _ptr(p_bf16), n, _stream(p))
+
+
 # ------------------------------------------------------------------------------------------------ Mixup / CutMix
 MIX_ROW_BYTES = 32  # vit_mix_row (include/vit_amd_mix.h)
 

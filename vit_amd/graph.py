@@ -17,6 +17,11 @@ Masked spectrum modelling (`model.task_type: mim`) rides on the same selection: 
 loss's denominator -- the number of masked windows, which varies with the mask -- is counted on the device, so nothing on the
 host changes from replay to replay.
 Global average pooling (`model.global_pool: avg`) adds two nodes, vit_token_pool_fwd / _bwd, whose arguments are shapes alone.
+Sharpness-aware minimisation (`train.sam_rho`, vit_amd/sam.py) doubles the body between vit_step_advance and the clip: forward,
+backward, the norm of that gradient (vit_sam_sqnorm into a device cell), vit_sam_ascend over [0, n_trainable) -- the range the
+optimizer launch covers -- which reads the norm from the cell and keeps the weights in the backup buffer, LayerScale's fold again,
+the second forward and backward, vit_sam_descend.  vit_step_advance runs once, so both passes read the same keys from the bound
+record: a replay draws the same masks twice and fresh ones on the next replay.  The returned loss is the first pass's.
 
 Scope: one process, one GPU (the RCCL exchange of N > 1 is not captured), a fused optimizer (vit_amd/optimizer.py:
 FusedAdamW, FusedLamb, FusedSGD), no trainable input preprocessor, a fixed batch shape.  The reference's step semantics are unchanged
@@ -91,6 +96,9 @@ class GraphedTrainStep:
         if averager is not None:
             averager._ensure()  # the capture holds the addresses of its buffer and of its weight cell
             keep_ema = averager.clone_state()
+        self.sam = getattr(model, "sam", None)
+        if self.sam is not None:
+            self.sam._ensure()  # likewise: the backup buffer and the norm's cell
         # warm-up on a side stream (torch's capture protocol): sizes the arena / workspace, sets the kernels' LDS attributes
         # one stream inside the graph: two-branch graphs (the weight-gradient GEMMs on their second stream) replayed 0.7 ms per
         # step SLOWER than the same two streams launched eagerly on this stack.  The engine's own setting is put back after
@@ -112,12 +120,16 @@ class GraphedTrainStep:
             # the engine or the handle do later (another batch size, a grown workspace), the captured addresses stay valid and
             # are nobody else's.  (The engine also keeps evaluation forwards in their own arena: engine._ensure_arena.)
             self._held = (eng.act, eng.tmp, self.h._ws, eng._ls)  # _ls: LayerScale's folded operands, slabs and table
+            if self.sam is not None:
+                self._held += (self.sam.backup, self.sam._sq)
         finally:
             # also on a failed warm-up / capture: the warm-up steps were real optimisation steps and must not leak into the run
             _cabi.check(self.h.lib.vit_step_state_bind(self.h.h, None), "vit_step_state_bind")
             eng.overlap_dw = overlap_was
             torch.cuda.synchronize(dev)
             eng.flat.copy_(keep[0])
+            if self.sam is not None:
+                self.sam.perturbed = False  # a failure between the two passes: the weights are the kept ones again
             optimizer.restore_state(keep[1])  # in place: the graph holds the state buffers' addresses
             eng.step_counter = keep[2]
             if averager is not None:
@@ -148,6 +160,15 @@ class GraphedTrainStep:
         loss, _, _, _ = eng.forward(self.x, self.labels, training=True, need_grad=True)
         eng.backward(self.dloss)
         n = eng.layout.n_trainable
+        if self.sam is not None:
+            # the two-pass step, stated explicitly: perturb by the gradient just formed, evaluate the same function (same record,
+            # same keys) at the perturbed weights, restore; `loss` stays the first pass's
+            self.sam.ascend(runs=[(0, n)])
+            if eng.layer_scale:
+                eng.fold_layer_scale()  # from the perturbed weights; the next replay's first node folds from the stepped ones
+            eng.forward(self.x, self.labels, training=True, need_grad=True, reuse_step=True)
+            eng.backward(self.dloss)
+            self.sam.descend()
         sq = None
         if opt._clip is not None:
             sq = vf.grad_sqnorm(eng.grads[:n], out=opt._sq)

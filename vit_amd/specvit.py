@@ -93,11 +93,22 @@ class _ViTFunction(torch.autograd.Function):
     `loss.backward()` idiom) finds those views as the parameters' `.grad`.  Returning them again would make autograd run
     `p.grad += <the same memory>` after the kernels overwrote it -- twice the last micro-batch's gradient.  So when every
     trainable parameter still holds its view, the kernels ADD into the buffer (ViTEngine.backward(accumulate=True)) and
-    autograd gets None for them."""
+    autograd gets None for them.
+
+    With a `SharpnessAware` attached (MyViT.set_sam, vit_amd/sam.py) the backward is the whole two-pass step: the first
+    eng.backward (silent towards the gradient exchange), ascend, a second forward on the node's own input with the first one's
+    random draws, the second eng.backward with the same dloss (this one is exchanged), descend -- the last in a `finally`, so no
+    exception leaves perturbed weights behind.  The flat gradient buffer then holds the gradient at the perturbed weights."""
 
     @staticmethod
     def forward(ctx, model, x, labels, training, keep_hidden, *params):
         eng = model.engine
+        if model._sam is not None:
+            if x.requires_grad:
+                raise ValueError("sharpness-aware minimisation (set_sam / train.sam_rho) does not cover an input that requires "
+                                 "grad (a trainable input preprocessor)")
+            # what the second pass needs to be the same function at other weights: the input, and the caller's selections
+            ctx.sam_args = (x, labels, training, keep_hidden, eng.mim_mask, eng.patch_keep)
         # keep_hidden: the caller reads eng.act["x"] afterwards, so the engine has to know BEFORE it runs that the last
         # layer's token rows are wanted (otherwise it computes that layer's CLS rows only: ViTEngine.cls_tail)
         loss, logits, model._kept_hidden, _ = eng.forward(x, labels, training=training, need_grad=True,
@@ -105,6 +116,8 @@ class _ViTFunction(torch.autograd.Function):
         ctx.model = model
         ctx.gen = eng._gen
         ctx.need_dx = bool(x.requires_grad)  # a trainable input preprocessor in front of the ViT
+        if model._sam is not None and eng.mim:
+            logits = logits.clone()  # a view of the arena's mim_pred: the second pass overwrites it
         ctx.mark_non_differentiable(logits)
         return loss, logits
 
@@ -123,9 +136,37 @@ class _ViTFunction(torch.autograd.Function):
             raise VitError(f"backward: {bad}.grad is not the flat gradient buffer's view while other parameters still hold "
                            f"theirs from an earlier backward; gradients accumulate in place for all trainable parameters or "
                            f"for none -- call zero_grad() on the whole model (set_to_none=True or False), not on single parameters")
-        dx = eng.backward(dloss, need_dx=ctx.need_dx, gen=ctx.gen, accumulate=accumulate)
+        sam = model._sam
+        if sam is not None and hasattr(ctx, "sam_args"):
+            if accumulate:
+                raise VitError("backward: gradients would accumulate into an earlier backward's (no zero_grad in between) while "
+                               "sharpness-aware minimisation is attached; the two-pass step does not cover accumulation")
+            _ViTFunction._sam_backward(ctx, model, sam, dloss)
+            dx = None
+        else:
+            dx = eng.backward(dloss, need_dx=ctx.need_dx, gen=ctx.gen, accumulate=accumulate)
         grads = [eng.g(name) if ok and not accumulate else None for ok, name in zip(live, model._param_names)]
         return (None, dx, None, None, None, *grads)
+
+    @staticmethod
+    def _sam_backward(ctx, model, sam, dloss):
+        eng = model.engine
+        x, labels, training, keep_hidden, mim_mask, patch_keep = ctx.sam_args
+        cb, eng.grad_ready_cb = eng.grad_ready_cb, None  # the first gradient stays local: only the second one is exchanged
+        try:
+            eng.backward(dloss, gen=ctx.gen)
+        finally:
+            eng.grad_ready_cb = cb
+        held = (eng.mim_mask, eng.patch_keep)
+        try:
+            sam.ascend()
+            eng.mim_mask, eng.patch_keep = mim_mask, patch_keep
+            with torch.no_grad():
+                eng.forward(x, labels, training=training, need_grad=True, output_hidden_states=keep_hidden, reuse_step=True)
+            eng.backward(dloss)
+        finally:
+            eng.mim_mask, eng.patch_keep = held
+            sam.descend()
 
 
 class MyViT(nn.Module):
@@ -143,6 +184,7 @@ class MyViT(nn.Module):
         self.preprocessor = preprocessor  # specvit.py:43, 72-73: applied to pixel_values before the ViT
         self.engine = ViTEngine(config, loss_name=loss_name)
         self._kept_hidden = None
+        self._sam = None  # a SharpnessAware (set_sam): the autograd node's backward then runs the two-pass step
         self._loss_name = self.engine.loss_name
         self._name_args = (model_name, full_config)
         self._model_name = build_model_name(config, model_name, full_config=full_config)
@@ -226,6 +268,21 @@ class MyViT(nn.Module):
         self.engine.set_global_pool(mode)
         self._model_name = build_model_name(self.config, self._name_args[0], full_config=self._name_args[1])
 
+    def set_sam(self, rho, adaptive: bool = False):
+        """Attach sharpness-aware minimisation (vit_amd/sam.py): from now on every `loss.backward()` through this model leaves
+        the gradient at the perturbed weights w + e(w) in the flat gradient buffer and the weights restored.  `rho=None` detaches.
+        Returns the SharpnessAware (or None)."""
+        from .sam import SharpnessAware
+
+        if self._sam is not None and self._sam.perturbed:
+            raise RuntimeError("set_sam: the model holds perturbed weights")
+        self._sam = None if rho is None else SharpnessAware(self, rho, adaptive)
+        return self._sam
+
+    @property
+    def sam(self):
+        return self._sam
+
     def train(self, mode: bool = True):
         """eval() (= train(False)) also restarts a 'mim' model's evaluation-mask counter (see forward)."""
         if not mode:
@@ -294,8 +351,11 @@ class MyViT(nn.Module):
                 atts = None
         hs, atts = tuple(hs) if hs is not None else None, tuple(atts) if atts is not None else None
         if mim:
+            mask = eng._last["mask"]
+            if want_grad and self._sam is not None:
+                mask = mask.clone()  # the arena's: the second pass of a sharpness-aware backward writes it again
             out = MaskedModelingOutput(loss=loss, logits=logits, hidden_states=hs, attentions=atts, reconstruction=logits,
-                                       mask=eng._last["mask"])
+                                       mask=mask)
         else:
             out = SequenceClassifierOutput(loss=loss, logits=logits, hidden_states=hs, attentions=atts)
         if return_dict is False:

@@ -39,6 +39,7 @@ import torch
 
 from . import ddp as ddp_mod
 from .ema import WeightAverager, averaging_config
+from .sam import sam_config
 from .optimizer import FusedOptimizer
 
 __all__ = ["Trainer", "Checkpointer", "FreezeSchedule", "select_accelerator_and_devices", "get_training_strategy", "seed_everything"]
@@ -232,6 +233,11 @@ class Trainer:
         # steps, validated and checkpointed in place of the raw weights (vit_amd/ema.py); absent by default
         self.ema_cfg = averaging_config(config)
         self.averager: Optional[WeightAverager] = None
+        # train.sam_rho (+ sam_adaptive): sharpness-aware minimisation, the two-pass step (vit_amd/sam.py); absent by default
+        self.sam_cfg = sam_config(config)
+        if self.sam_cfg is not None and self.accumulate_grad_batches > 1:
+            raise ValueError("train.sam_rho and train.accumulate_grad_batches > 1 exclude each other: the two-pass step does not "
+                             "cover gradient accumulation")
         self.verbose = verbose and self.rank == 0
         self.logged: Dict[str, float] = {}
         self.metric_totals: Dict[str, float] = {}
@@ -301,6 +307,10 @@ class Trainer:
             own = {id(p) for p in module.model._param_list}
             extras = [p for grp in self.optimizer.param_groups for p in grp["params"] if id(p) not in own]
             self.averager = WeightAverager(module.model, extras=extras, **self.ema_cfg)
+        if self.sam_cfg is not None:
+            if module.model.preprocessor is not None and any(p.requires_grad for p in module.model.preprocessor.parameters()):
+                raise ValueError("train.sam_rho does not cover a trainable input preprocessor")
+            module.model.set_sam(**self.sam_cfg)
         # freeze schedule of the input preprocessor (src/prepca/callbacks.py): warmup.freeze_epochs > 0 freezes it for
         # that many epochs, -1 for good, 0 never.  (As in the reference, the optimizer was built from the parameters that
         # existed at configure time: a preprocessor unfrozen later becomes trainable for autograd but is only stepped if it
