@@ -397,5 +397,8 @@ int vit_adamw_step(vit_handle h, float* p, const float* g, float* m, float* v, v
 /* Sharpness-aware minimisation (`train.sam_rho`): the norm of the first gradient, the ascent that perturbs the flat parameter
  * buffer and keeps a backup, and the descent that restores it.  Declared in their own header, part of this ABI. */
 #include "vit_amd_sam.h"
+/* Register tokens (`model.num_register_tokens`): the embedding finish over [CLS, R registers, N patches] and its backward, for
+ * the plain and the masked model.  Declared in their own header, part of this ABI. */
+#include "vit_amd_registers.h"
 
 #endif /* VIT_AMD_H_ */

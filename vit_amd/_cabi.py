@@ -176,6 +176,10 @@ _PROTOS = {
     "vit_sam_sqnorm": [_P, _P, _P, _I64, _I, _I, _P, _P],
     "vit_sam_ascend": [_P, _P, _P, _P, _P, _I64, _F, _I, _P, _P],
     "vit_sam_descend": [_P, _P, _P, _P, _I64, _P],
+    # register tokens (include/vit_amd_registers.h): (h, tokens, cls, reg, pos, mask, mask_token, B, R, N, D, p, seed, site, stream) /
+    # (h, dtokens, mask, dpatch, dpatch_dtype, dcls, dreg, dpos, dmask_token, B, R, N, D, p, seed, site, accumulate, stream)
+    "vit_embed_finish_reg": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _U64, _U64, _P],
+    "vit_embed_finish_reg_bwd": [_P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _F, _U64, _U64, _I, _P],
 }
 _RESTYPES = {"vit_last_error": C.c_char_p, "vit_last_gemm_kernel": C.c_char_p, "vit_workspace_needed": C.c_size_t}
 
@@ -184,7 +188,7 @@ _lock = threading.Lock()
 
 
 def declared_symbols(header_path: str = HEADER_PATH):
-    """Every function the C header declares, the headers it includes from its own directory (vit_amd_cov.h, vit_amd_optim.h, vit_amd_ema.h, vit_amd_droppath.h, vit_amd_layerscale.h, vit_amd_mix.h, vit_amd_patchdrop.h, vit_amd_mim.h, vit_amd_pool.h, vit_amd_sam.h) included (used by
+    """Every function the C header declares, the headers it includes from its own directory (vit_amd_cov.h, vit_amd_optim.h, vit_amd_ema.h, vit_amd_droppath.h, vit_amd_layerscale.h, vit_amd_mix.h, vit_amd_patchdrop.h, vit_amd_mim.h, vit_amd_pool.h, vit_amd_sam.h, vit_amd_registers.h) included (used by
     the CPU test that checks the library exports them all)."""
     seen, names, todo = set(), set(), [os.path.abspath(header_path)]
     while todo:

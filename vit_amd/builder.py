@@ -88,7 +88,8 @@ def _build_preprocessor(preproc_type: str, warmup_cfg: dict, stats: dict, initia
 def init_from_state(model, state: Dict[str, torch.Tensor], verbose: bool = True):
     """The fine-tuning hand-over: copy into `model` every tensor of `state` (a network state_dict, e.g. a masked pre-training
     run's) whose name and shape match one of the model's, and leave the rest -- the other task's head (`decoder.*` /
-    `classifier.*` / `regressor.*`), `mask_token` -- alone.  Returns (loaded, skipped_in_checkpoint, skipped_in_model), three
+    `classifier.*` / `regressor.*`), `mask_token`, `register_tokens` of another count (or of a model without them: the
+    model's own keep their initial values) -- alone.  Returns (loaded, skipped_in_checkpoint, skipped_in_model), three
     sorted name lists, and prints the two skipped ones; raises ValueError when nothing matched."""
     own = model.state_dict()
     loaded = sorted(k for k, v in state.items() if k in own and tuple(own[k].shape) == tuple(v.shape))

@@ -56,6 +56,9 @@ class ViTConfig:
     # reference's model; 'avg' = the mean of the patch rows, CLS excluded (timm's global_pool='avg', fc_norm=False) -- how
     # SimMIM / MAE / BEiT fine-tune, since a masked objective never trains the CLS token.  No parameter is added or renamed.
     global_pool: str = "token"
+    # register tokens (HF Dinov2WithRegisters' name; this build's key): R learned tokens behind CLS that take no position
+    # information, that every layer attends to and every head ignores.  0 = the reference's model, parameter for parameter
+    num_register_tokens: int = 0
     use_return_dict: bool = True
 
     def __post_init__(self):
@@ -68,6 +71,12 @@ class ViTConfig:
         rate = self.patch_drop_rate
         if isinstance(rate, bool) or not isinstance(rate, (int, float)) or not 0.0 <= float(rate) < 1.0:
             raise ValueError(f"patch_drop_rate must lie in [0, 1) (got {rate!r})")
+        reg = self.num_register_tokens
+        if isinstance(reg, bool) or not isinstance(reg, int) or reg < 0:
+            raise ValueError(f"model.num_register_tokens must be an integer >= 0 (got {reg!r})")
+        if reg > 0 and float(rate) > 0.0:
+            raise ValueError(f"model.num_register_tokens ({reg}) together with model.patch_drop_rate ({rate}) is not built yet: "
+                             f"the gather forms of the embedding kernels take no register rows")
         if self.task_type == "mim":
             ratio, span = self.mim_mask_ratio, self.mim_span
             if isinstance(ratio, bool) or not isinstance(ratio, (int, float)) or not 0.0 < float(ratio) < 1.0:
@@ -102,7 +111,8 @@ class ViTConfig:
 
     @property
     def seq_len(self) -> int:
-        return self.num_patches + 1
+        """T = 1 + R + N: CLS, the register tokens, the patches."""
+        return self.num_patches + 1 + self.num_register_tokens
 
     @property
     def num_kept_patches(self) -> int:
@@ -157,7 +167,8 @@ def get_vit_config(config) -> ViTConfig:
     else:
         num_labels = int(model.get("num_labels", 1) or 1)
     optional = {k: model[k] for k in ("stride_ratio", "stride_size", "pos_encoding_type", "max_position_embeddings", "rope_base",
-                                      "drop_path_rate", "layer_scale_init", "patch_drop_rate", "global_pool") if k in model}
+                                      "drop_path_rate", "layer_scale_init", "patch_drop_rate", "global_pool", "num_register_tokens")
+                if k in model}
     if task == "mim":
         # the `mim:` section: {mask_ratio, span, loss, norm_target}; anything else in it is a spelling mistake
         section = dict(config.get("mim") or {})

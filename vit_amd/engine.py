@@ -24,6 +24,10 @@ Data layout in HBM (one MI355X, 288 GB: nothing is recomputed or re-materialised
            selection it is expanded from (mim_keep [B, Kb], mim_slot [B, Nb]), the decoder's output mim_pred f32 [M, P], in bf16
            mode the operand copy mim_last bf16 [M, D] of `last`, and for training mim_dpred [M, P] (operand dtype).  `last` then
            has the GEMMs' zeroed pad rows, the CLS tail is off, and the head is the Linear `decoder` [P, D].
+  Register tokens (cfg.num_register_tokens = R, off by default): T = 1 + R + N everywhere above; the projection writes the patch
+           rows 1 + R .., vit_embed_finish_reg fills CLS and the R register rows; the average pool and the 'mim' decoder start
+           at row 1 + R.  'mim': mim_last / mim_pred / mim_dpred are then compact [B * (N + 1), .] (rows R .. T-1 of each
+           sample: the row in front of the patches stands where the loss kernels expect a CLS row and is ignored by them).
   Global average pooling (cfg.global_pool 'avg'): the CLS tail is off; c_last [B, 1, D] holds the mean of the patch rows of
            `last` (vit_token_pool_fwd) and is what the head reads; c_dlast [B, 1, D] takes the head's gradient, which
            vit_token_pool_bwd spreads over every row of dlast.  No other buffer, no parameter, no workspace.
@@ -52,6 +56,7 @@ ALIGN = 8  # elements; keeps every view 32-byte (f32) / 16-byte (bf16) aligned
 EMBED = "vit.embeddings."
 PROJ = EMBED + "patch_embeddings.projection"
 MASK_TOKEN = EMBED + "mask_token"  # task_type 'mim' only (HF ViTForMaskedImageModeling's name)
+REGISTERS = EMBED + "register_tokens"  # cfg.num_register_tokens > 0 only (HF Dinov2WithRegisters' name), shape (1, R, D)
 # the name stems of one encoder layer's parameters (+ ".weight" / ".bias"): ViTEngine.names[i].fc1 etc.
 LayerNames = collections.namedtuple("LayerNames", "ln1 q wo ln2 fc1 fc2")
 _LAYER_STEMS = LayerNames("layernorm_before", "attention.attention.query", "attention.output.dense", "layernorm_after",
@@ -85,7 +90,9 @@ class ParamLayout:
     """name -> (offset, shape) inside the flat buffers; `state_order` is the reference's state_dict order."""
 
     def __init__(self, cfg: ViTConfig):
-        D, P, Fd, T = cfg.hidden_size, cfg.patch_size, cfg.intermediate_size, cfg.seq_len
+        D, P, Fd = cfg.hidden_size, cfg.patch_size, cfg.intermediate_size
+        R = int(getattr(cfg, "num_register_tokens", 0) or 0)
+        T = cfg.seq_len - R  # the rows of position_embeddings: CLS and the patches; a register takes no position
         self.entries: Dict[str, Tuple[int, Tuple[int, ...]]] = {}
         self._span: Dict[str, Tuple[int, int, Tuple[int, ...]]] = {}  # name -> (offset, offset + numel, shape): what view() needs
         self.layer_ranges: List[Tuple[int, int]] = []
@@ -101,6 +108,8 @@ class ParamLayout:
         e = "vit.embeddings."
         self.embed_start = off
         add(e + "cls_token", (1, 1, D))
+        if R > 0:  # directly behind cls_token, inside the embedding block: its bucket, its gradient exchange
+            add(e + "register_tokens", (1, R, D))
         if cfg.pos_encoding_type == "learned":
             add(e + "position_embeddings", (1, T, D))
         add(e + "patch_embeddings.projection.weight", (D, P) if cfg.proj_fn == "SW" else (D, 1, P))
@@ -144,6 +153,8 @@ class ParamLayout:
         self.n_total = off
         # the order MyViT's state_dict has in the reference (HF module registration order)
         order = [e + "cls_token"]
+        if R > 0:
+            order.append(e + "register_tokens")
         if cfg.pos_encoding_type == "learned":
             order.append(e + "position_embeddings")
         order += [e + "patch_embeddings.projection.weight", e + "patch_embeddings.projection.bias"]
@@ -243,7 +254,14 @@ class ViTEngine:
         ls = cfg.layer_scale_init
         if ls is not None and (isinstance(ls, bool) or not isinstance(ls, (int, float)) or not math.isfinite(ls) or not ls > 0):
             raise ValueError(f"layer_scale_init must be a finite number > 0, or None for no LayerScale (got {ls!r})")
+        reg = getattr(cfg, "num_register_tokens", 0)
+        if isinstance(reg, bool) or not isinstance(reg, int) or reg < 0:
+            raise ValueError(f"num_register_tokens must be an integer >= 0 (got {reg!r})")
+        if reg > 0 and float(cfg.patch_drop_rate) > 0.0:
+            raise ValueError(f"num_register_tokens ({reg}) together with patch_drop_rate ({cfg.patch_drop_rate}) is not built yet")
         self.cfg = cfg
+        # register tokens: R rows behind CLS; every forward then runs at T = 1 + R + N
+        self.reg = int(reg)
         self.loss_name, self.loss_kind = resolved_loss(cfg.task_type, loss_name)
         # masked spectrum modelling (task_type 'mim'): every forward masks a block selection of the patch
         # tokens and the loss is the reconstruction of the masked windows; labels are ignored
@@ -557,8 +575,10 @@ class ViTEngine:
         gc.collect()
         c = self.cfg
         dev = self.flat.device
-        D, Fd, H, L, N, P = c.hidden_size, c.intermediate_size, c.num_attention_heads, c.num_hidden_layers, T - 1, c.patch_size
+        R = self.reg  # 0 under patch dropout (the two exclude each other)
+        D, Fd, H, L, N, P = c.hidden_size, c.intermediate_size, c.num_attention_heads, c.num_hidden_layers, T - 1 - R, c.patch_size
         M = B * T
+        Mc = B * (N + 1)  # 'mim': the rows the decoder reads and the loss kernels index (= M without registers)
         # GEMM row count: token rows padded to the 256-row tiles of the ping-pong GEMM core when the widths allow it.
         # Every buffer a GEMM reads or writes is allocated ZEROED with Mp rows and used through its first M rows by
         # everything else (LayerNorm, attention, reducers write real rows only), so pad rows hold zeros or finite
@@ -606,16 +626,20 @@ class ViTEngine:
             # (in f32 mode the x3 products read `last` itself); its output, f32 in either mode
             i32 = torch.int32
             nb, kb = mim_blocks(N, c.mim_span, c.mim_mask_ratio)
+            # With registers both are compact: rows R .. T-1 of each sample (mim_last then is a copy in either precision).
             act.update(mim_mask=E((B, N), i32), mim_keep=E((B, kb), i32), mim_slot=E((B, nb), i32),
-                       mim_last=G(D, b16) if self.precision == "bf16" else act["last"].view(M, D), mim_pred=E((M, P), f32))
+                       mim_last=G(D, b16)[:Mc] if (self.precision == "bf16" or R > 0) else act["last"].view(M, D),
+                       mim_pred=E((Mc, P), f32))
         tmp = {}
         if train and self.mim:
-            tmp["mim_dpred"] = G(P, b16)
+            tmp["mim_dpred"] = G(P, b16)[:Mc]
         if train:
             tmp.update(
                 dxa=E((M, D), f32), dxb=E((M, D), f32), dy=G(D, b16), dy2=G(D, b16), dU=G(Fd, b16), dh=G(D, b16),
                 dqkv=G(3 * D, b16), dctx=G(D, b16), delta=E((B * H, T), f32), dpatch=E((B * N, D), b16),
-                dlast=E((B, T, D), f32),
+                # 'mim' with registers: the decoder's dX writes rows R .. T-1 of each sample and nothing else writes dlast, so the
+                # CLS and register rows in front keep the zeros of the allocation (the decoder reads none of them)
+                dlast=torch.zeros((B, T, D), dtype=f32, device=dev) if (self.mim and R > 0) else E((B, T, D), f32),
                 c_dxa=E((B, D), f32), c_dxb=E((B, D), f32), c_dy=E((B, D), b16), c_dy2=E((B, D), b16), c_dU=E((B, Fd), b16),
                 c_dh=E((B, D), b16), c_dlast=E((B, 1, D), f32),
                 # the CLS tail's dctx: only its rows b*T are ever written, every other row keeps the zero it was allocated
@@ -637,13 +661,20 @@ class ViTEngine:
 
     def _rope_tables(self, T: int):
         """Half-width cos / sin tables of RotaryPositionEmbedding (rope.py:36-56), computed on the host by the reference's
-        own expression (so the table bits are the reference's) and kept on the device."""
+        own expression (so the table bits are the reference's) and kept on the device.
+        With R register tokens the table of the 1 + N positions is gathered by row on the host: table_R[0] = table[0] and
+        table_R[t] = table[max(0, t - R)] for t >= 1 -- CLS keeps position 0, patch n position 1 + n, and a register takes
+        position 0, the identity rotation.  Such a table is not linear in t, so it goes to vit_rope_qk (which reads the table
+        per row), never to the GEMM's rotating epilogue."""
         c = self.cfg
-        key = (T, c.head_dim, float(c.rope_base), self.flat.device)
+        R = self.reg
+        key = (T, R, c.head_dim, float(c.rope_base), self.flat.device)
         if self._rope_key != key:
             dim = c.head_dim
             inv_freq = 1.0 / (c.rope_base ** (torch.arange(0, dim, 2).float() / dim))
-            freqs = torch.outer(torch.arange(T).type_as(inv_freq), inv_freq)
+            freqs = torch.outer(torch.arange(T - R).type_as(inv_freq), inv_freq)
+            if R > 0:
+                freqs = freqs[(torch.arange(T) - R).clamp_(min=0)]
             self._rope = (freqs.cos().contiguous().to(self.flat.device), freqs.sin().contiguous().to(self.flat.device))
             self._rope_key = key
         return self._rope
@@ -767,14 +798,21 @@ class ViTEngine:
         full, cls = self._rows
         # --- embeddings: unfold -> projection (+bias) into token rows 1..N -> CLS / pos-emb / dropout
         x0 = a["x"][0]
-        pos = self.p(EMBED + "position_embeddings").view(c.seq_len, D) if c.pos_encoding_type == "learned" else None
+        R = self.reg
+        pos = self.p(EMBED + "position_embeddings").view(1 + N, D) if c.pos_encoding_type == "learned" else None
         rope = self._rope_tables(c.seq_len) if c.pos_encoding_type == "rope" else None
+        # RoPE by a vit_rope_qk pass behind the QKV projection instead of its rotating epilogue: tables that are not linear in the
+        # row (patch dropout's per-row gather; the register rows' position 0)
+        rope_pass = K is not None or R > 0
         if K is None:
             mask = self._mim_select(B, seed, training) if self.mim else None
             vf.unfold_cast(x, P, S, N, out=a["patches"])  # bf16 or f32 patches, per the arena dtype
             vf.gemm(a["patches"], self.W(PROJ).view(D, P), M=B * N, N=D, K=P, out=x0.view(M, D), bias=self.b(PROJ),
-                    row_map=(N, T, 1))
-            if mask is None:
+                    row_map=(N, T, 1 + R))
+            if R > 0:  # CLS, the register rows, (the mask token,) pos-emb on CLS and patches, dropout on every row
+                vf.embed_finish_reg(x0, R, self.p(EMBED + "cls_token").view(D), self.p(REGISTERS).view(R, D), pos, mask,
+                                    self.p(MASK_TOKEN).view(D) if mask is not None else None, dropout=(ph, seed, 0))
+            elif mask is None:
                 vf.embed_finish(x0, self.p(EMBED + "cls_token").view(D), pos, dropout=(ph, seed, 0))
             else:  # a masked patch's projected token gives way to the mask token, in front of pos-emb and dropout
                 vf.embed_finish_masked(x0, self.p(EMBED + "cls_token").view(D), mask, self.p(MASK_TOKEN).view(D), pos,
@@ -810,9 +848,9 @@ class ViTEngine:
             # vit_with_rope.py:58-60: q, k rotated per head before the scores -- inside the projection's epilogue where the
             # kernel has one (f32 values, one rounding), by a vit_rope_qk pass behind it otherwise (the library decides)
             vf.gemm(a["h1"][j], self._qkv16(i), M=full.n, N=3 * D, K=D, out=a["qkv"][j], bias=self._qkv_bias(i, self.flat),
-                    rope=None if rope is None or K is not None else (rope[0], rope[1], T, dh, 2 * D))
-            if rope is not None and K is not None:
-                vf.rope_qk(a["qkv"][j], rope[0], rope[1], M, H, dh)
+                    rope=None if rope is None or rope_pass else (rope[0], rope[1], T, dh, 2 * D))
+            if rope is not None and rope_pass:  # position = row % (the table's rows): M under patch dropout, T with registers
+                vf.rope_qk(a["qkv"][j], rope[0], rope[1], M if K is not None else T, H, dh)
             vf.attention_fwd(a["qkv"][j], B, H, T, dh, scale, dropout=(pa, seed, self._site(i, 0)), ctx=a["ctx"][j],
                              lse=a["lse"][j], ctx_lo=a["ctx_lo"][j])
             if output_attentions:
@@ -831,11 +869,16 @@ class ViTEngine:
         if self.mim:
             # pred[b, n, :] = decoder(last[b, 1 + n, :]) over all M rows (the CLS row's output is ignored by the loss), then the
             # reconstruction loss of the masked windows against the signal this forward was given
-            if self.precision == "bf16":
+            # With registers the decoder reads rows R .. T-1 of each sample, gathered (and cast) into the compact mim_last by a
+            # strided device copy: N + 1 rows per sample, the loss kernels' layout, whose first row they ignore.
+            if R > 0:
+                a["mim_last"].view(B, N + 1, D).copy_(full.last[:, R:, :])
+            elif self.precision == "bf16":
                 vf.cast_f32_bf16(full.last2[:M], a["mim_last"])
-            pred = vf.gemm(a["mim_last"], self.W(hn), M=M, N=P, K=D, out=a["mim_pred"], bias=self.b(hn))
+            Mc = B * (N + 1)
+            pred = vf.gemm(a["mim_last"], self.W(hn), M=Mc, N=P, K=D, out=a["mim_pred"], bias=self.b(hn))
             loss, count = vf.mim_loss_fwd(x, pred, mask, P, S, kind, c.mim_norm_target)
-            recon = pred.view(B, T, P)[:, 1:, :]
+            recon = pred.view(B, N + 1, P)[:, 1:, :]
             self._last = dict(B=B, seed=seed, ph=ph, pa=pa, pd=pd, labels=None, logits=recon, gen=self._gen, grad=need_grad,
                               tail=False, kind=kind, T=T, keep=None, mim=True, mask=mask, count=count, x=x, pred=pred,
                               pool="token")
@@ -852,7 +895,7 @@ class ViTEngine:
         pooled = r.last
         if self.avg_pool:  # the mean of this forward's patch rows (under patch dropout: of the K kept ones), read as [B, 1, D]
             pooled = a["c_last"]
-            vf.token_pool_fwd(full.last, 1, out=pooled)
+            vf.token_pool_fwd(full.last, 1 + R, out=pooled)
         logits, loss = vf.head_loss_fwd(pooled, self.p(hn + ".weight"), self.p(hn + ".bias"), labels, kind)
         self._last = dict(B=B, seed=seed, ph=ph, pa=pa, pd=pd, labels=labels, logits=logits, gen=self._gen, grad=need_grad,
                           tail=tail, kind=kind, T=T, keep=a["keep"] if K is not None else None, mim=False,
@@ -1087,7 +1130,8 @@ class ViTEngine:
         B, seed, ph, pa, pd = st["B"], st["seed"], st["ph"], st["pa"], st["pd"]  # pd: the forward's path rates
         T, keep = st["T"], st["keep"]  # the forward's sequence length and, under patch dropout, its selection [B, T - 1]
         self._T = T
-        D, H, L, N, P = c.hidden_size, c.num_attention_heads, c.num_hidden_layers, T - 1, c.patch_size  # N: patch rows per sample
+        R = self.reg  # 0 under patch dropout
+        D, H, L, N, P = c.hidden_size, c.num_attention_heads, c.num_hidden_layers, T - 1 - R, c.patch_size  # N: patch rows per sample
         dh, M = c.head_dim, B * T
         scale = dh ** -0.5
         rope, rope_T = None, T
@@ -1104,14 +1148,16 @@ class ViTEngine:
             dpred = t["mim_dpred"]
             vf.mim_loss_bwd(st["x"], st["pred"], st["mask"], st["count"], dloss, P, c.stride, st["kind"], c.mim_norm_target,
                             dpred=dpred)
-            vf.gemm(dpred, self.W(hn), M=M, N=D, K=P, b_trans=True, out=full.dlast.view(M, D))
+            # with registers dpred is compact: its row b * (N + 1) + j is the gradient of token row b * T + R + j
+            vf.gemm(dpred, self.W(hn), M=B * (N + 1), N=D, K=P, b_trans=True, out=full.dlast.view(M, D),
+                    row_map=(N + 1, T, R) if R > 0 else (0, 0, 0))
             self._dw(full, dpred, a["mim_last"], self.dW(hn))
             vf.colsum(dpred, out=self.db(hn), accumulate=self._accum)
         elif st["pool"] == "avg":
             # the head's backward over the pooled rows, then every patch row of dlast takes its sample's share (CLS rows: zeros)
             vf.head_loss_bwd(a["c_last"], self.p(hn + ".weight"), st["logits"], st["labels"], dloss, st["kind"],
                              dlast=t["c_dlast"], dW=self.dW(hn), db=self.db(hn))
-            vf.token_pool_bwd(t["c_dlast"], full.dlast, 1)
+            vf.token_pool_bwd(t["c_dlast"], full.dlast, 1 + R)
             self._setup_side()
         else:
             vf.head_loss_bwd(r.last, self.p(hn + ".weight"), st["logits"], st["labels"], dloss, st["kind"], dlast=r.dlast,
@@ -1148,8 +1194,13 @@ class ViTEngine:
             dx, spare = spare, dx
             self._unfold_layer_scale(i)
             self._notify(*self.layout.layer_ranges[i])
-        dpos = self.g(EMBED + "position_embeddings").view(c.seq_len, D) if c.pos_encoding_type == "learned" else None
-        if st["mim"]:  # masked rows: a zero dpatch row, their gradient goes to the mask token
+        dpos = self.g(EMBED + "position_embeddings").view(-1, D) if c.pos_encoding_type == "learned" else None
+        if R > 0:  # the plain and the masked model alike: dcls, dreg, dpos (CLS and patch rows), dmask_token
+            mim = st["mim"]
+            vf.embed_finish_reg_bwd(dx.view(B, T, D), R, self.g(EMBED + "cls_token").view(D), self.g(REGISTERS).view(R, D), dpos,
+                                    st["mask"] if mim else None, self.g(MASK_TOKEN).view(D) if mim else None,
+                                    dropout=(ph, seed, 0), dpatch=t["dpatch"])
+        elif st["mim"]:  # masked rows: a zero dpatch row, their gradient goes to the mask token
             vf.embed_finish_masked_bwd(dx.view(B, T, D), st["mask"], self.g(EMBED + "cls_token").view(D), self.g(MASK_TOKEN).view(D),
                                        dpos, dropout=(ph, seed, 0), dpatch=t["dpatch"])
         elif keep is None:

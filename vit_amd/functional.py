@@ -547,6 +547,60 @@ def embed_finish_masked_bwd(dtokens, mask, dcls, dmask_token, dpos=None, dropout
     return dpatch
 
 
+# ------------------------------------------------------------------------------------------------ register tokens
+def _chk_reg(tokens, R: int, cls, reg, pos, mask, mask_token, who: str, mt_name: str):
+    """The shape and dtype checks the two register entry points share; returns (B, N, D)."""
+    _chk(tokens, torch.float32, who + " tokens")
+    if isinstance(R, bool) or not isinstance(R, int) or R < 0:
+        raise _cabi.VitError(f"{who}: R must be an integer >= 0, got {R!r}")
+    if tokens.dim() != 3 or tokens.shape[1] < 2 + R:
+        raise _cabi.VitError(f"{who}: tokens must be [B, 1 + R + N, D] with N >= 1, got {tuple(tokens.shape)} at R={R}")
+    B, T, D = tokens.shape
+    N = T - 1 - R
+    _chk(cls, torch.float32, who + " cls")
+    if R > 0:
+        if reg is None:
+            raise _cabi.VitError(f"{who}: R={R} needs the register tensor [{R}, {D}]")
+        _chk(reg, torch.float32, who + " reg")
+    if (mask is None) != (mask_token is None):
+        raise _cabi.VitError(f"{who}: mask and {mt_name} go together")
+    if mask is not None:
+        _chk_index(mask, B, N, who + " mask")
+        _chk(mask_token, torch.float32, f"{who} {mt_name}")
+    if pos is not None:
+        _chk(pos, torch.float32, who + " pos")
+    if cls.numel() != D or (R > 0 and reg.numel() != R * D) or (mask_token is not None and mask_token.numel() != D) or \
+            (pos is not None and pos.numel() != (1 + N) * D):
+        raise _cabi.VitError(f"{who}: cls and {mt_name} must hold [{D}], reg [{R}, {D}], pos [{1 + N}, {D}]")
+    return B, N, D
+
+
+def embed_finish_reg(tokens, R: int, cls, reg, pos=None, mask=None, mask_token=None, dropout: Dropout = NO_DROP):
+    """embed_finish / embed_finish_masked over tokens [B, 1 + R + N, D] with R register rows behind CLS (vit_embed_finish_reg):
+    row 0 <- cls, rows 1 .. R <- reg [R, D], a masked patch (mask int32 [B, N] non-zero) <- mask_token; pos [1 + N, D] is added to
+    CLS (row 0) and patch n (row 1 + n), nothing to a register; dropout over every row.  In place."""
+    B, N, D = _chk_reg(tokens, R, cls, reg, pos, mask, mask_token, "embed_finish_reg", "mask_token")
+    p, seed, site = dropout
+    _h(tokens).call("vit_embed_finish_reg", tokens.data_ptr(), cls.data_ptr(), _ptr(reg if R > 0 else None), _ptr(pos), _ptr(mask),
+                    _ptr(mask_token), B, R, N, D, p, seed, site, _stream(tokens))
+    return tokens
+
+
+def embed_finish_reg_bwd(dtokens, R: int, dcls, dreg, dpos=None, mask=None, dmask_token=None, dropout: Dropout = NO_DROP,
+                         dpatch=None, out_dtype=torch.bfloat16, accumulate: bool = False):
+    """The backward of embed_finish_reg: dpatch [B * N, D] (exact zeros in masked rows); dcls [D], dreg [R, D], dpos [1 + N, D],
+    dmask_token [D] (with a mask) as batch sums in the order of include/vit_amd_registers.h."""
+    B, N, D = _chk_reg(dtokens, R, dcls, dreg, dpos, mask, dmask_token, "embed_finish_reg_bwd", "dmask_token")
+    dpatch = dpatch if dpatch is not None else torch.empty((B * N, D), dtype=out_dtype, device=dtokens.device)
+    if dpatch.numel() != B * N * D:
+        raise _cabi.VitError("embed_finish_reg_bwd: dpatch must hold [B*N, D]")
+    p, seed, site = dropout
+    _h(dtokens).call("vit_embed_finish_reg_bwd", dtokens.data_ptr(), _ptr(mask), dpatch.data_ptr(), _DT[dpatch.dtype], dcls.data_ptr(),
+                     _ptr(dreg if R > 0 else None), _ptr(dpos), _ptr(dmask_token), B, R, N, D, p, seed, site, int(accumulate),
+                     _stream(dtokens))
+    return dpatch
+
+
 def _chk_mim(x, pred, mask, P: int, who: str):
     _chk(x, torch.float32, who + " x")
     B, L = x.shape

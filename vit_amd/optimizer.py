@@ -646,7 +646,8 @@ def _scheduler_kwargs(fam: str, cfg: dict, lr: float) -> dict:
     return kw
 
 
-_NO_DECAY_NAMES = ("vit.embeddings.cls_token", "vit.embeddings.position_embeddings", "vit.embeddings.mask_token")  # mask_token: 'mim' models
+_NO_DECAY_NAMES = ("vit.embeddings.cls_token", "vit.embeddings.position_embeddings", "vit.embeddings.mask_token",  # mask_token: 'mim' models
+                   "vit.embeddings.register_tokens")  # model.num_register_tokens > 0
 _LAYER = re.compile(r"(?:^|\.)encoder\.layer\.(\d+)\.")
 
 

@@ -56,7 +56,7 @@ class MaskedModelingOutput(SequenceClassifierOutput):
 
 
 def build_model_name(config, model_prefix: str = "ViT", full_config: dict = None) -> str:
-    """Run name `{prefix}_p{patch}_h{hidden}_l{layers}_a{heads}_s{stride}_p{proj_fn}[_nz{noise digits}][_mim][_gap]` -- the rule of
+    """Run name `{prefix}_p{patch}_h{hidden}_l{layers}_a{heads}_s{stride}_p{proj_fn}[_nz{noise digits}][_mim][_gap][_reg{R}]` -- the rule of
     src/models/model_utils.py:9-45 (pinned by tests/golden/names.json).  The stride tag is the explicit `stride_size` when
     one is set (truthy), else the `stride_ratio`; a positive noise level is appended with its decimal point removed; a masked
     spectrum model (task_type 'mim', this build's) appends `_mim`, a model whose head reads the mean of the patch tokens
@@ -74,6 +74,8 @@ def build_model_name(config, model_prefix: str = "ViT", full_config: dict = None
         name += "_mim"
     if getattr(config, "global_pool", "token") == "avg":
         name += "_gap"
+    if int(getattr(config, "num_register_tokens", 0) or 0) > 0:  # register tokens (this build's): `_reg{R}`
+        name += f"_reg{int(config.num_register_tokens)}"
     return name
 
 
@@ -237,10 +239,17 @@ class MyViT(nn.Module):
     def init_weights(self):
         """HF `_init_weights` as the reference triggers it (specvit.py:57): Linear / Conv weights ~ trunc_normal(0,
         initializer_range), biases 0, LayerNorm 1/0.  cls_token and learned position_embeddings belong to
-        SpectraEmbeddings (not an HF ViTEmbeddings), so they keep their torch.randn values (embedding.py:47,62-64)."""
+        SpectraEmbeddings (not an HF ViTEmbeddings), so they keep their torch.randn values (embedding.py:47,62-64).
+        `register_tokens` (model.num_register_tokens > 0) ~ N(0, initializer_range^2), drawn AFTER every other tensor: a model
+        with registers starts from the values the same config and seed give every other tensor without them.  timm starts its
+        registers at std 1e-6; initializer_range is this project's choice (HF Dinov2WithRegisters starts them at zero, where
+        identical registers receive identical gradients and stay identical for ever)."""
         std = self.config.initializer_range
+        registers = None
         for name, p in zip(self._param_names, self._param_list):
-            if name.endswith("cls_token") or name.endswith("position_embeddings"):
+            if name.endswith("register_tokens"):
+                registers = p
+            elif name.endswith("cls_token") or name.endswith("position_embeddings"):
                 p.copy_(torch.randn(p.shape))
             elif name.endswith("mask_token"):  # task_type 'mim': HF ViTEmbeddings starts it at zero
                 p.zero_()
@@ -252,6 +261,8 @@ class MyViT(nn.Module):
                 p.zero_()
             else:
                 _trunc_normal_(p, std)
+        if registers is not None:
+            registers.copy_(torch.randn(registers.shape) * std)
 
     # ------------------------------------------------------------------ reference surface
     @property

@@ -176,6 +176,23 @@ def saved_global_pool(ckpt: Dict[str, Any]) -> Optional[str]:
     return str(cfg["model"].get("global_pool") or "token")
 
 
+def saved_register_tokens(ckpt: Dict[str, Any]) -> Optional[int]:
+    """`model.num_register_tokens` of the run that wrote `ckpt` (0 when its config has no such key), or None for a file without
+    a stored config (a bare state_dict)."""
+    cfg = (ckpt.get("hyper_parameters") or {}).get("config")
+    if not isinstance(cfg, dict) or not isinstance(cfg.get("model"), dict):
+        return None
+    return int(cfg["model"].get("num_register_tokens") or 0)
+
+
+def check_register_tokens(ckpt: Dict[str, Any], config, what: str):
+    """A checkpoint continues, or is evaluated by, a model of its own sequence layout only: ValueError naming both values."""
+    saved, own = saved_register_tokens(ckpt), int(getattr(config, "num_register_tokens", 0) or 0)
+    if saved is not None and saved != own:
+        raise ValueError(f"{what}: the checkpoint was trained with model.num_register_tokens {saved}, the config says {own}; "
+                         f"to start a model with other registers from its weights use model.init_from")
+
+
 class FreezeSchedule:
     """When the input preprocessor is trainable (reference: PreprocessorFreezeCallback, src/prepca/callbacks.py; pinned on
     it by tests/golden/freeze.json): `freeze_epochs` > 0 = frozen at the start of training and released once, at the first
@@ -559,6 +576,7 @@ class Trainer:
         if ckpt_path not in (None, "", "none", "None"):
             path = self.checkpointer.resolve(ckpt_path) if self.checkpointer else ckpt_path
             ckpt = load_checkpoint_file(path)
+            check_register_tokens(ckpt, module.model.config, "test --ckpt")
             module.model.load_state_dict(model_state_from_checkpoint(ckpt))
             # the pooling mode changes no tensor's name or shape, so the state_dict cannot tell: the checkpoint's own config does
             pool = saved_global_pool(ckpt)
@@ -600,6 +618,7 @@ class Trainer:
 
     def _resume(self, module, ckpt_path: str) -> int:
         ckpt = load_checkpoint_file(ckpt_path)
+        check_register_tokens(ckpt, module.model.config, "--ckpt")
         pool = saved_global_pool(ckpt)
         if pool is not None and pool != getattr(module.model.config, "global_pool", "token"):
             raise ValueError(f"--ckpt resumes a run trained with model.global_pool '{pool}', the config says "
