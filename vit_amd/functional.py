@@ -67,7 +67,8 @@ def gemm(a: torch.Tensor, b: torch.Tensor, *, M: int, N: int, K: int, a_trans: b
          dropout: Dropout = NO_DROP, residual: Optional[torch.Tensor] = None, row_map: Tuple[int, int, int] = (0, 0, 0),
          out_rows: Optional[int] = None, split_k: int = 0, accumulate: bool = False,
          colsum_out: Optional[torch.Tensor] = None,
-         rope: Optional[Tuple[torch.Tensor, torch.Tensor, int, int, int]] = None, drop_row_stride: int = 0) -> torch.Tensor:
+         rope: Optional[Tuple[torch.Tensor, torch.Tensor, int, int, int]] = None, drop_row_stride: int = 0,
+         ldaux: Optional[int] = None, ldres: Optional[int] = None) -> torch.Tensor:
     """`drop_row_stride = s > 1`: the dropout mask of output row r is the one of row r * s (the rows are a strided subset of
     a larger problem's: A read in place with `lda = s * K`, compact output).
     `rope = (cos, sin, T, head_dim, cols)`: rotary embedding of columns [0, cols) of the output (the q / k thirds of a fused QKV
@@ -89,10 +90,10 @@ def gemm(a: torch.Tensor, b: torch.Tensor, *, M: int, N: int, K: int, a_trans: b
     d.alpha = alpha
     d.bias = _ptr(bias)
     d.act = act
-    d.aux_out, d.aux_in, d.ldaux = _ptr(aux_out), _ptr(aux_in), N
+    d.aux_out, d.aux_in, d.ldaux = _ptr(aux_out), _ptr(aux_in), ldaux if ldaux is not None else N
     d.dropout_p, d.seed, d.site = dropout
     d.drop_row_stride = int(drop_row_stride)
-    d.residual, d.ldres = _ptr(residual), N
+    d.residual, d.ldres = _ptr(residual), ldres if ldres is not None else N
     d.rows_per_batch, d.out_batch_rows, d.out_row_offset = row_map
     d.split_k = split_k
     d.accumulate = int(accumulate)
