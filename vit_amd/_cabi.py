@@ -67,6 +67,20 @@ class MixRow(C.Structure):
                 ("reserved", C.c_int32 * 2)]
 
 
+class MuonMat(C.Structure):
+    """vit_muon_mat (include/vit_amd_muon.h): one matrix of a Muon table, 48 bytes."""
+    _fields_ = [("off", C.c_int64), ("xoff", C.c_int64), ("rows", C.c_int32), ("cols", C.c_int32), ("group", C.c_int32),
+                ("ratio", C.c_float), ("tile0", C.c_int32), ("ttile0", C.c_int32), ("reserved", C.c_int64)]
+
+
+class MuonProblem(C.Structure):
+    """vit_muon_problem (include/vit_amd_muon.h): one product of a grouped launch, 72 bytes."""
+    _fields_ = [("A", C.c_void_p), ("B", C.c_void_p), ("R", C.c_void_p), ("C", C.c_void_p),
+                ("m", C.c_int32), ("n", C.c_int32), ("k", C.c_int32),
+                ("lda", C.c_int32), ("ldb", C.c_int32), ("ldr", C.c_int32), ("ldc", C.c_int32),
+                ("alpha", C.c_float), ("beta", C.c_float), ("reserved", C.c_int32)]
+
+
 _P, _I, _F, _U64, _I64, _SZ = C.c_void_p, C.c_int, C.c_float, C.c_uint64, C.c_int64, C.c_size_t
 
 # name -> argtypes (restype is int unless listed in _RESTYPES)
@@ -181,6 +195,18 @@ _PROTOS = {
     "vit_embed_finish_reg": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _U64, _U64, _P],
     "vit_embed_finish_reg_bwd": [_P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _F, _U64, _U64, _I, _P],
 }
+# Muon (include/vit_amd_muon.h, which includes vit_amd.h and is not included by it): a table of its own, bound beside _PROTOS
+# (h, g, buf, u, mats, n_mats, n_tiles, momentum, nesterov, sqnorm, max_norm, part, stream) /
+# (h, mats, n_mats, part, eps, inv_norm, norms, stream) / (h, u, x, mats, n_mats, n_ttiles, inv_norm, stream) /
+# (h, problems, n_problems, tiles, n_tiles, b_trans, stream) / (h, p, p_bf16, o, mats, n_mats, n_ttiles, groups, n_groups, stream)
+_PROTOS_MUON = {
+    "vit_muon_momentum": [_P, _P, _P, _P, _P, _I, _I, C.c_double, _I, _P, _F, _P, _P],
+    "vit_muon_norms": [_P, _P, _I, _P, _F, _P, _P, _P],
+    "vit_muon_normalize": [_P, _P, _P, _P, _I, _I, _P, _P],
+    "vit_muon_gemm_grouped": [_P, _P, _I, _P, _I, _I, _P],
+    "vit_muon_apply": [_P, _P, _P, _P, _P, _I, _I, _P, _I, _P],
+}
+MUON_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "vit_amd_muon.h")
 _RESTYPES = {"vit_last_error": C.c_char_p, "vit_last_gemm_kernel": C.c_char_p, "vit_workspace_needed": C.c_size_t}
 
 _lib = None
@@ -205,6 +231,11 @@ def declared_symbols(header_path: str = HEADER_PATH):
     return sorted(names)
 
 
+def declared_muon_symbols():
+    """The functions vit_amd_muon.h itself declares (what vit_amd.h's closure declares is `declared_symbols()`'s)."""
+    return sorted(set(declared_symbols(MUON_HEADER_PATH)) - set(declared_symbols()))
+
+
 def load():
     """dlopen the library (after torch, so both share torch's HIP runtime) and set prototypes."""
     global _lib
@@ -220,7 +251,7 @@ def load():
                 f"{LIB_PATH} is missing: run `python -m vit_amd.build` (or __graft_entry__.build()). "
                 "vit_amd has no fallback path; the HIP library is required.")
         lib = C.CDLL(LIB_PATH)
-        for name, argtypes in _PROTOS.items():
+        for name, argtypes in {**_PROTOS, **_PROTOS_MUON}.items():
             fn = getattr(lib, name)
             fn.argtypes = argtypes
             fn.restype = _RESTYPES.get(name, C.c_int)

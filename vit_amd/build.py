@@ -24,14 +24,14 @@ LIB = os.path.join(LIBDIR, "libvit_amd.so")
 ARCH = "gfx950"
 SOURCES = ["api.hip", "gemm.hip", "gemm2.hip", "layernorm.hip", "attention.hip", "attention_tiled.hip", "attention_resident.hip",
            "attention_pipe.hip", "attention_f32.hip", "elementwise.hip", "covariance.hip", "optim.hip", "ema.hip", "layerscale.hip", "mix.hip",
-           "patchdrop.hip", "mim.hip", "pool.hip", "sam.hip", "registers.hip"]
+           "patchdrop.hip", "mim.hip", "pool.hip", "sam.hip", "registers.hip", "muon.hip"]
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "attention.h"), os.path.join(ROOT, "include", "vit_amd.h"),
            os.path.join(ROOT, "include", "vit_amd_cov.h"), os.path.join(ROOT, "include", "vit_amd_optim.h"),
            os.path.join(ROOT, "include", "vit_amd_ema.h"), os.path.join(ROOT, "include", "vit_amd_droppath.h"),
            os.path.join(ROOT, "include", "vit_amd_layerscale.h"), os.path.join(ROOT, "include", "vit_amd_mix.h"),
            os.path.join(ROOT, "include", "vit_amd_patchdrop.h"), os.path.join(ROOT, "include", "vit_amd_mim.h"),
            os.path.join(ROOT, "include", "vit_amd_pool.h"), os.path.join(ROOT, "include", "vit_amd_sam.h"),
-           os.path.join(ROOT, "include", "vit_amd_registers.h")]
+           os.path.join(ROOT, "include", "vit_amd_registers.h"), os.path.join(ROOT, "include", "vit_amd_muon.h")]
 
 
 def _hipcc() -> str:

@@ -968,6 +968,243 @@ def lamb_step_groups(p, g, m, v, p_bf16, tables: ParamTables, trust, *, base=0, 
            *(() if dyn else (step,)), _ptr(sqnorm), max_norm, trust.data_ptr(), _stream(p))
 
 
+# ------------------------------------------------------------------------------------------------ optimizer: Muon
+MUON_TILE = 4096      # VIT_MUON_TILE (include/vit_amd_muon.h): elements per streaming tile of the norm's partial sums
+MUON_GEMM_TILE = 64   # VIT_MUON_GEMM_TILE: rows and columns of C per workgroup of the grouped product
+_MUON_TT = 32         # the transposing tile of vit_muon_normalize / vit_muon_apply
+
+
+def muon_adjust_ratio(mode: str, rows: int, cols: int) -> float:
+    """torch.optim.Muon's `_adjust_lr` as the factor on lr, for a matrix [rows, cols]."""
+    if mode == "original":
+        return max(1.0, rows / cols) ** 0.5
+    if mode == "match_rms_adamw":
+        return 0.2 * max(rows, cols) ** 0.5
+    if mode in (None, "none"):
+        return 1.0
+    raise ValueError(f"muon adjust_lr = {mode!r}: expected 'match_rms_adamw', 'original' or 'none'")
+
+
+def _device_bytes(array, device):
+    return torch.frombuffer(bytearray(bytes(array)), dtype=torch.uint8).to(device)
+
+
+class MuonTables:
+    """The device table of vit_muon_mat entries (include/vit_amd_muon.h) with its host mirror: `entries` = [(off, xoff, rows,
+    cols, group, ratio)], `n_tiles` / `n_ttiles` the totals of streaming / transposing tiles."""
+
+    def __init__(self, mats, entries, n_tiles, n_ttiles):
+        self.mats, self.entries, self.n_mats, self.n_tiles, self.n_ttiles = mats, entries, len(entries), n_tiles, n_ttiles
+
+    def check_run(self, base: int, n: int):
+        """A Muon call covers whole matrices: one of the table's that the run [base, base + n) cuts is a ValueError."""
+        muon_check_run([(off, rows, cols) for off, _, rows, cols, _, _ in self.entries], base, n)
+
+
+def muon_check_run(mats, base: int, n: int):
+    """`mats`: (off, rows, cols) of the matrices a run [base, base + n) of the flat buffer is to step.  The orthogonalisation is a
+    function of a whole matrix, so a run that cuts one is a ValueError (the one statement of that rule: the table's `check_run`
+    and FusedMuon's runs both come here)."""
+    lo, hi = int(base), int(base) + int(n)
+    for off, rows, cols in mats:
+        if not (lo <= off and off + rows * cols <= hi):
+            raise ValueError(f"muon: the run [{lo}, {hi}) cuts the matrix at [{off}, {off + rows * cols}); the orthogonalisation "
+                             f"is a function of the whole matrix")
+
+
+def muon_mat_table(entries, device, total: Optional[int] = None, compact_total: Optional[int] = None) -> MuonTables:
+    """Build and validate the matrix table from (off, xoff, rows, cols, group, ratio): rows and cols multiples of 16 (the MFMA
+    tiles' and the 16-byte accesses' granule), offsets multiples of 8 and non-negative, matrices overlapping neither in the flat
+    buffer nor in the compact one, inside `total` / `compact_total` where given."""
+    ents = [(int(o), int(x), int(r), int(c), int(gi), float(ratio)) for o, x, r, c, gi, ratio in entries]
+    if not ents:
+        raise ValueError("muon_mat_table: needs at least one matrix")
+    arr = (_cabi.MuonMat * len(ents))()
+    tile0 = ttile0 = 0
+    for i, (off, xoff, rows, cols, gi, ratio) in enumerate(ents):
+        if rows < 16 or cols < 16 or rows % 16 or cols % 16:
+            raise ValueError(f"muon_mat_table: matrix {i} is [{rows}, {cols}]; both sizes must be multiples of 16, at least 16")
+        if off < 0 or xoff < 0 or off % 8 or xoff % 8:
+            raise ValueError(f"muon_mat_table: matrix {i}: offsets ({off}, {xoff}) must be non-negative multiples of 8")
+        if gi < 0 or not ratio > 0:
+            raise ValueError(f"muon_mat_table: matrix {i}: group {gi} / ratio {ratio}")
+        if total is not None and off + rows * cols > total or compact_total is not None and xoff + rows * cols > compact_total:
+            raise ValueError(f"muon_mat_table: matrix {i} ends past its buffer")
+        arr[i] = _cabi.MuonMat(off, xoff, rows, cols, gi, ratio, tile0, ttile0, 0)
+        tile0 += -(-rows * cols // MUON_TILE)
+        ttile0 += -(-rows // _MUON_TT) * -(-cols // _MUON_TT)
+    for key in (0, 1):
+        spans = sorted((e[key], e[key] + e[2] * e[3]) for e in ents)
+        if any(a[1] > b[0] for a, b in zip(spans, spans[1:])):
+            raise ValueError("muon_mat_table: two matrices overlap")
+    return MuonTables(_device_bytes(arr, device), ents, tile0, ttile0)
+
+
+class MuonProblems:
+    """The device tables of one vit_muon_gemm_grouped launch: vit_muon_problem entries and the (problem, tile row, tile column, 0)
+    tile table.  `held` keeps the operand tensors alive: the table holds their addresses."""
+
+    def __init__(self, problems, tiles, n_problems, n_tiles, b_trans, held, shapes):
+        self.problems, self.tiles, self.n_problems, self.n_tiles = problems, tiles, n_problems, n_tiles
+        self.b_trans, self.held, self.shapes = bool(b_trans), held, shapes
+
+
+def _chk_muon_operand(t, shape, who):
+    if t.dtype != torch.bfloat16 or t.ndim != 2 or tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{who}: expected a bf16 matrix {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
+    if t.stride(1) != 1 or t.stride(0) % 8 or t.stride(0) < t.shape[1] or t.data_ptr() % 16:
+        raise ValueError(f"{who}: rows must be contiguous, the leading dimension a multiple of 8 and the pointer 16-byte aligned")
+
+
+def muon_problem_table(problems, b_trans: bool, device) -> MuonProblems:
+    """`problems`: [(A, B, R or None, C, alpha, beta)] of bf16 2-D views, C [m, n] = bf16(alpha * A op(B) + beta * R) with A [m, k]
+    and B [n, k] (`b_trans`: A B^T) or [k, n] (A B).  m, n, k multiples of 16; C must alias no operand."""
+    if not problems:
+        raise ValueError("muon_problem_table: needs at least one problem")
+    arr = (_cabi.MuonProblem * len(problems))()
+    tiles, held, shapes = [], [], []
+    for i, (A, B, R, Cm, alpha, beta) in enumerate(problems):
+        m, k = A.shape
+        n = B.shape[0] if b_trans else B.shape[1]
+        who = f"muon_problem_table: problem {i}"
+        if min(m, n, k) < 16 or m % 16 or n % 16 or k % 16:
+            raise ValueError(f"{who}: (m, n, k) = ({m}, {n}, {k}) must be multiples of 16, at least 16")
+        _chk_muon_operand(A, (m, k), who + " A")
+        _chk_muon_operand(B, (n, k) if b_trans else (k, n), who + " B")
+        _chk_muon_operand(Cm, (m, n), who + " C")
+        if R is not None:
+            _chk_muon_operand(R, (m, n), who + " R")
+        if beta != 0 and R is None:
+            raise ValueError(f"{who}: beta = {beta} needs R")
+        c_lo, c_hi = Cm.data_ptr(), Cm.data_ptr() + 2 * ((m - 1) * Cm.stride(0) + n)
+        for t in (A, B, R):
+            if t is not None and t.data_ptr() < c_hi and c_lo < t.data_ptr() + 2 * ((t.shape[0] - 1) * t.stride(0) + t.shape[1]):
+                raise ValueError(f"{who}: C overlaps an operand (other tiles still read it while one writes)")
+        arr[i] = _cabi.MuonProblem(A.data_ptr(), B.data_ptr(), None if R is None else R.data_ptr(), Cm.data_ptr(), m, n, k,
+                                   A.stride(0), B.stride(0), 0 if R is None else R.stride(0), Cm.stride(0), float(alpha),
+                                   float(beta), 0)
+        tiles += [(i, tr, tc, 0) for tr in range(-(-m // MUON_GEMM_TILE)) for tc in range(-(-n // MUON_GEMM_TILE))]
+        held += [A, B, R, Cm]
+        shapes.append((m, n, k))
+    # the header's rule is table-wide: no C_i may overlap an operand -- or another output -- of ANY problem of the launch
+    span = lambda t: (t.data_ptr(), t.data_ptr() + 2 * ((t.shape[0] - 1) * t.stride(0) + t.shape[1]))
+    outs = sorted(span(p[3]) + (i,) for i, p in enumerate(problems))
+    for (_, a_hi, i), (b_lo, _, j) in zip(outs, outs[1:]):
+        if b_lo < a_hi:
+            raise ValueError(f"muon_problem_table: the outputs of problems {i} and {j} overlap")
+    reads = sorted({span(t) for p in problems for t in p[:3] if t is not None})
+    for c_lo, c_hi, i in outs:
+        for r_lo, r_hi in reads:  # ascending by start: nothing behind the first that starts at or past c_hi can overlap
+            if r_lo >= c_hi:
+                break
+            if c_lo < r_hi:
+                raise ValueError(f"muon_problem_table: C of problem {i} overlaps an operand of the launch (other tiles still "
+                                 f"read it while one writes)")
+    return MuonProblems(_device_bytes(arr, device), torch.tensor(tiles, dtype=torch.int32, device=device), len(problems), len(tiles),
+                        b_trans, held, shapes)
+
+
+def muon_gemm_grouped(table: MuonProblems):
+    """Every problem of the table in one launch (vit_muon_gemm_grouped)."""
+    _h(table.problems).call("vit_muon_gemm_grouped", table.problems.data_ptr(), table.n_problems, table.tiles.data_ptr(),
+                            table.n_tiles, int(table.b_trans), _stream(table.problems))
+
+
+def _chk_muon_compact(t, dtype, tables: MuonTables, name: str):
+    _chk(t, dtype, name)
+    need = max(x + r * c for _, x, r, c, _, _ in tables.entries)
+    if t.numel() < need:
+        raise ValueError(f"{name}: holds {t.numel()} elements, the table's matrices need {need}")
+
+
+def muon_momentum(g, buf, u, tables: MuonTables, part, *, momentum=0.95, nesterov=True, sqnorm=None, max_norm=0.0):
+    """buf <- lerp(buf, g * clip, 1 - momentum); u (bf16) <- the Nesterov (or plain) momentum; part[tile] <- sum bf16(u)^2 (f64).
+    `g` is the flat gradient buffer from element 0 (the table's `off`), `buf` / `u` the compact ones (`xoff`)."""
+    _chk(g, torch.float32, "muon_momentum g")
+    _chk_muon_compact(buf, torch.float32, tables, "muon_momentum buf")
+    _chk_muon_compact(u, torch.bfloat16, tables, "muon_momentum u")
+    _chk(part, torch.float64, "muon_momentum part")
+    if part.numel() < tables.n_tiles or g.numel() < max(o + r * c for o, _, r, c, _, _ in tables.entries):
+        raise ValueError("muon_momentum: part or g is shorter than the table needs")
+    _h(g).call("vit_muon_momentum", g.data_ptr(), buf.data_ptr(), u.data_ptr(), tables.mats.data_ptr(), tables.n_mats,
+               tables.n_tiles, float(momentum), int(bool(nesterov)), _ptr(sqnorm), float(max_norm), part.data_ptr(), _stream(g))
+
+
+def muon_norms(tables: MuonTables, part, inv_norm, norms, *, eps=1e-7):
+    """norms[i] <- ||X0_i||_F and inv_norm[i] <- 1 / max(norm, eps), one wave per matrix over its tiles' partials."""
+    _chk(part, torch.float64, "muon_norms part")
+    _chk(inv_norm, torch.float32, "muon_norms inv_norm")
+    _chk(norms, torch.float32, "muon_norms norms")
+    if part.numel() < tables.n_tiles or min(inv_norm.numel(), norms.numel()) < tables.n_mats:
+        raise ValueError("muon_norms: part, inv_norm or norms is shorter than the table needs")
+    _h(part).call("vit_muon_norms", tables.mats.data_ptr(), tables.n_mats, part.data_ptr(), float(eps), inv_norm.data_ptr(),
+                  norms.data_ptr(), _stream(part))
+
+
+def muon_normalize(u, x, tables: MuonTables, inv_norm):
+    """x (bf16, the wide orientation [m, n], m <= n) <- bf16(u * inv_norm), transposed where rows > cols."""
+    _chk_muon_compact(u, torch.bfloat16, tables, "muon_normalize u")
+    _chk_muon_compact(x, torch.bfloat16, tables, "muon_normalize x")
+    _chk(inv_norm, torch.float32, "muon_normalize inv_norm")
+    if inv_norm.numel() < tables.n_mats or u.data_ptr() == x.data_ptr():
+        raise ValueError("muon_normalize: inv_norm is shorter than the table, or x aliases u")
+    _h(u).call("vit_muon_normalize", u.data_ptr(), x.data_ptr(), tables.mats.data_ptr(), tables.n_mats, tables.n_ttiles,
+               inv_norm.data_ptr(), _stream(u))
+
+
+def muon_apply(p, p_bf16, o, tables: MuonTables, groups):
+    """W <- W * (1 - lr * wd) - lr * ratio * O per matrix, O = `o` transposed back; `groups`: the f32 [n_groups, 4] group table."""
+    _chk(p, torch.float32, "muon_apply p")
+    _chk_muon_compact(o, torch.bfloat16, tables, "muon_apply o")
+    _chk(groups, torch.float32, "muon_apply groups")
+    need = max(off + r * c for off, _, r, c, _, _ in tables.entries)
+    if p.numel() < need or (p_bf16 is not None and p_bf16.numel() < need):
+        raise ValueError("muon_apply: p or p_bf16 is shorter than the table needs")
+    if max(e[4] for e in tables.entries) >= groups.shape[0]:
+        raise ValueError("muon_apply: a matrix names a group past the group table")
+    _h(p).call("vit_muon_apply", p.data_ptr(), _ptr(p_bf16), o.data_ptr(), tables.mats.data_ptr(), tables.n_mats, tables.n_ttiles,
+               groups.data_ptr(), groups.shape[0], _stream(p))
+
+
+class MuonPlan:
+    """Everything one orthogonalisation of a table's matrices launches: the workspaces (u / the two X, A, B -- bf16, owned here)
+    and the three problem tables of an iteration for either parity of the X ping-pong.  `ns_steps` iterations are
+    3 * ns_steps launches; the result lies in `result(ns_steps)`."""
+
+    def __init__(self, tables: MuonTables, coefficients, device, x=None):
+        a, b, c = (float(v) for v in coefficients)
+        self.tables = tables
+        n_x = max(xo + r * cl for _, xo, r, cl, _, _ in tables.entries)
+        dims = [(min(r, cl), max(r, cl)) for _, _, r, cl, _, _ in tables.entries]
+        n_a = sum(m * m for m, _ in dims)
+        self.x = x if x is not None else [torch.zeros(n_x, dtype=torch.bfloat16, device=device) for _ in range(2)]
+        self.A = torch.zeros(n_a, dtype=torch.bfloat16, device=device)
+        self.B = torch.zeros(n_a, dtype=torch.bfloat16, device=device)
+        gram, poly, upd = [[], []], [], [[], []]
+        aoff = 0
+        for (_, xo, _, _, _, _), (m, n) in zip(tables.entries, dims):
+            X = [buf[xo:xo + m * n].view(m, n) for buf in self.x]
+            Am, Bm = self.A[aoff:aoff + m * m].view(m, m), self.B[aoff:aoff + m * m].view(m, m)
+            aoff += m * m
+            poly.append((Am, Am, Am, Bm, c, b))                       # B = b A + c A A   (A A^T: A is symmetric)
+            for par in (0, 1):
+                gram[par].append((X[par], X[par], None, Am, 1.0, 0.0))     # A = X X^T
+                upd[par].append((Bm, X[par], X[par], X[1 - par], 1.0, a))  # X' = a X + B X
+        self.gram = [muon_problem_table(g, True, device) for g in gram]
+        self.poly = muon_problem_table(poly, True, device)
+        self.upd = [muon_problem_table(u, False, device) for u in upd]
+
+    def iterate(self, ns_steps: int, start: int = 0):
+        """`ns_steps` Newton-Schulz iterations from x[start]; returns the buffer the result lies in."""
+        par = start
+        for _ in range(int(ns_steps)):
+            muon_gemm_grouped(self.gram[par])
+            muon_gemm_grouped(self.poly)
+            muon_gemm_grouped(self.upd[par])
+            par ^= 1
+        return self.x[par]
+
+
 # ------------------------------------------------------------------------------------------------ weight averaging
 def ema_update(ema, p, weight: float = 0.0, *, weight_dev=None, n: Optional[int] = None):
     """ema <- torch.lerp(ema, p, weight) over the first `n` elements (include/vit_amd_ema.h); `weight` is 1 - decay, already

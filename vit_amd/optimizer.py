@@ -9,6 +9,9 @@ against its torch class in tests/.  Any other optimizer type falls through to to
 (src/opt/optimizer.py:14-26,108; it then works on the `.grad` views the model's backward produces).
 One type beside the reference's: `lamb` -> `FusedLamb` (timm's Lamb; torch.optim has none, so there is nothing to fall
 through to and the type is an error on any other model), verified against a float64 restatement in tests/test_lamb_gpu.py.
+And `muon` -> `FusedMuon`: Muon on the encoder's weight matrices (a grouped MFMA kernel runs the Newton-Schulz products of all
+matrices in one launch each), AdamW on everything else; verified against torch.optim.Muon and a float64 restatement in
+tests/test_muon_gpu.py.  torch's own Muon refuses every parameter that is not 2-D, so this type, too, is an error on any other model.
 """
 from __future__ import annotations
 
@@ -20,7 +23,7 @@ import torch
 
 from . import functional as vf
 
-__all__ = ["OptModule", "FusedOptimizer", "FusedAdamW", "FusedLamb", "FusedSGD", "build_param_groups"]
+__all__ = ["OptModule", "FusedOptimizer", "FusedAdamW", "FusedLamb", "FusedMuon", "FusedSGD", "build_param_groups", "muon_matrix_names"]
 
 
 class FusedOptimizer(torch.optim.Optimizer):
@@ -508,6 +511,209 @@ class FusedLamb(FusedAdamW):
         return names, torch.cat(parts)
 
 
+MUON_STEMS = ("attention.attention.query", "attention.attention.key", "attention.attention.value", "attention.output.dense",
+              "intermediate.dense", "output.dense")
+_MUON_NAME = re.compile(r"^vit\.encoder\.layer\.\d+\.(?:" + "|".join(re.escape(s) for s in MUON_STEMS) + r")\.weight$")
+_MUON_KEYS = ("momentum", "nesterov", "ns_steps", "ns_coefficients", "eps", "adjust_lr")
+
+
+def muon_matrix_names(names):
+    """Of `names`, the Muon matrices: the six 2-D weights of every encoder layer (query, key and value each on its own, as
+    torch.optim.Muon would be given them).  Everything else -- biases, LayerNorms, tokens, positions, LayerScale, the patch
+    projection, the head, a decoder -- steps with AdamW."""
+    return [n for n in names if _MUON_NAME.match(n)]
+
+
+class _MuonRun:
+    """What one `_launch(lo, hi)` of FusedMuon issues: the AdamW sub-runs around the matrices, and the matrices' tables, plan
+    and per-matrix scale cells (None when the run holds no trainable matrix)."""
+
+    def __init__(self, adam_runs, names, tables, plan, part, inv_norm, norms):
+        self.adam_runs, self.names, self.tables, self.plan = adam_runs, names, tables, plan
+        self.part, self.inv_norm, self.norms = part, inv_norm, norms
+
+
+class FusedMuon(FusedAdamW):
+    """Muon on the encoder's weight matrices, AdamW on everything else, in one optimizer over MyViT's flat buffers (see
+    FusedOptimizer; the formulas stand in include/vit_amd_muon.h).  For each of `muon_matrix_names`: SGD momentum in an f32 buffer,
+    its Newton-Schulz orthogonalisation in bf16 (torch.optim.Muon's rounding points), and W = W (1 - lr wd) - lr ratio O with the
+    group's lr / weight_decay and ratio = torch's `_adjust_lr` (`adjust_lr`: 'match_rms_adamw' -- the default, so that one lr and
+    one weight_decay serve both halves --, 'original', 'none').  Every other tensor takes FusedAdamW's launch over the sub-runs
+    between the matrices, bit for bit FusedAdamW's result.  A frozen matrix is neither read nor written, nor is its buffer.
+    A step is, per active run: one vit_adamw_step_groups launch per sub-run between matrices (4 per encoder layer and the
+    embeddings': 49 at ViT-B), then 4 + 3 * ns_steps launches for all of the run's matrices together.
+    `state_dict()` holds torch.optim.Muon's {"momentum_buffer"} for a matrix and AdamW's {"step", "exp_avg", "exp_avg_sq"} for
+    the rest.  `last_ns_norms`: (names, norms) of the last step's ||X0||_F per matrix, a device tensor; None before a step.
+    The 'zero1' exchange is refused for LAMB's reason: a shard cuts matrices."""
+
+    _STATE = ("_m", "_v", "_buf")
+    _SHARED = ("betas", "eps", "momentum", "nesterov", "ns_steps", "ns_coefficients", "muon_eps", "adjust_lr")
+
+    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, momentum=0.95, nesterov=True, ns_steps=5,
+                 ns_coefficients=(3.4445, -4.775, 2.0315), muon_eps=1e-7, adjust_lr="match_rms_adamw", param_groups=None):
+        if not 0.0 <= float(momentum) < 1.0:
+            raise ValueError(f"FusedMuon: momentum = {momentum} must lie in [0, 1)")
+        if int(ns_steps) != ns_steps or not 0 <= int(ns_steps) < 100:
+            raise ValueError(f"FusedMuon: ns_steps = {ns_steps} must be an integer in [0, 100)")
+        if len(tuple(ns_coefficients)) != 3:
+            raise ValueError(f"FusedMuon: ns_coefficients = {ns_coefficients} must be three numbers (a, b, c)")
+        if not float(muon_eps) > 0:
+            raise ValueError(f"FusedMuon: eps = {muon_eps} must be positive")
+        vf.muon_adjust_ratio(adjust_lr, 16, 16)  # ValueError on an unknown mode
+        FusedOptimizer.__init__(self, model, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, momentum=float(momentum),
+                                                  nesterov=bool(nesterov), ns_steps=int(ns_steps),
+                                                  ns_coefficients=tuple(float(c) for c in ns_coefficients),
+                                                  muon_eps=float(muon_eps), adjust_lr=adjust_lr or "none"), param_groups)
+        self.adam_l2 = False
+        self._m = None
+        self._v = None
+        self._buf = None     # f32, compact: the matrices one behind the other (MuonTables' xoff)
+        self._x = None       # the two bf16 X workspaces, compact like _buf
+        self._mats = None    # [(name, parameter, off, xoff, rows, cols)] of every Muon matrix a group owns, by offset
+        self._runs = {}
+        self._last_runs, self._last_step = [], -1
+
+    def attach_reducer(self, reducer):
+        if getattr(reducer, "mode", "") == "zero1":
+            raise ValueError("FusedMuon does not support the 'zero1' exchange: its shards cut weight matrices and the "
+                             "orthogonalisation is a function of a whole matrix; use the all-reduce exchange")
+        super().attach_reducer(reducer)
+
+    # ------------------------------------------------------------------ the split
+    def _matrices(self):
+        if self._mats is None:
+            lay, by_name = self.model.engine.layout, dict(zip(self.model._param_names, self.model._param_list))
+            mats, xoff = [], 0
+            for name in sorted(muon_matrix_names(self.model._param_names), key=lambda n: lay.entries[n][0]):
+                off, (rows, cols) = lay.entries[name]
+                if off < lay.n_trainable and id(by_name[name]) in self._group_index:
+                    mats.append((name, by_name[name], off, xoff, rows, cols))
+                xoff += rows * cols  # a matrix's place in the compact buffers does not depend on who owns its neighbours
+            self._mats, self._mat_total = mats, xoff
+        return self._mats
+
+    def muon_split(self):
+        """(names of the Muon matrices, names of the AdamW-side tensors) among the flat buffer's trainable parameters a group owns."""
+        lay, mats = self.model.engine.layout, {m[0] for m in self._matrices()}
+        owned = [n for n, p in zip(self.model._param_names, self.model._param_list)
+                 if lay.entries[n][0] < lay.n_trainable and id(p) in self._group_index]
+        return [n for n in owned if n in mats], [n for n in owned if n not in mats]
+
+    def _refresh_members(self):
+        super()._refresh_members()
+        self._mats, self._runs = None, {}
+
+    def _ensure_state(self):
+        self._ensure_sq()
+        self._ensure_flat(("_m", "_v"))
+        self._matrices()
+        dev = self.model.engine.flat.device
+        if self._buf is None or self._buf.device != dev:
+            new = torch.zeros(max(self._mat_total, 8), dtype=torch.float32, device=dev)
+            if self._buf is not None:
+                new.copy_(self._buf)
+            self._buf, self._runs = new, {}
+        if self._x is None or self._x[0].device != dev:
+            self._x = [torch.zeros(max(self._mat_total, 8), dtype=torch.bfloat16, device=dev) for _ in range(2)]
+            self._runs = {}
+
+    def _run_for(self, lo, hi):
+        """The `_MuonRun` of flat[lo:hi]: cached per run, partition and set of frozen matrices."""
+        mats = [m for m in self._matrices() if m[2] < hi and m[2] + m[4] * m[5] > lo]
+        key = (lo, hi, self._partition_signature(), tuple(m[1].requires_grad for m in mats))
+        run = self._runs.get(key)
+        if run is None:
+            g0, dev = self.param_groups[0], self.model.engine.flat.device
+            vf.muon_check_run([(m[2], m[4], m[5]) for m in mats], lo, hi - lo)  # ValueError: the run cuts a matrix
+            adam_runs, at = [], lo
+            for _, _, off, _, rows, cols in mats:
+                if off > at:
+                    adam_runs.append((at, off))
+                at = off + rows * cols
+            if at < hi:
+                adam_runs.append((at, hi))
+            live = [m for m in mats if m[1].requires_grad]
+            if live:
+                tables = vf.muon_mat_table([(off, xoff, rows, cols, self._group_index[id(p)],
+                                             vf.muon_adjust_ratio(g0["adjust_lr"], rows, cols))
+                                            for _, p, off, xoff, rows, cols in live], dev, total=self.model.engine.flat.numel(),
+                                           compact_total=self._buf.numel())
+                run = _MuonRun(adam_runs, [m[0] for m in live], tables, vf.MuonPlan(tables, g0["ns_coefficients"], dev, x=self._x),
+                               torch.zeros(tables.n_tiles, dtype=torch.float64, device=dev),
+                               torch.zeros(tables.n_mats, dtype=torch.float32, device=dev),
+                               torch.zeros(tables.n_mats, dtype=torch.float32, device=dev))
+            else:
+                run = _MuonRun(adam_runs, [], None, None, None, None, None)
+            self._runs[key] = run
+        return run
+
+    def _launch(self, lo, hi, tables, shadow, sq, dyn=False):
+        eng, g0 = self.model.engine, self.param_groups[0]
+        run = self._run_for(lo, hi)
+        for a, b in run.adam_runs:
+            FusedAdamW._launch(self, a, b, tables, shadow, sq, dyn=dyn)
+        if self._last_step != self._step:
+            self._last_runs, self._last_step = [], self._step
+        if run.tables is None:
+            return
+        if run not in self._last_runs:
+            self._last_runs.append(run)
+        vf.muon_momentum(eng.grads, self._buf, self._x[1], run.tables, run.part, momentum=g0["momentum"], nesterov=g0["nesterov"],
+                         sqnorm=sq, max_norm=float(self._clip or 0.0))
+        vf.muon_norms(run.tables, run.part, run.inv_norm, run.norms, eps=g0["muon_eps"])
+        vf.muon_normalize(self._x[1], self._x[0], run.tables, run.inv_norm)
+        out = run.plan.iterate(g0["ns_steps"], start=0)
+        vf.muon_apply(eng.flat, shadow, out, run.tables, tables.groups)
+
+    @property
+    def last_ns_norms(self):
+        """(names, norms): ||X0||_F of every matrix the last step orthogonalised, in flat-buffer order; `norms` is a device tensor
+        (reading it synchronises).  None before the first step."""
+        if not self._last_runs:
+            return None
+        return [n for r in self._last_runs for n in r.names], torch.cat([r.norms for r in self._last_runs])
+
+    def _graph_signature(self):
+        return super()._graph_signature(), tuple(m[1].requires_grad for m in self._matrices())
+
+    def _graph_validate(self, signature):
+        partition, frozen = signature
+        super()._graph_validate(partition)
+        if frozen != tuple(m[1].requires_grad for m in self._matrices()):
+            raise ValueError("a Muon matrix was frozen or released after the step was captured")
+
+    # ------------------------------------------------------------------ state: torch.optim.Muon's for a matrix, AdamW's for the rest
+    def state_dict(self):
+        sd = super().state_dict()
+        if self._buf is not None and self._step > 0:
+            index = {id(p): i for i, p in enumerate(self._all_params())}
+            for _, p, _, xoff, rows, cols in self._matrices():
+                sd["state"][index[id(p)]] = {
+                    "momentum_buffer": self._buf[xoff:xoff + rows * cols].detach().cpu().clone().view(rows, cols)}
+        return sd
+
+    def load_state_dict(self, sd):
+        if "state" not in sd:  # FusedAdamW's round-1 layout (flat moment buffers): no momentum buffers in it
+            return super().load_state_dict(sd)
+        params = self._all_params()
+        mats = {id(m[1]): m for m in self._matrices()}
+        dev, size = self.model.engine.flat.device, max(self._mat_total, 8)
+        if self._buf is not None and self._buf.device == dev and self._buf.numel() == size:
+            self._buf.zero_()  # in place: a captured step holds the buffer's address (and the cached runs stay valid)
+        else:
+            self._buf, self._runs = torch.zeros(size, dtype=torch.float32, device=dev), {}
+        rest = {}
+        for idx, st in sd["state"].items():
+            m = mats.get(id(params[int(idx)]))
+            if m is not None and "momentum_buffer" in st:
+                self._buf[m[3]:m[3] + m[4] * m[5]].copy_(st["momentum_buffer"].reshape(-1))
+            elif m is None:
+                rest[idx] = st
+        super().load_state_dict({"state": rest, "param_groups": sd.get("param_groups", [])})
+        for grp in self.param_groups:
+            grp["ns_coefficients"] = tuple(grp["ns_coefficients"])
+
+
 class FusedSGD(FusedOptimizer):
     """SGD over MyViT's flat buffers (see FusedOptimizer).  `step()` == torch.optim.SGD.step() with dampening 0.
     `param_groups[0]` carries torch SGD's keys, and `lr` and `momentum` are read from it on every step: a one-cycle scheduler
@@ -699,8 +905,13 @@ class OptModule:
     a one-cycle scheduler gets the groups' rates as its `max_lr` list (a scalar would flatten them)."""
 
     def __init__(self, lr, monitor_metric="loss", opt_type="adam", weight_decay=0.0, lr_scheduler_name=None,
-                 warmup_ratio=0.0, warmup_epochs=None, no_decay=None, layer_decay=None, lamb_options=None, **kwargs) -> None:
+                 warmup_ratio=0.0, warmup_epochs=None, no_decay=None, layer_decay=None, lamb_options=None, muon_options=None,
+                 **kwargs) -> None:
         self.lamb_options = dict(lamb_options or {})  # eps / always_adapt / trust_clip of `type: lamb`
+        self.muon_options = dict(muon_options or {})  # the `opt.muon` section of `type: muon`
+        unknown = sorted(set(self.muon_options) - set(_MUON_KEYS))
+        if unknown:
+            raise ValueError(f"opt.muon: unknown keys {unknown}; known: {list(_MUON_KEYS)}")
         self.no_decay = no_decay
         self.layer_decay = None if layer_decay is None else float(layer_decay)
         self.lr = float(lr)
@@ -729,6 +940,8 @@ class OptModule:
                 common[key] = config[key]
         if common["opt_type"] == "lamb":  # read only for this type
             common["lamb_options"] = {k: config[k] for k in ("eps", "always_adapt", "trust_clip") if config.get(k) is not None}
+        if common["opt_type"] == "muon":  # likewise: the `opt.muon` section
+            common["muon_options"] = dict(config.get("muon") or {})
         if "lr_sch" not in config:
             return cls(**common)
         name = config["lr_sch"].lower()
@@ -744,6 +957,12 @@ class OptModule:
                 raise ValueError("opt.type 'lamb' is the fused LAMB over a MyViT's flat buffers (FusedLamb); torch has no LAMB "
                                  f"to fall through to for a {type(model).__name__}")
             return FusedLamb(model, lr=self.lr, weight_decay=self.weight_decay, **self.lamb_options, **fused)
+        if self.opt_type == "muon":  # torch.optim.Muon refuses every parameter that is not 2-D: nothing to fall through to either
+            if not isinstance(model, MyViT):
+                raise ValueError("opt.type 'muon' is the fused Muon + AdamW hybrid over a MyViT's flat buffers (FusedMuon); "
+                                 f"there is nothing to fall through to for a {type(model).__name__}")
+            opts = {("muon_eps" if k == "eps" else k): v for k, v in self.muon_options.items()}
+            return FusedMuon(model, lr=self.lr, weight_decay=self.weight_decay, **opts, **fused)
         if isinstance(model, MyViT) and self.opt_type in ("adam", "adamw"):
             # torch.optim.Adam's weight_decay is L2-in-the-gradient; with the reference's default weight_decay=0
             # (optimizer.py:51) Adam == AdamW, and only with a decay does 'adam' need the L2 form of the kernel
